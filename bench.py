@@ -21,9 +21,19 @@ on the GPU by the library's own kernels before the timed region; all inputs are 
 HBM when timing starts.  With N GPUs every rank holds its own 1024 detectors of a 1024 N
 detector focalplane observing the same scan (weak scaling, detector-sharded like configs[3]).
 
-Usage:  python bench.py [--gpus N] [--steps K] [--warmup W] [--workload cfg3|cfg2]
+Usage:  python bench.py [--gpus N] [--steps K] [--warmup W] [--workload cfg3|cfg2] [--full] [--dump-outputs DIR]
         (N > 1: one rank per GPU -- either launched by torch.distributed.run, or, when called
         as plain `python bench.py --gpus N`, bench.py starts that launcher itself as a child process)
+
+A plain run sets up, warms up, times the K steps and prints the line (metric, value, unit, ms_per_step, the
+kernels' own event times and the roofline figures derived from them).  Everything else it can measure -- the
+operator-level workflow, the CPU baseline, the FFT noise weighting, the offset-template left-hand sides, stream
+ceilings, lane widths, the expansion kernels' timings, the communicator's modes and the configs[3] shard of an
+8-GPU run -- is part of the line only with --full.
+
+--dump-outputs DIR: after the timed steps, rank 0 writes what the last step computed -- the map C A^T N^-1 d
+(zmap.npy) and the noise-weighted residual timestream (tod2.npy), float64 -- into DIR; an output of more than
+3 M values is written as a fixed, seeded sample of them (the same elements in every run of the same workload).
 """
 
 import argparse
@@ -79,7 +89,37 @@ def parse():
                          "(default: cfg4 when --gpus 8 runs the default workload)")
     ap.add_argument("--hwp", action="store_true", help="rotating half-wave plate (88 rpm): Stokes weights with HWP angle")
     ap.add_argument("--unfused", action="store_true", help="run noise_weight as its own kernel (105 B variant)")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="also run every measurement beside the headline (operator level, CPU baseline, FFT, offset-template "
+                         "left-hand sides, stream ceilings, lane widths, expansion kernels, communicator modes, cfg4 shard)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the last timed step computed (zmap, tod2) as DIR/<name>.npy")
+    args = ap.parse_args()
+    if args.pcg_extra and not args.full:
+        ap.error("--pcg-extra is a measurement of --full")
+    return args
+
+
+DUMP_MAX_VALUES = 3 << 20      # per output: 24 MB of float64, 48 MB for the two
+
+
+def dump_outputs(path, workload, outputs):
+    """Write {name: device tensor} as path/<name>.npy (float64).  A tensor of more than DUMP_MAX_VALUES elements is written
+    as the sorted, seeded sample of its flattened elements that depends only on the workload, the name and the size."""
+    import zlib
+
+    import torch
+
+    os.makedirs(path, exist_ok=True)
+    for name, t in outputs.items():
+        flat = t.reshape(-1)
+        if flat.numel() > DUMP_MAX_VALUES:
+            rng = np.random.default_rng(zlib.crc32(("%s/%s/%d" % (workload, name, flat.numel())).encode()))
+            pick = np.unique(rng.integers(0, flat.numel(), size=DUMP_MAX_VALUES, dtype=np.int64))
+            host = flat[torch.from_numpy(pick).to(flat.device)].cpu().numpy()
+        else:
+            host = t.cpu().numpy()
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(host, dtype=np.float64))
 
 
 def _map_residual_vs_reference():
@@ -297,15 +337,15 @@ def main():
         else:
             dist.init_process_group("nccl", device_id=dev)
     op_level = None
-    if (rank == 0 and world == 1 and args.workload == "cfg3" and not args.no_operator_level
+    if (args.full and rank == 0 and world == 1 and args.workload == "cfg3" and not args.no_operator_level
             and not args.no_cpu_baseline):
-        # (like the CPU baseline an extra of the default invocation only: profiling runs pass --no-cpu-baseline.)
+        # (like the CPU baseline an extra of --full only, and not with --no-cpu-baseline.)
         # First, while the process holds no device memory: its allocations are then as fresh as a user's, and
         # everything it held is released again before the benchmark buffers are allocated.
         op_level = operator_level()
     out = run(args, args.workload, world, rank, dev, headline=True)
     shard = args.shard_workload
-    if shard is None and world == 8 and args.workload == "cfg3" and not args.no_cfg4:
+    if shard is None and args.full and world == 8 and args.workload == "cfg3" and not args.no_cfg4:
         shard = "cfg4"
     if shard is not None:
         # BASELINE configs[3] (4096 detectors x 4 h @ 200 Hz over 8 GPUs): the default line above is the
@@ -472,12 +512,12 @@ def run(args, workload, world, rank, dev, headline=True):
     pd_call = lambda: D.pointing_detector(fp, d_bore.data_ptr(), idx, d_quats.data_ptr(), n_samp, ivl,
                                           d_sflags.data_ptr(), n_samp, 1, stream)
     pd_call()                     # (the first pass over a fresh block also pays its first touch: 5.7 instead of ~4 ms)
-    t_pd = timed(pd_call, 2)
+    t_pd = timed(pd_call, 2) if args.full else None
     pix_call = lambda: D.pixels_healpix(idx, d_quats.data_ptr(), d_sflags.data_ptr(), n_samp, 1, idx,
                                         d_pixels.data_ptr(), n_samp, ivl, d_hsub.data_ptr(), n_submap, nps,
                                         nside, True, stream)
     pix_call()
-    t_pix = timed(pix_call, 3)
+    t_pix = timed(pix_call, 3) if args.full else None
     d_hwp = None
     if args.hwp:
         hwp_h = np.ascontiguousarray(2 * np.pi * ((np.arange(n_samp) * (88.0 / 60.0) / rate) % 1.0))
@@ -491,19 +531,22 @@ def run(args, workload, world, rank, dev, headline=True):
     sw_call = lambda: D.stokes_weights_IQU(idx, d_quats.data_ptr(), idx, d_weights.data_ptr(), n_samp, hwp_ptr, hwp_n, ivl,
                                            np.zeros(n_det), gamma, np.ones(n_det), False, stream)
     sw_call()
-    t_sw = timed(sw_call, 2)
+    t_sw = timed(sw_call, 2) if args.full else None
     drop(d_quats)
     del d_quats
-    # the same two outputs straight from the boresight (no quaternion buffer)
-    pt_x = capi.otf_pointing(d_bore.data_ptr(), fp, nside, True, nnz, d_shared_flags=d_sflags.data_ptr(),
-                             n_shared_flags=n_samp, shared_flag_mask=1, epsilon=np.zeros(n_det), gamma=gamma,
-                             cal=np.ones(n_det), d_hwp=hwp_ptr, n_hwp=hwp_n, d_hwp_table=hwp_tab_ptr)
-    pix_x = lambda: D.otf_pixels_healpix(pt_x, idx, d_pixels.data_ptr(), n_samp, ivl, d_hsub.data_ptr(), n_submap, nps, stream)
-    sw_x = lambda: D.otf_stokes_weights(pt_x, idx, d_weights.data_ptr(), n_samp, ivl, stream)
-    pix_x()        # (the first launch of a kernel also loads its code object: 5.7 instead of 3.5 ms in a process that has
-    sw_x()         #  not run the operator-level workflow before)
-    t_pix_x = timed(pix_x, 2)
-    t_sw_x = timed(sw_x, 2)
+    if args.full:
+        # the same two outputs straight from the boresight (no quaternion buffer; bit for bit the same pixels, hit submaps
+        # and weights: tests/test_gpu_otf.py)
+        pt_x = capi.otf_pointing(d_bore.data_ptr(), fp, nside, True, nnz, d_shared_flags=d_sflags.data_ptr(),
+                                 n_shared_flags=n_samp, shared_flag_mask=1, epsilon=np.zeros(n_det), gamma=gamma,
+                                 cal=np.ones(n_det), d_hwp=hwp_ptr, n_hwp=hwp_n, d_hwp_table=hwp_tab_ptr)
+        pix_x = lambda: D.otf_pixels_healpix(pt_x, idx, d_pixels.data_ptr(), n_samp, ivl, d_hsub.data_ptr(), n_submap, nps,
+                                             stream)
+        sw_x = lambda: D.otf_stokes_weights(pt_x, idx, d_weights.data_ptr(), n_samp, ivl, stream)
+        pix_x()        # (the first launch of a kernel also loads its code object: 5.7 instead of 3.5 ms in a process that
+        sw_x()         #  has not run the operator-level workflow before)
+        t_pix_x = timed(pix_x, 2)
+        t_sw_x = timed(sw_x, 2)
 
     # union of hit submaps over ranks -> one global2local for everybody
     hs = d_hsub.to(torch.int32)
@@ -655,6 +698,9 @@ def run(args, workload, world, rank, dev, headline=True):
         tmax = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         elapsed = float(tmax.item())
+    if args.dump_outputs and headline and rank == 0:
+        # (before anything below touches the map or the timestream again)
+        dump_outputs(args.dump_outputs, workload, {"zmap": d_zmap, "tod2": d_tod2})
 
     ms = {k: float(np.mean([a.elapsed_time(b) for a, b in v])) for k, v in ev.items()}
     value = world * nsamp_tot * args.steps / elapsed
@@ -793,55 +839,56 @@ def run(args, workload, world, rank, dev, headline=True):
         "iteration_GBs": (BYTES_BNW + BYTES_SCAN) * nsamp_tot / ((ms["bnw"] + ms["scan"]) * 1e-3) / 1e9,
     }
 
-    # measured stream ceiling on this box ("report % of both"): a pure
-    # 8 B read + 8 B write stream (k_noise_weight over the work timestream, scale 1.0)
-    ones = np.ones(n_det)
-    D.noise_weight(d_tod2.data_ptr(), n_samp, idx, ivl, ones, stream)
-    t_rw = timed(lambda: D.noise_weight(d_tod2.data_ptr(), n_samp, idx, ivl, ones, stream), 5)
-    stream_rw = 16.0 * nsamp_tot / t_rw / 1e6
-    roofline["stream_ceiling"] = {
-        "read_write_GBs": stream_rw,
-        "frac_of_read_write_stream": ach / stream_rw,
-        "note": "k_noise_weight_v2, a pure read + write stream (16 B per lane and access) over the same work buffer",
-    }
-    if nnz == 3 and n_samp % 2 == 0 and hasattr(capi.real_lib(), "toast_hip_probe_byte_mix_dev"):
-        # ... and the two kernels' OWN byte mixes as plain streams over the very arrays they read and write, in their launch
-        # shape (no gather, no scan, no atomics; flags left out): what the places of these arrays in HBM let such a kernel reach
-        mix_scan = lambda: capi.probe_byte_mix(d_pixels.data_ptr(), d_weights.data_ptr(), d_tod.data_ptr(), d_tod2.data_ptr(),    # noqa: E731
-                                               n_det, n_samp, stream)
-        mix_bnw = lambda: capi.probe_byte_mix(d_pixels.data_ptr(), d_weights.data_ptr(), d_tod.data_ptr(), 0, n_det, n_samp, stream)    # noqa: E731
-        mix_scan()
-        mix_bnw()
-        t_ms, t_mb = timed(mix_scan, 5), timed(mix_bnw, 5)
-        roofline["stream_ceiling"].update({
-            "scan_map_byte_mix_ms": t_ms, "scan_map_byte_mix_GBs": 48.0 * nsamp_tot / t_ms / 1e6,
-            "build_noise_weighted_byte_mix_ms": t_mb, "build_noise_weighted_byte_mix_GBs": 40.0 * nsamp_tot / t_mb / 1e6,
-            "scan_map_frac_of_its_mix": t_ms / ms["scan"], "build_noise_weighted_frac_of_its_mix": t_mb / ms["bnw"],
-            "byte_mix_note": "k_probe_byte_mix: 40 B read (+ 8 B written) per det-sample from / to the arrays of the timed kernels",
-        })
-    # the same three kernels with one sample per lane (8-byte lane accesses) and two consecutive samples per lane
-    # (16-byte lane accesses; the default), same buffers, same process
-    if headline:
-        lanes = {}
-        bnw_only = lambda: D.build_noise_weighted(d_g2l.data_ptr(), d_zmap.data_ptr(), nps, nnz, idx, d_pixels.data_ptr(),
-                                                  idx, d_weights.data_ptr(), idx, d_tod.data_ptr(), idx,
-                                                  d_dflags.data_ptr(), n_samp, det_scale, 1, n_samp, ivl,
-                                                  d_sflags.data_ptr(), n_samp, 1, stream)
-        scan_only = lambda: D.scan_map(np.float64, d_g2l.data_ptr(), nps, d_zmap.data_ptr(), nnz, d_tod2.data_ptr(), idx,
-                                       d_pixels.data_ptr(), idx, d_weights.data_ptr(), idx, n_samp, ivl, 1.0, False, True,
-                                       False, det_w, stream)
-        rw_only = lambda: D.noise_weight(d_tod2.data_ptr(), n_samp, idx, ivl, ones, stream)
-        for v2, name in ((0, "one_sample_per_lane"), (1, "two_samples_per_lane")):
-            capi.set_tuning("vec2", v2)
-            for fn in (bnw_only, scan_only, rw_only):
-                fn()
-            t_b, t_s, t_r = timed(bnw_only, 3), timed(scan_only, 3), timed(rw_only, 3)
-            lanes[name] = {"build_noise_weighted_ms": t_b, "scan_map_ms": t_s, "read_write_stream_ms": t_r,
-                           "build_noise_weighted_GBs": BYTES_BNW * nsamp_tot / t_b / 1e6,
-                           "scan_map_GBs": BYTES_SCAN * nsamp_tot / t_s / 1e6,
-                           "read_write_stream_GBs": 16.0 * nsamp_tot / t_r / 1e6}
-        capi.set_tuning("vec2", 1)
-        roofline["lane_width"] = lanes
+    if args.full:
+        # measured stream ceiling on this box ("report % of both"): a pure
+        # 8 B read + 8 B write stream (k_noise_weight over the work timestream, scale 1.0)
+        ones = np.ones(n_det)
+        D.noise_weight(d_tod2.data_ptr(), n_samp, idx, ivl, ones, stream)
+        t_rw = timed(lambda: D.noise_weight(d_tod2.data_ptr(), n_samp, idx, ivl, ones, stream), 5)
+        stream_rw = 16.0 * nsamp_tot / t_rw / 1e6
+        roofline["stream_ceiling"] = {
+            "read_write_GBs": stream_rw,
+            "frac_of_read_write_stream": ach / stream_rw,
+            "note": "k_noise_weight_v2, a pure read + write stream (16 B per lane and access) over the same work buffer",
+        }
+        if nnz == 3 and n_samp % 2 == 0 and hasattr(capi.real_lib(), "toast_hip_probe_byte_mix_dev"):
+            # ... and the two kernels' OWN byte mixes as plain streams over the very arrays they read and write, in their launch
+            # shape (no gather, no scan, no atomics; flags left out): what the places of these arrays in HBM let such a kernel reach
+            mix_scan = lambda: capi.probe_byte_mix(d_pixels.data_ptr(), d_weights.data_ptr(), d_tod.data_ptr(), d_tod2.data_ptr(),    # noqa: E731
+                                                   n_det, n_samp, stream)
+            mix_bnw = lambda: capi.probe_byte_mix(d_pixels.data_ptr(), d_weights.data_ptr(), d_tod.data_ptr(), 0, n_det, n_samp, stream)    # noqa: E731
+            mix_scan()
+            mix_bnw()
+            t_ms, t_mb = timed(mix_scan, 5), timed(mix_bnw, 5)
+            roofline["stream_ceiling"].update({
+                "scan_map_byte_mix_ms": t_ms, "scan_map_byte_mix_GBs": 48.0 * nsamp_tot / t_ms / 1e6,
+                "build_noise_weighted_byte_mix_ms": t_mb, "build_noise_weighted_byte_mix_GBs": 40.0 * nsamp_tot / t_mb / 1e6,
+                "scan_map_frac_of_its_mix": t_ms / ms["scan"], "build_noise_weighted_frac_of_its_mix": t_mb / ms["bnw"],
+                "byte_mix_note": "k_probe_byte_mix: 40 B read (+ 8 B written) per det-sample from / to the arrays of the timed kernels",
+            })
+        # the same three kernels with one sample per lane (8-byte lane accesses) and two consecutive samples per lane
+        # (16-byte lane accesses; the default), same buffers, same process
+        if headline:
+            lanes = {}
+            bnw_only = lambda: D.build_noise_weighted(d_g2l.data_ptr(), d_zmap.data_ptr(), nps, nnz, idx, d_pixels.data_ptr(),
+                                                      idx, d_weights.data_ptr(), idx, d_tod.data_ptr(), idx,
+                                                      d_dflags.data_ptr(), n_samp, det_scale, 1, n_samp, ivl,
+                                                      d_sflags.data_ptr(), n_samp, 1, stream)
+            scan_only = lambda: D.scan_map(np.float64, d_g2l.data_ptr(), nps, d_zmap.data_ptr(), nnz, d_tod2.data_ptr(), idx,
+                                           d_pixels.data_ptr(), idx, d_weights.data_ptr(), idx, n_samp, ivl, 1.0, False, True,
+                                           False, det_w, stream)
+            rw_only = lambda: D.noise_weight(d_tod2.data_ptr(), n_samp, idx, ivl, ones, stream)
+            for v2, name in ((0, "one_sample_per_lane"), (1, "two_samples_per_lane")):
+                capi.set_tuning("vec2", v2)
+                for fn in (bnw_only, scan_only, rw_only):
+                    fn()
+                t_b, t_s, t_r = timed(bnw_only, 3), timed(scan_only, 3), timed(rw_only, 3)
+                lanes[name] = {"build_noise_weighted_ms": t_b, "scan_map_ms": t_s, "read_write_stream_ms": t_r,
+                               "build_noise_weighted_GBs": BYTES_BNW * nsamp_tot / t_b / 1e6,
+                               "scan_map_GBs": BYTES_SCAN * nsamp_tot / t_s / 1e6,
+                               "read_write_stream_GBs": 16.0 * nsamp_tot / t_r / 1e6}
+            capi.set_tuning("vec2", 1)
+            roofline["lane_width"] = lanes
 
     out = {
         "metric": "detector-samples/sec through one PCG (A^T N^-1 A) iteration",
@@ -878,7 +925,7 @@ def run(args, workload, world, rank, dev, headline=True):
             "three_kernel_chain_ms": t_pd + t_pix + t_sw,
             "from_boresight_pixels_ms": t_pix_x,
             "from_boresight_weights_ms": t_sw_x,
-        },
+        } if args.full else None,
         "setup_s": t_setup,
         "allocator": allocator,
         "placement": placement,
@@ -904,7 +951,7 @@ def run(args, workload, world, rank, dev, headline=True):
 
     if headline and world > 1:
         _lifeline_arm(out, rank)
-    if comm_impl is not None and comm_impl.startswith("toast_hip_comm"):
+    if args.full and comm_impl is not None and comm_impl.startswith("toast_hip_comm"):
         # the same sum + covariance as ONE owner-computes pass (reduce-scatter, cov_apply_diag on the owned pixel
         # shard, all-gather): what ops.BinMap / the fused SolverLHS do with sync_type = "alltoallv"
         oc = lambda: D.comm_map_reduce_apply(n_local * nps, nnz, d_cov.data_ptr(), d_zmap.data_ptr(), True, stream)
@@ -978,7 +1025,7 @@ def run(args, workload, world, rank, dev, headline=True):
     # "report separately"): ops.NoiseFilter's device call on the same timestream shape -- every detector
     # row convolved with its own N_tt'^-1 = NET^2 / PSD(f) kernel (reference src/toast/ops/noise_filter.py:130-188
     # -> toast.fft.convolve, src/toast/fft.py:252-350).  Not part of the PCG step; timed once per run.
-    if not args.no_fft:
+    if args.full and not args.no_fft:
         from toast_amd import fft as hipfft
         from toast_amd.noise import AnalyticNoise
 
@@ -1061,7 +1108,7 @@ def run(args, workload, world, rank, dev, headline=True):
     # sequence (8 + 41 + 8 + 48 + 9 B per det-sample, five passes) and fused (33 + 33 B, two passes).
     # The complete left-hand side with one Offset template on the same buffers (operator sequence, fused sweeps, fused
     # sweeps from the packed pointing cache): part of every run; the on-the-fly / compact variants only with --pcg-extra.
-    if not args.no_lhs and nnz == 3 and not args.torch_alloc:
+    if args.full and not args.no_lhs and nnz == 3 and not args.torch_alloc:
         # the two set-up sweeps of a destriping run that read the same pixels / weights / flags -- solver covariance + hits,
         # then the right-hand side's A^T N^-1 d -- apart and as ONE sweep (toast_hip_build_cov_hits_signal_dev)
         d_invcov = manager_tensor(n_local * nps * 6 * 8, torch.float64, (n_local, nps, 6), scatter=True)
@@ -1097,7 +1144,7 @@ def run(args, workload, world, rank, dev, headline=True):
         manager_release(d_invcov)
         manager_release(d_hits)
         del d_invcov, d_hits
-    if args.pcg_extra or not args.no_lhs:
+    if args.full and (args.pcg_extra or not args.no_lhs):
         step_len = int(rate)  # 1 s baselines
         nav = np.array([(int(v["last"]) - int(v["first"]) + step_len - 1) // step_len for v in ivl], dtype=np.int64)
         n_amp_det = int(nav.sum())
@@ -1345,7 +1392,7 @@ def run(args, workload, world, rank, dev, headline=True):
         }
 
     # ------------------------------------------------------------------ CPU baseline (rank 0, N=1)
-    if world == 1 and rank == 0 and headline and not args.no_cpu_baseline:
+    if args.full and world == 1 and rank == 0 and headline and not args.no_cpu_baseline:
         import oracle
 
         nd = min(args.cpu_dets, n_det)

@@ -13,7 +13,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 def test_bench_contract_small_workload():
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
-                          "--workload", "mini", "--cpu-dets", "4", "--pcg-extra"], capture_output=True, text=True,
+                          "--workload", "mini", "--cpu-dets", "4", "--pcg-extra", "--full"], capture_output=True, text=True,
                          timeout=600, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
@@ -74,6 +74,34 @@ def test_bench_contract_small_workload():
     assert d["compact_pixels_weights_on_the_fly"]["offset_lhs_vs_sequence_max_rel_diff"] < 1e-12
 
 
+def test_bench_plain_run_and_dump_outputs(tmp_path):
+    """A plain run (no --full) times the steps it is asked for, carries the headline keys and none of the extras, and
+    --dump-outputs writes the last step's map and timestream as float64 .npy files (whole arrays at this size)."""
+    import numpy as np
+
+    dump = tmp_path / "out"
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "4", "--warmup", "1",
+                          "--workload", "mini", "--dump-outputs", str(dump)], capture_output=True, text=True, timeout=600,
+                         cwd=ROOT)
+    assert out.returncode == 0, out.stderr[-2000:]
+    lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1
+    d = json.loads(lines[0])
+    for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "kernel_ms", "roofline"):
+        assert key in d, key
+    assert d["steps"] == 4 and d["warmup"] == 1 and d["ms_per_step"] > 0 and d["dtype"] == "f64"
+    n = d["config"]["detectors_per_gpu"] * d["config"]["samples_per_detector"]
+    assert abs(d["value"] - n / (d["ms_per_step"] * 1e-3)) < 1e-6 * d["value"]
+    for key in ("cpu_baseline", "fft_noise_weight", "pcg_lhs_offset_templates", "mapmaker_setup_sweeps", "operator_level"):
+        assert key not in d, key
+    assert "stream_ceiling" not in d["roofline"] and d["expansion"] is None
+    zmap, tod2 = np.load(dump / "zmap.npy"), np.load(dump / "tod2.npy")
+    assert zmap.dtype == np.float64 and tod2.dtype == np.float64
+    assert zmap.shape == (d["config"]["n_local_submap"], 3072, 3) and tod2.shape == (16, 50000)
+    assert np.all(np.isfinite(zmap)) and np.all(np.isfinite(tod2)) and np.any(zmap != 0) and np.any(tod2 != 0)
+    assert sum(f.stat().st_size for f in dump.iterdir()) <= 64 << 20
+
+
 def test_bench_two_ranks_code_path():
     """bench.py --gpus 2 as the driver launches it (torch.distributed.run, one rank per GPU), here
     with both ranks sharing the one GPU and gloo instead of RCCL (TOAST_BENCH_SHARE_GPU=1): rank 0
@@ -125,7 +153,7 @@ def test_bench_collective_path_with_one_rank():
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")}
     env.update(TOAST_BENCH_SINGLE_RANK_COMM="1", OMP_NUM_THREADS="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--workload",
-                          "mini", "--no-fft", "--no-cpu-baseline", "--shard-workload", "cfg2"], capture_output=True,
+                          "mini", "--no-fft", "--no-cpu-baseline", "--shard-workload", "cfg2", "--full"], capture_output=True,
                          text=True, timeout=900, cwd=ROOT, env=env)
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-4000:]
     assert len(out.stdout.strip().splitlines()) == 1, out.stdout[:600]     # nothing but the JSON line on stdout

@@ -89,7 +89,7 @@ def test_bench_ranks_through_the_library_communicator(mock_lib, n):
                                                              "MASTER_PORT")}
     env.update(TOAST_BENCH_SHARE_GPU="1", OMP_NUM_THREADS="1", TOAST_HIP_RCCL_LIB=mock_lib)
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(n), "--steps", "2", "--warmup",
-                          "1", "--workload", "mini", "--no-fft", "--shard-workload", "cfg2"], capture_output=True,
+                          "1", "--workload", "mini", "--no-fft", "--shard-workload", "cfg2", "--full"], capture_output=True,
                          text=True, timeout=900, cwd=ROOT, env=env)
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-4000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]

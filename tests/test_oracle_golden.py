@@ -1,5 +1,5 @@
-"""CPU: the oracle restatement against the reference's own outputs (golden fixtures), the
-reference's known-answer values, and -- when oracle/_ref is present -- the live reference."""
+"""CPU: the oracle restatement against the reference's own outputs (golden fixtures and the recorded outputs of the
+reference build, tests/golden/reference_outputs.json) and the reference's known-answer values."""
 import os
 
 import numpy as np
@@ -118,15 +118,25 @@ def test_hits_and_invcov_fixture_vs_python_loop(name):
     np.testing.assert_allclose(invcov, g[name + "_invcov"], rtol=1e-13, atol=1e-13 * np.max(np.abs(invcov)))
 
 
-def test_cov_apply_diag_live_reference(oracle, ref):
+# The tests "vs live reference" below run the oracle on cases drawn from fixed seeds and require its products to be bit for
+# bit the reference's own (oracle/_ref) on the same cases.  The reference's products are recorded in
+# tests/golden/reference_outputs.json by tests/golden/make_golden_reference_outputs.py, which calls the functions below with
+# the reference build (``tail = (False,)``: the trailing use_accel of its bindings); the tests call them with the oracle.
+
+
+def cov_apply_diag_outputs(impl, tail=()):
     rng = np.random.default_rng(4)
+    out = {}
     for nnz in (1, 2, 3):
         mat = rng.standard_normal((4, 33, nnz * (nnz + 1) // 2))
         a = rng.standard_normal((4, 33, nnz))
-        b = a.copy()
-        ref.cov_apply_diag(4, 33, nnz, mat.reshape(-1), a.reshape(-1))
-        oracle.cov_apply_diag(4, 33, nnz, mat, b)
-        assert np.array_equal(a, b)
+        impl.cov_apply_diag(4, 33, nnz, mat.reshape(-1), a.reshape(-1), *tail)
+        out["nnz%d" % nnz] = a
+    return out
+
+
+def test_cov_apply_diag_live_reference(oracle):
+    gu.assert_reference_outputs("cov_apply_diag", cov_apply_diag_outputs(oracle))
 
 
 LIVE = {
@@ -145,29 +155,33 @@ LIVE = {
 }
 
 
+def live_chain_outputs(impl, name, nest, tail=()):
+    return cases.run_chain(impl, cases.make_case(**LIVE[name]), nest=nest, tail=tail)
+
+
 @pytest.mark.parametrize("name", list(LIVE))
 @pytest.mark.parametrize("nest", [True, False])
-def test_oracle_vs_live_reference(oracle, ref, name, nest):
-    c = cases.make_case(**LIVE[name])
-    a = cases.run_chain(ref, c, nest=nest, tail=(False,))
-    b = cases.run_chain(oracle, c, nest=nest)
-    for k in a:
-        assert np.array_equal(a[k], b[k]), k
+def test_oracle_vs_live_reference(oracle, name, nest):
+    gu.assert_reference_outputs("chain/%s/%s" % (name, nest), live_chain_outputs(oracle, name, nest))
+
+
+SCAN_DTYPES = {"float32": np.float32, "int64": np.int64, "int32": np.int32}
+
+
+def scan_map_dtype_outputs(impl, map_dtype, tail=()):
+    c = cases.make_case(n_samp=3000, nside=128, n_split=2)
+    return {"tod": cases.run_chain(impl, c, map_dtype=map_dtype, scan_scale=0.37, tail=tail)["tod"]}
 
 
 @pytest.mark.parametrize("map_dtype", [np.float32, np.int64, np.int32])
-def test_oracle_scan_map_dtypes_vs_live_reference(oracle, ref, map_dtype):
-    c = cases.make_case(n_samp=3000, nside=128, n_split=2)
-    a = cases.run_chain(ref, c, map_dtype=map_dtype, scan_scale=0.37, tail=(False,))
-    b = cases.run_chain(oracle, c, map_dtype=map_dtype, scan_scale=0.37)
-    assert np.array_equal(a["tod"], b["tod"])
+def test_oracle_scan_map_dtypes_vs_live_reference(oracle, map_dtype):
+    gu.assert_reference_outputs("scan_map/%s" % np.dtype(map_dtype).name, scan_map_dtype_outputs(oracle, map_dtype))
 
 
-@pytest.mark.parametrize("nside", [1, 1 << 14, 1 << 20, 1 << 29])
-def test_oracle_pixels_on_boundaries_vs_live_reference(oracle, ref, nside):
-    """The pointings of tests/test_gpu_pixels_adversarial.py (|z| = 2/3, poles, face meridians within
-    0 .. 1e3 ulp) through the reference's own compiled kernel and the oracle: identical indices up
-    to the largest nside."""
+BOUNDARY_NSIDES = [1, 1 << 14, 1 << 20, 1 << 29]
+
+
+def pixels_on_boundaries_outputs(impl, nside, tail=()):
     from test_gpu_pixels_adversarial import boundary_pointings
 
     q = boundary_pointings(np.random.default_rng(nside % 9973), n_each=1500)
@@ -178,19 +192,27 @@ def test_oracle_pixels_on_boundaries_vs_live_reference(oracle, ref, nside):
     npix = 12 * nside * nside
     nps = npix if nside < 16 else npix // 3072
     idx, flags = np.zeros(1, np.int32), np.zeros(1, np.uint8)
+    out = {}
     for nest in (True, False):
-        a = np.full((1, n), -7, np.int64)
-        b = np.full((1, n), -9, np.int64)
-        ha, hb = np.zeros(npix // nps, np.uint8), np.zeros(npix // nps, np.uint8)
-        ref.pixels_healpix(idx, quats, flags, 0, idx, a, iv, ha, nps, nside, nest, False)
-        oracle.pixels_healpix(idx, quats, flags, 0, idx, b, iv, hb, nps, nside, nest)
-        assert np.array_equal(a, b) and np.array_equal(ha, hb)
+        pix = np.full((1, n), -7, np.int64)
+        hsub = np.zeros(npix // nps, np.uint8)
+        impl.pixels_healpix(idx, quats, flags, 0, idx, pix, iv, hsub, nps, nside, nest, *tail)
+        out["pixels_%s" % nest], out["hsub_%s" % nest] = pix, hsub
+    return out
 
 
-@pytest.mark.parametrize("seed", list(range(24)))
-def test_oracle_vs_live_reference_random(oracle, ref, seed):
-    """The same randomly drawn chain cases as tests/test_gpu_parity.py::test_chain_random_cases: the oracle and the
-    reference's own compiled kernels agree bit for bit on every product."""
+@pytest.mark.parametrize("nside", BOUNDARY_NSIDES)
+def test_oracle_pixels_on_boundaries_vs_live_reference(oracle, nside):
+    """The pointings of tests/test_gpu_pixels_adversarial.py (|z| = 2/3, poles, face meridians within
+    0 .. 1e3 ulp) through the reference's own compiled kernel and the oracle: identical indices up
+    to the largest nside."""
+    gu.assert_reference_outputs("boundaries/%d" % nside, pixels_on_boundaries_outputs(oracle, nside))
+
+
+RANDOM_SEEDS = list(range(24))
+
+
+def random_chain_outputs(impl, seed, tail=()):
     rng = np.random.default_rng(5000 + seed)
     n_samp = int(rng.integers(1, 3000))
     kw = dict(
@@ -210,11 +232,14 @@ def test_oracle_vs_live_reference_random(oracle, ref, seed):
     if kw["n_det"] == 1:
         kw["extra_rows"] = 0
     nest, iau = bool(rng.integers(0, 2)), bool(rng.integers(0, 2))
-    c = cases.make_case(**kw)
-    a = cases.run_chain(ref, c, nest=nest, iau=iau, tail=(False,))
-    b = cases.run_chain(oracle, c, nest=nest, iau=iau)
-    for k in a:
-        assert np.array_equal(a[k], b[k]), k
+    return cases.run_chain(impl, cases.make_case(**kw), nest=nest, iau=iau, tail=tail)
+
+
+@pytest.mark.parametrize("seed", RANDOM_SEEDS)
+def test_oracle_vs_live_reference_random(oracle, seed):
+    """The same randomly drawn chain cases as tests/test_gpu_parity.py::test_chain_random_cases: the oracle and the
+    reference's own compiled kernels agree bit for bit on every product."""
+    gu.assert_reference_outputs("random/%d" % seed, random_chain_outputs(oracle, seed))
 
 
 def test_mapmaker_e2e_fixture_is_what_the_reference_chain_produces_now():

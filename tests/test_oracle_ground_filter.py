@@ -1,5 +1,6 @@
 """CPU: pin oracle/ground_filter.py against the outputs of the reference's own tod_filter kernels
-(tests/golden/cov_filter.npz, produced by tests/golden/make_golden_cov.py from oracle/_ref)."""
+(tests/golden/cov_filter.npz, produced by tests/golden/make_golden_cov.py from oracle/_ref, and
+tests/golden/reference_outputs.json, recorded by tests/golden/make_golden_reference_outputs.py)."""
 import numpy as np
 import pytest
 
@@ -35,28 +36,48 @@ def test_projection_gram_fit_and_subtraction(gold):
         assert abs(coeff[3 + 2] - 3.0) < 0.1 and abs(coeff[0] + 1.5) < 0.1
 
 
-def test_live_reference_kernels(ref):
+LEGENDRE_SPANS = ((0, 1), (0, 2), (1, 2), (1, 6), (0, 9), (3, 7))
+
+
+def _live_case():
     rng = np.random.default_rng(8)
     n = 2500
     x = np.sort(rng.uniform(-1, 1, n))
-    for start, stop in ((0, 1), (0, 2), (1, 2), (1, 6), (0, 9), (3, 7)):
-        want = np.zeros((stop - start, n))
-        ref.legendre_templates(x, want, start, stop)
-        assert np.array_equal(GF.legendre_templates(x, start, stop), want)
-    t = GF.legendre_templates(x, 0, 5)
     sig = rng.standard_normal(n)
     good = (rng.random(n) > 0.2).astype(np.uint8)
+    c = rng.standard_normal(5)
+    return x, GF.legendre_templates(x, 0, 5), sig, good, c
+
+
+def reference_kernel_outputs(ref):
+    """The reference's tod_filter kernels (oracle/_ref) on the case of test_live_reference_kernels; recorded in
+    tests/golden/reference_outputs.json by tests/golden/make_golden_reference_outputs.py."""
+    x, t, sig, good, c = _live_case()
+    out = {}
+    for start, stop in LEGENDRE_SPANS:
+        want = np.zeros((stop - start, x.size))
+        ref.legendre_templates(x, want, start, stop)
+        out["legendre_%d_%d" % (start, stop)] = want
     proj = np.zeros(5)
     inv = np.zeros((5, 5))
     ref.bin_proj(sig, t, good, proj)
     ref.bin_invcov(t, good, inv)
-    assert np.allclose(GF.bin_proj(sig, t, good), proj, rtol=1e-12, atol=1e-12)
-    assert np.allclose(GF.bin_invcov(t, good), inv, rtol=1e-12, atol=1e-12)
-    a, b = sig.copy(), sig.copy()
-    c = rng.standard_normal(5)
+    a = sig.copy()
     ref.add_templates(a, t, c)
+    out.update(proj=proj, invcov=inv, added=a)
+    return out
+
+
+def test_live_reference_kernels():
+    want = gu.reference_outputs("ground_filter")
+    x, t, sig, good, c = _live_case()
+    for start, stop in LEGENDRE_SPANS:
+        assert gu.fingerprint(GF.legendre_templates(x, start, stop)) == want["legendre_%d_%d" % (start, stop)]
+    assert np.allclose(GF.bin_proj(sig, t, good), np.array(want["proj"]), rtol=1e-12, atol=1e-12)
+    assert np.allclose(GF.bin_invcov(t, good), np.array(want["invcov"]), rtol=1e-12, atol=1e-12)
+    b = sig.copy()
     GF.add_templates(b, t, c)
-    assert np.array_equal(a, b)
+    assert gu.fingerprint(b) == want["added"]
 
 
 def test_build_templates_shapes_and_split():

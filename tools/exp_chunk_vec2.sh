@@ -4,7 +4,7 @@
 out=${1:-gpurun_out/r03a/chunk_sweep.txt}
 mkdir -p $(dirname $out); : > $out
 for c in 512 1024 2048 4096; do
-  TOAST_HIP_CHUNK=$c python bench.py --no-cpu-baseline --no-fft --no-operator-level --steps 5 --warmup 2 2>/dev/null | python -c "
+  TOAST_HIP_CHUNK=$c python bench.py --full --no-cpu-baseline --no-fft --no-operator-level --steps 5 --warmup 2 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1])
 l=d['roofline']['lane_width']

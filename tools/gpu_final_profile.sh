@@ -4,11 +4,12 @@
 tag=${1:-x}
 out=$GRAFT_REPO_ROOT/gpurun_out/$tag
 mkdir -p $out
-python bench.py > $out/bench.json 2> $out/bench.err
+repo=$PWD
+python bench.py --full > $out/bench.json 2> $out/bench.err
 cd /tmp && export TMPDIR=/tmp
 # the traced process with the library's own log of the slab search (TOAST_HIP_TRACE=1 prints; it does not synchronise)
 export TOAST_HIP_TRACE=1
-timeout -k 5 900 rocprofv3 --kernel-trace --stats -d $out/trace -o bench -- python3 $GRAFT_REPO_ROOT/bench.py --steps 10 --warmup 3 --no-cpu-baseline > $out/trace.json 2> $out/trace.err
+timeout -k 5 900 rocprofv3 --kernel-trace --stats -d $out/trace -o bench -- python3 $repo/bench.py --steps 10 --warmup 3 --no-cpu-baseline --full > $out/trace.json 2> $out/trace.err
 unset TOAST_HIP_TRACE
 # A trace of a process whose zone placement did not work out is not a profile of the line (round 5: 1 chunk of 8 in the
 # other zone under the profiler, scan_map 12 % slower than in the line): refuse to turn it into profiles/ text.
