@@ -841,6 +841,70 @@ int toast_hip_template_subtract_dev(
     void * stream);
 
 /* ------------------------------------------------------------------------------------
+ * Polynomial and common-mode filters for toast.ops.PolyFilter / toast.ops.CommonModeFilter
+ * (device-resident buffers; host index and interval arrays)
+ *
+ * toast_hip_filter_polynomial_dev replaces `filter_polynomial` of src/libtoast/src/toast_tod_filter.cpp:18-158
+ * (binding src/toast/_libtoast/tod_filter.cpp:326-383), which the reference calls once per group of detectors
+ * with identical flags (src/toast/ops/polyfilter/polyfilter.py:556-602).  For every detector row signal_index[d]
+ * and every interval [starts[v], stops[v]) clipped to [0, n_samp) -- the stop is EXCLUSIVE, like the compiled
+ * reference kernel -- with good[i] = !(shared_flags[i] & shared_flag_mask) && !(det_flags[d][i] & det_flag_mask):
+ *   ngood == 0 leaves the interval untouched; norder = min(ngood, order + 1); the Legendre templates of
+ *   x_i = (0.5 dx - 1) + i dx, dx = 2 / scanlen (same recurrence) are fitted to the good samples by least squares
+ *   (normal equations, Cholesky in fp64) and the fit is subtracted from ALL samples of the interval.
+ * d_coeff [n_det][n_interval][order + 1] receives the coefficients (zero beyond norder), d_status
+ * [n_det][n_interval] one of TOAST_HIP_POLY_*; both are required.  With TOAST_HIP_POLY_NOT_POSITIVE (a Cholesky
+ * pivot was not positive) the signal is left untouched.  Nothing throws from the device.  order < 0 is a no-op;
+ * order + 1 > 16 is an error.  d_det_flags / d_shared_flags may be NULL.
+ * path: 0 = by the rule -- an interval of at most toast_hip_filter_polynomial_stage_cap() samples is filtered by
+ * one workgroup that stages it in LDS (one read and one write of the signal), a longer one in two passes (partial
+ * Gram matrices per chunk, reduced in chunk order; then the subtraction) --, 1 = single pass for every interval
+ * (an error when one exceeds the cap), 2 = two passes for every interval.  Both paths are order-deterministic.
+ *
+ * toast_hip_sum_detectors_dev / toast_hip_subtract_mean_dev replace `sum_detectors` / `subtract_mean` of
+ * src/toast/_libtoast/tod_filter.cpp:9-97: d_sum[i] += signal[row_d][i], d_hits[i]++ over the listed detectors
+ * whose shared and detector flags are clear, in list order (the reference's summation order: bit-identical);
+ * then d_sum[i] /= d_hits[i] where d_hits[i] != 0 and signal[row_d][i] -= d_sum[i] for all listed rows.
+ * toast_hip_subtract_mean_dev with n_det == 0 is NOT a no-op: it still turns d_sum into the mean where d_hits != 0 and
+ * subtracts from no row (CommonModeFilter's regression takes its mean template that way).
+ * toast_hip_common_mode_subtract_dev does all of it in one launch starting from sum = 0, hits = 0; d_mean /
+ * d_hits are written only when non-NULL.  It sweeps the rows twice (sum, then subtract) with the mean in a register:
+ * 25 B per detector-sample (two reads and one write of the signal, one of the flags).
+ * ---------------------------------------------------------------------------------- */
+#define TOAST_HIP_POLY_FITTED 0
+#define TOAST_HIP_POLY_NO_GOOD 1
+#define TOAST_HIP_POLY_REDUCED 2
+#define TOAST_HIP_POLY_NOT_POSITIVE 3
+int toast_hip_filter_polynomial_stage_cap(void);
+int toast_hip_filter_polynomial_dev(
+    int64_t order, int64_t n_samp, const int32_t * signal_index /*host*/, double * d_signal,
+    const int32_t * flag_index /*host*/, const uint8_t * d_det_flags, uint8_t det_flag_mask,
+    const uint8_t * d_shared_flags, uint8_t shared_flag_mask, int64_t n_det, const int64_t * starts /*host*/,
+    const int64_t * stops /*host*/, int64_t n_interval, double * d_coeff, int32_t * d_status, int path, void * stream);
+int toast_hip_sum_detectors_dev(
+    int64_t n_samp, const int32_t * signal_index /*host*/, const double * d_signal, const int32_t * flag_index /*host*/,
+    const uint8_t * d_det_flags, uint8_t det_flag_mask, const uint8_t * d_shared_flags, uint8_t shared_flag_mask,
+    int64_t n_det, double * d_sum, int64_t * d_hits, void * stream);
+int toast_hip_subtract_mean_dev(int64_t n_samp, const int32_t * signal_index /*host*/, double * d_signal, int64_t n_det,
+                                double * d_sum, const int64_t * d_hits, void * stream);
+int toast_hip_common_mode_subtract_dev(
+    int64_t n_samp, const int32_t * signal_index /*host*/, double * d_signal, const int32_t * flag_index /*host*/,
+    const uint8_t * d_det_flags, uint8_t det_flag_mask, const uint8_t * d_shared_flags, uint8_t shared_flag_mask,
+    int64_t n_det, double * d_mean, int64_t * d_hits, void * stream);
+/* Host-pointer forms with the reference's arguments (src/toast/_libtoast/tod_filter.cpp:326-383, 9-97): buffers are
+ * looked up in the memory manager (use_accel) or staged through the device.  `signals` are n_signal separate arrays of
+ * n_samp doubles sharing one flag vector (non-zero = flagged). */
+int toast_hip_filter_polynomial(int64_t order, const uint8_t * flags, int64_t n_samp, double * const * signals,
+                                int64_t n_signal, const int64_t * starts, const int64_t * stops, int64_t n_scan,
+                                int use_accel);
+int toast_hip_sum_detectors(const int64_t * det_index, const int64_t * flag_index, int64_t n_det,
+                            const uint8_t * shared_flags, uint8_t shared_flag_mask, const double * det_data,
+                            int64_t n_data_rows, const uint8_t * det_flags, int64_t n_flag_rows, uint8_t det_flag_mask,
+                            int64_t n_samp, double * sum_data, int64_t * hits, int use_accel);
+int toast_hip_subtract_mean(const int64_t * det_index, int64_t n_det, double * det_data, int64_t n_data_rows,
+                            int64_t n_samp, double * sum_data, const int64_t * hits, int use_accel);
+
+/* ------------------------------------------------------------------------------------
  * FFT noise weighting
  *
  * toast_hip_fft_convolve: in-place convolution (or deconvolution) of each selected timestream

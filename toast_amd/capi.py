@@ -1228,6 +1228,51 @@ class _Dev:
             _p(d_templates), _i64(n_template), _i64(first_template), _i64(n_samp), _p(si), _p(d_signal), _p(d_coeff),
             _i64(si.size), _p(stream)))
 
+    # ---- PolyFilter / CommonModeFilter kernels (csrc/poly_filter.hip)
+    POLY_FITTED, POLY_NO_GOOD, POLY_REDUCED, POLY_NOT_POSITIVE = 0, 1, 2, 3
+    POLY_PATH_RULE, POLY_PATH_SINGLE, POLY_PATH_TWO_PASS = 0, 1, 2
+
+    def filter_polynomial_stage_cap(self):
+        """Longest interval (samples) the single-pass path stages in LDS: the path rule's one threshold."""
+        return int(real_lib().toast_hip_filter_polynomial_stage_cap())
+
+    def filter_polynomial(self, order, n_samp, signal_index, d_signal, flag_index, d_det_flags, det_flag_mask,
+                          d_shared_flags, shared_flag_mask, starts, stops, d_coeff, d_status, path=0, stream=0):
+        """``stops`` exclusive; ``d_coeff`` float64 [n_det][n_interval][order + 1], ``d_status`` int32 [n_det][n_interval]."""
+        si = self._small(signal_index, np.int32)
+        fi = self._small(flag_index if flag_index is not None else np.zeros(si.size), np.int32)
+        st = self._small(starts, np.int64)
+        sp = self._small(stops, np.int64)
+        if st.size != sp.size:
+            raise RuntimeError("Starts / stops buffer sizes are not consistent.")
+        if fi.size != si.size:
+            raise RuntimeError("filter_polynomial: one flag row per signal row")
+        _check(lib().toast_hip_filter_polynomial_dev(
+            _i64(order), _i64(n_samp), _p(si), _p(d_signal), _p(fi), _p(d_det_flags), _u8(det_flag_mask),
+            _p(d_shared_flags), _u8(shared_flag_mask), _i64(si.size), _p(st), _p(sp), _i64(st.size), _p(d_coeff),
+            _p(d_status), C.c_int(int(path)), _p(stream)))
+
+    def sum_detectors(self, n_samp, signal_index, d_signal, flag_index, d_det_flags, det_flag_mask, d_shared_flags,
+                      shared_flag_mask, d_sum, d_hits, stream=0):
+        si = self._small(signal_index, np.int32)
+        fi = self._small(flag_index if flag_index is not None else np.zeros(si.size), np.int32)
+        _check(lib().toast_hip_sum_detectors_dev(
+            _i64(n_samp), _p(si), _p(d_signal), _p(fi), _p(d_det_flags), _u8(det_flag_mask), _p(d_shared_flags),
+            _u8(shared_flag_mask), _i64(si.size), _p(d_sum), _p(d_hits), _p(stream)))
+
+    def subtract_mean(self, n_samp, signal_index, d_signal, d_sum, d_hits, stream=0):
+        si = self._small(signal_index, np.int32)
+        _check(lib().toast_hip_subtract_mean_dev(_i64(n_samp), _p(si), _p(d_signal), _i64(si.size), _p(d_sum), _p(d_hits),
+                                                 _p(stream)))
+
+    def common_mode_subtract(self, n_samp, signal_index, d_signal, flag_index, d_det_flags, det_flag_mask, d_shared_flags,
+                             shared_flag_mask, d_mean=0, d_hits=0, stream=0):
+        si = self._small(signal_index, np.int32)
+        fi = self._small(flag_index if flag_index is not None else np.zeros(si.size), np.int32)
+        _check(lib().toast_hip_common_mode_subtract_dev(
+            _i64(n_samp), _p(si), _p(d_signal), _p(fi), _p(d_det_flags), _u8(det_flag_mask), _p(d_shared_flags),
+            _u8(shared_flag_mask), _i64(si.size), _p(d_mean), _p(d_hits), _p(stream)))
+
     def combine_flags(self, d_out, out_index, d_det_flags, n_flag_samp, flag_index, det_flag_mask, d_shared_flags,
                       n_shared_flags, shared_flag_mask, n_samp, intervals, n_out_rows=0, outside_value=-1, stream=0):
         oi = self._small(out_index, np.int32)

@@ -4,6 +4,8 @@
 // reference's `omgr.device_ptr(...)` lookups, e.g. ops_scan_map.cpp:166-171), or by staging
 // temporary device copies otherwise -- and forwards to the *_dev kernel launcher.
 // No computation happens on the host.
+#include <vector>
+
 #include "runtime.hpp"
 
 using namespace toast_hip;
@@ -199,6 +201,59 @@ int toast_hip_noise_weight(double * det_data, int64_t n_data_rows, int64_t n_sam
         double * d_tod = c.st.inout(det_data, (size_t)(n_data_rows * n_samp));
         c.check(toast_hip_noise_weight_dev(d_tod, n_samp, data_index, n_det, intervals, n_view,
                                            detector_weights, c.stream));
+        c.st.finish();
+    });
+}
+
+int toast_hip_filter_polynomial(int64_t order, const uint8_t * flags, int64_t n_samp, double * const * signals,
+                                int64_t n_signal, const int64_t * starts, const int64_t * stops, int64_t n_scan,
+                                int use_accel) {
+    return guarded([&] {
+        if (order < 0 || n_signal <= 0 || n_scan <= 0) return;
+        Call c(use_accel);
+        // one flag vector for all signals (the reference's grouping): it plays the shared flags, any bit counts
+        const uint8_t * d_flags = c.st.temp_in(flags, (size_t)n_samp);
+        std::vector<double> coeff((size_t)(n_scan * (order + 1)));
+        std::vector<int32_t> status((size_t)n_scan);
+        double * d_coeff = c.st.temp_inout(coeff.data(), coeff.size());
+        int32_t * d_status = c.st.temp_inout(status.data(), status.size());
+        const int32_t row = 0;
+        for (int64_t k = 0; k < n_signal; ++k) {
+            double * d_sig = c.st.inout(signals[k], (size_t)n_samp);
+            c.check(toast_hip_filter_polynomial_dev(order, n_samp, &row, d_sig, nullptr, nullptr, 0, d_flags, 0xff, 1, starts,
+                                                    stops, n_scan, d_coeff, d_status, 0, c.stream));
+        }
+        c.st.finish();
+    });
+}
+
+int toast_hip_sum_detectors(const int64_t * det_index, const int64_t * flag_index, int64_t n_det,
+                            const uint8_t * shared_flags, uint8_t shared_flag_mask, const double * det_data,
+                            int64_t n_data_rows, const uint8_t * det_flags, int64_t n_flag_rows, uint8_t det_flag_mask,
+                            int64_t n_samp, double * sum_data, int64_t * hits, int use_accel) {
+    return guarded([&] {
+        Call c(use_accel);
+        std::vector<int32_t> di(det_index, det_index + n_det), fi(flag_index, flag_index + n_det);
+        const double * d_tod = c.st.in(det_data, (size_t)(n_data_rows * n_samp));
+        const uint8_t * d_df = c.st.in(det_flags, (size_t)(n_flag_rows * n_samp));
+        const uint8_t * d_sf = c.st.in(shared_flags, (size_t)n_samp);
+        double * d_sum = c.st.inout(sum_data, (size_t)n_samp);
+        int64_t * d_hits = c.st.inout(hits, (size_t)n_samp);
+        c.check(toast_hip_sum_detectors_dev(n_samp, di.data(), d_tod, fi.data(), d_df, det_flag_mask, d_sf, shared_flag_mask,
+                                            n_det, d_sum, d_hits, c.stream));
+        c.st.finish();
+    });
+}
+
+int toast_hip_subtract_mean(const int64_t * det_index, int64_t n_det, double * det_data, int64_t n_data_rows,
+                            int64_t n_samp, double * sum_data, const int64_t * hits, int use_accel) {
+    return guarded([&] {
+        Call c(use_accel);
+        std::vector<int32_t> di(det_index, det_index + n_det);
+        double * d_tod = c.st.inout(det_data, (size_t)(n_data_rows * n_samp));
+        double * d_sum = c.st.inout(sum_data, (size_t)n_samp);
+        const int64_t * d_hits = c.st.in(hits, (size_t)n_samp);
+        c.check(toast_hip_subtract_mean_dev(n_samp, di.data(), d_tod, n_det, d_sum, d_hits, c.stream));
         c.st.finish();
     });
 }

@@ -429,6 +429,61 @@ PYBIND11_MODULE(_libtoast_hip, m) {
         check(toast_hip_noise_weight(tod, n_rows, n_samp, d_idx, n_det, ivl, n_view, dw, use_accel));
     });
 
+    // ---- filter_polynomial / sum_detectors / subtract_mean (tod_filter.cpp:326-383, 9-97, 496-497)
+    m.def("filter_polynomial", [](int64_t order, py::buffer flags, py::list signals, py::buffer starts, py::buffer stops,
+                                  bool use_accel) {
+        Shape s(3);
+        uint8_t * fl = extract<uint8_t>(flags, "flags", 1, s, {-1});
+        const int64_t n_samp = s[0];
+        int64_t * st = extract<int64_t>(starts, "starts", 1, s, {-1});
+        const int64_t n_scan = s[0];
+        if (stops.request().size != n_scan) throw std::runtime_error("Starts / stops buffer sizes are not consistent.");
+        int64_t * sp = extract<int64_t>(stops, "stops", 1, s, {n_scan});
+        std::vector<double *> sigs;
+        for (auto const & sg : signals) {
+            auto buf = sg.cast<py::buffer>();
+            if (buf.request().size != n_samp) throw std::runtime_error("Signal and flag buffer sizes are not consistent.");
+            sigs.push_back(extract<double>(buf, "signal", 1, s, {n_samp}));
+        }
+        check(toast_hip_filter_polynomial(order, fl, n_samp, sigs.data(), (int64_t)sigs.size(), st, sp, n_scan, use_accel));
+    }, py::arg("order"), py::arg("flags"), py::arg("signals"), py::arg("starts"), py::arg("stops"),
+       py::arg("use_accel") = false);
+    m.def("sum_detectors", [](py::array_t<int64_t, py::array::c_style | py::array::forcecast> det_indx,
+                              py::array_t<int64_t, py::array::c_style | py::array::forcecast> flag_indx,
+                              py::buffer shared_flags, uint8_t shared_flag_mask, py::buffer det_data, py::buffer det_flags,
+                              uint8_t det_flag_mask, py::buffer sum_data, py::buffer hits) {
+        Shape s(3);
+        const int64_t n_det = det_indx.size();
+        if (flag_indx.size() != n_det) throw std::runtime_error("sum_detectors: one flag row per detector row");
+        double * tod = extract<double>(det_data, "det_data", 2, s, {-1, -1});
+        const int64_t n_rows = s[0], n_samp = s[1];
+        uint8_t * df = extract<uint8_t>(det_flags, "det_flags", 2, s, {-1, n_samp});
+        const int64_t n_frows = s[0];
+        uint8_t * sf = extract<uint8_t>(shared_flags, "shared_flags", 1, s, {n_samp});
+        double * sum = extract<double>(sum_data, "sum_data", 1, s, {n_samp});
+        int64_t * h = extract<int64_t>(hits, "hits", 1, s, {n_samp});
+        for (int64_t k = 0; k < n_det; ++k) {
+            if (det_indx.at(k) < 0 || det_indx.at(k) >= n_rows || flag_indx.at(k) < 0 || flag_indx.at(k) >= n_frows) {
+                throw std::runtime_error("sum_detectors: row index out of range");
+            }
+        }
+        check(toast_hip_sum_detectors(det_indx.data(), flag_indx.data(), n_det, sf, shared_flag_mask, tod, n_rows, df, n_frows,
+                                      det_flag_mask, n_samp, sum, h, 0));
+    });
+    m.def("subtract_mean", [](py::array_t<int64_t, py::array::c_style | py::array::forcecast> detectors, py::buffer det_data,
+                              py::buffer sum_data, py::buffer hits) {
+        Shape s(3);
+        const int64_t n_det = detectors.size();
+        double * tod = extract<double>(det_data, "det_data", 2, s, {-1, -1});
+        const int64_t n_rows = s[0], n_samp = s[1];
+        double * sum = extract<double>(sum_data, "sum_data", 1, s, {n_samp});
+        int64_t * h = extract<int64_t>(hits, "hits", 1, s, {n_samp});
+        for (int64_t k = 0; k < n_det; ++k) {
+            if (detectors.at(k) < 0 || detectors.at(k) >= n_rows) throw std::runtime_error("subtract_mean: row index out of range");
+        }
+        check(toast_hip_subtract_mean(detectors.data(), n_det, tod, n_rows, n_samp, sum, h, 0));
+    });
+
     // ---- cov_apply_diag (map_cov.cpp:372-401; flat buffers)
     m.def("cov_apply_diag", [](int64_t nsub, int64_t nsubpix, int64_t nnz, py::buffer mat, py::buffer vec,
                                bool use_accel) {

@@ -20,5 +20,6 @@ from .ground_filter import GroundFilter
 from .noise_filter import NoiseFilter
 from .operator import Operator
 from .pipeline import Pipeline
+from .poly_filter import CommonModeFilter, PolyFilter
 from .pointing import BuildPixelDistribution, PixelsHealpix, PointingDetectorSimple, StokesWeights
 from .sim_ground import SimGround

@@ -7,6 +7,7 @@ configs[4] is upstream of this path and is not part of
 
     python workflows/ground_filter_mapmaker.py [--ndet 256] [--minutes 60] [--rate 200] [--nside 2048]
                                                [--iter 10] [--split] [--filter-order 5] [--trend-order 5]
+                                               [--polyfilter ORDER] [--common-mode] [--save-map FILE]
 """
 import argparse
 import os
@@ -43,6 +44,10 @@ def main(argv=None):
                     help="with --scheduled: an el-nod (+1, -1, 0 degrees) before and after every scan and elevation steps of "
                          "0.05 degrees after every scan pair (ops.SimGround elnod_start / elnod_end / el_mod_step); the "
                          "el-nod samples carry the `irregular` flag bit and stay out of the maps")
+    ap.add_argument("--polyfilter", type=int, default=None, metavar="ORDER",
+                    help="run ops.PolyFilter(order=ORDER, view='throw') before GroundFilter (off by default)")
+    ap.add_argument("--common-mode", action="store_true", help="run ops.CommonModeFilter() before GroundFilter (off by default)")
+    ap.add_argument("--save-map", default=None, metavar="FILE", help="save the binned map as a .npy file")
     args = ap.parse_args(argv)
     n_samp = int(args.minutes * 60 * args.rate)
     t = time.time()
@@ -83,6 +88,15 @@ def main(argv=None):
     lap("simulate (host)")
     good = (ob.shared[defaults.shared_flags].data & 1) == 0
     rms_before = float(np.std(sig[0][good]))
+    if args.polyfilter is not None:
+        for o in data.obs:
+            if "throw" not in o.intervals:      # the synthetic generator names the sweeps `scanning` only
+                o.intervals.create("throw", [(int(iv.first), int(iv.last)) for iv in o.intervals[defaults.scanning_interval]])
+        ops.PolyFilter(order=args.polyfilter, view="throw", name="polyfilter").apply(data)
+        lap("PolyFilter")
+    if args.common_mode:
+        ops.CommonModeFilter(name="commonmode").apply(data)
+        lap("CommonModeFilter")
     gf = ops.GroundFilter(trend_order=args.trend_order, filter_order=args.filter_order, split_template=args.split,
                           name="groundfilter")
     gf.apply(data)
@@ -111,6 +125,8 @@ def main(argv=None):
         print(f"PCG iteration (median wall time): {1e3 * med:.1f} ms  = {nds / med / 1e9:.1f} G det-samples/s")
     hits = data["mapmaker_hits"]
     print(f"hit pixels {int(np.count_nonzero(hits.data))}  relative residual {mapper.history[-1]:.2e}")
+    if args.save_map is not None:
+        np.save(args.save_map, np.asarray(data["mapmaker_map"].data))
     return data
 
 
