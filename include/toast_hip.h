@@ -891,6 +891,77 @@ int toast_hip_common_mode_subtract_dev(
     int64_t n_samp, const int32_t * signal_index /*host*/, double * d_signal, const int32_t * flag_index /*host*/,
     const uint8_t * d_det_flags, uint8_t det_flag_mask, const uint8_t * d_shared_flags, uint8_t shared_flag_mask,
     int64_t n_det, double * d_mean, int64_t * d_hits, void * stream);
+/* ------------------------------------------------------------------------------------
+ * SubHarmonic and Periodic destriping templates (device-resident buffers; host index and interval arrays).
+ * The reference has no compiled kernel for either: both are NumPy, one detector and one view at a time
+ * (src/toast/templates/subharmonic.py, periodic.py).  Here all detectors of an observation go in one call.
+ * amp_offsets[d] = first amplitude of detector d's block for THIS observation; data_index / flag_index are the
+ * detector's rows in d_det_data / d_det_flags ([rows][n_samp]).  At most 65535 detectors per call.
+ *
+ * SubHarmonic, norder = order + 1 <= toast_hip_subharmonic_max_terms(); the amplitudes of view v of detector d are
+ * d_amplitudes[amp_offsets[d] + v * norder + k].  The Legendre basis is evaluated per sample and never stored:
+ * r_i = np.linspace(-1, 1, L)[i], T_k = (((2k - 1) r) T_{k-1} - (k - 1) T_{k-2}) / k (subharmonic.py:143-155,
+ * bit for bit).  Views are clipped to [0, n_samp); project_signal assigns 0 to the amplitudes of an empty view.
+ *   add_to_signal   signal[d][view] += sum_k T_k a_k, ascending k   [subharmonic.py:190-203; bit-identical]
+ *   project_signal  a_k = sum_i signal_i T_k(r_i): NO flags are applied and the amplitudes are ASSIGNED, not
+ *                   accumulated, both like the reference [subharmonic.py:205-218].  Fixed-order reduction, no atomics.
+ *   precond_build   d_gram[d][v][r][c] = det_weights[d] * sum_good T_r T_c with good = (flags & mask) == 0 (every
+ *                   sample when d_det_flags is NULL), d_ngood[d][v] = number of good samples [subharmonic.py:157-178].
+ *                   The inverse (:179) is the caller's: a block with d_ngood == 0 has no inverse.
+ *   apply_precond   d_amp_out[b * norder + r] = sum_c d_precond[b][r][c] d_amp_in[b * norder + c] for the n_block
+ *                   blocks of the whole amplitude vector [subharmonic.py:224-236]
+ *
+ * Periodic: the bin of every sample is cached as int32 (toast_hip_periodic_index_dev) and read by the sweeps.
+ *   index           d_index[row][i] = min(int32((d_key[row][i] - obs_min) / incr), nbins - 1) in fp64, truncating, for the
+ *                   samples of the views whose key flags are clear (d_flags may be NULL); -1 everywhere else
+ *                   [periodic.py:284-319 without the detector flags].  n_row = 1 for a shared key.
+ *   hits            d_hits[amp_offsets[d] + index] += 1 over first <= i < last with a bin and clear detector flags
+ *                   [periodic.py:251-269; exact].  index_rows: the detector's row in d_index, NULL = one shared row.
+ *   add_to_signal   signal[d][i] += amps[amp_offsets[d] + index[i]] where index[i] >= 0: the key's flags only, never
+ *                   the detector flags [periodic.py:321-350; bit-identical]
+ *   project_signal  amps[amp_offsets[d] + index[i]] += signal[d][i] where index[i] >= 0 and the detector flags are
+ *                   clear [periodic.py:352-390].  path 0 = by the rule: nbins <= toast_hip_periodic_lds_bins() takes
+ *                   private LDS copies per wave, no atomics, merged in wave and chunk order (order-deterministic), more bins take
+ *                   fp64 atomics in global memory (not order-deterministic); 1 / 2 force one form.
+ *   apply_precond   d_amp_out[i] = d_amp_in[i] * d_hits[i] where d_amp_flags[i] == 0, untouched elsewhere
+ *                   [periodic.py:396-419; exact]
+ * ---------------------------------------------------------------------------------- */
+int toast_hip_subharmonic_max_terms(void);
+int toast_hip_periodic_lds_bins(void);
+int toast_hip_subharmonic_add_to_signal_dev(
+    int64_t norder, const int64_t * amp_offsets /*host*/, const double * d_amplitudes, const int32_t * data_index /*host*/,
+    int64_t n_det, double * d_det_data, int64_t n_samp, const toast_hip_interval * intervals /*host*/, int64_t n_view,
+    void * stream);
+int toast_hip_subharmonic_project_signal_dev(
+    int64_t norder, const int64_t * amp_offsets /*host*/, double * d_amplitudes, const int32_t * data_index /*host*/,
+    int64_t n_det, const double * d_det_data, int64_t n_samp, const toast_hip_interval * intervals /*host*/,
+    int64_t n_view, void * stream);
+int toast_hip_subharmonic_precond_build_dev(
+    int64_t norder, const int32_t * flag_index /*host*/, const uint8_t * d_det_flags, uint8_t det_flag_mask,
+    const double * det_weights /*host*/, int64_t n_det, int64_t n_samp, const toast_hip_interval * intervals /*host*/,
+    int64_t n_view, double * d_gram, int64_t * d_ngood, void * stream);
+int toast_hip_subharmonic_apply_precond_dev(int64_t norder, int64_t n_block, const double * d_precond,
+                                            const double * d_amp_in, double * d_amp_out, void * stream);
+int toast_hip_periodic_index_dev(
+    const double * d_key, const uint8_t * d_flags, uint8_t flag_mask, int64_t n_row, int64_t n_samp, double obs_min,
+    double incr, int64_t nbins, const toast_hip_interval * intervals /*host*/, int64_t n_view, int32_t * d_index,
+    void * stream);
+int toast_hip_periodic_hits_dev(
+    const int32_t * d_index, const int32_t * index_rows /*host*/, const int32_t * flag_index /*host*/,
+    const uint8_t * d_det_flags, uint8_t det_flag_mask, const int64_t * amp_offsets /*host*/, int64_t n_det,
+    int64_t n_samp, int64_t nbins, int64_t first, int64_t last, int32_t * d_hits, void * stream);
+int toast_hip_periodic_add_to_signal_dev(
+    const int32_t * d_index, const int32_t * index_rows /*host*/, const int64_t * amp_offsets /*host*/,
+    const double * d_amplitudes, const int32_t * data_index /*host*/, int64_t n_det, double * d_det_data, int64_t n_samp,
+    int64_t nbins, void * stream);
+int toast_hip_periodic_project_signal_dev(
+    const int32_t * d_index, const int32_t * index_rows /*host*/, const int32_t * data_index /*host*/,
+    const double * d_det_data, const int32_t * flag_index /*host*/, const uint8_t * d_det_flags, uint8_t det_flag_mask,
+    const int64_t * amp_offsets /*host*/, double * d_amplitudes, int64_t n_det, int64_t n_samp, int64_t nbins, int path,
+    void * stream);
+int toast_hip_periodic_apply_precond_dev(int64_t n_amp, const int32_t * d_hits, const uint8_t * d_amp_flags,
+                                         const double * d_amp_in, double * d_amp_out, void * stream);
+
 /* Host-pointer forms with the reference's arguments (src/toast/_libtoast/tod_filter.cpp:326-383, 9-97): buffers are
  * looked up in the memory manager (use_accel) or staged through the device.  `signals` are n_signal separate arrays of
  * n_samp doubles sharing one flag vector (non-zero = flagged). */

@@ -1,0 +1,280 @@
+"""SubHarmonic and Periodic templates, host path (NumPy; no device), against tests/golden/templates_basis.npz -- the
+results of the reference's own methods (tests/golden/make_golden_templates.py) on the inputs of tests/templates_case.py.
+
+Bit-exact: amplitude layout, ``n_local``, SubHarmonic ``add_to_signal``; Periodic bin index, hits, flags,
+``add_to_signal``, ``apply_precond``.  The host path evaluates the reference's own NumPy expressions in the reference's
+order, so the two projections are compared bit for bit as well; the SubHarmonic preconditioner goes through
+``numpy.linalg.inv`` of a batch instead of one matrix at a time and is compared under ten times the reference's own
+measured deviation from the exact inverse, scaled by the condition number of each block.
+
+The end-to-end entries of the fixture (``e2e_*``: the reference's ``solve()`` over [Offset, SubHarmonic, Periodic]) need
+the map-making kernels and are compared in tests/test_gpu_templates.py, with the templates on the host path and on the
+device; here the two templates are set up on the end-to-end case and their layout and flags are compared.
+"""
+import os
+import sys
+
+import numpy as np
+import pytest
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+sys.path.insert(0, HERE)
+
+import templates_case as tc  # noqa: E402
+
+GOLD = np.load(os.path.join(HERE, "golden", "templates_basis.npz"), allow_pickle=False)
+EPS = np.finfo(np.float64).eps
+# The reference's own inverses deviate from the exact ones (rational arithmetic on the fixture's Gram matrices) by at most
+# 0.32 eps cond(G) max|G^-1|; ten times that for another LAPACK call order.  apply_precond adds the rounding of a dot
+# product of norder terms: (3.2 cond + norder) eps max|G^-1| sum|a| per amplitude.
+F_INVERSE = 3.2
+
+
+def _subharmonic(name):
+    from toast_amd.templates import SubHarmonic
+
+    layout, traits = tc.SUBHARMONIC_CASES[name]
+    data = tc.build(layout)
+    tmpl = tc.configure(SubHarmonic(name=name, **traits))
+    tmpl.data = data
+    return data, tmpl
+
+
+def _periodic(name, **extra):
+    from toast_amd.templates import Periodic
+
+    layout, traits = tc.PERIODIC_CASES[name]
+    data = tc.build(layout)
+    tmpl = tc.configure(Periodic(name=name, **{**traits, **extra}))
+    tmpl.data = data
+    return data, tmpl
+
+
+def _amps(tmpl, values=None):
+    z = tmpl.zeros()
+    if values is not None:
+        z.local[:] = values
+    return z
+
+
+@pytest.mark.parametrize("name", list(tc.SUBHARMONIC_CASES))
+def test_subharmonic_host_matches_reference(name):
+    data, tmpl = _subharmonic(name)
+    norder = tmpl.order + 1
+    assert tmpl._n_local == int(GOLD[f"{name}_n_local"])
+    assert np.array_equal([tmpl._det_start[d] for d in tmpl.detectors()], GOLD[f"{name}_det_start"])
+    assert tmpl.zeros().n_local_flagged == 0
+    # M^T d: assigned (the 123 must be gone), no flags
+    proj = _amps(tmpl, 123.0)
+    for det in tmpl.detectors():
+        tmpl.project_signal(det, proj)
+    assert np.array_equal(proj.local, GOLD[f"{name}_project"])
+    # d + M a: bit for bit
+    amps = _amps(tmpl, tc.amplitudes(tmpl._n_local, 1))
+    for det in tmpl.detectors():
+        tmpl.add_to_signal(det, amps)
+    for iob, ob in enumerate(data.obs):
+        assert np.array_equal(ob.detdata[tc.DET_DATA].data, GOLD[f"{name}_add_obs{iob}"]), (name, iob)
+    # preconditioner: inverse of the weighted Gram matrix, block by block
+    ref = GOLD[f"{name}_precond"]
+    assert tmpl._precond.shape == ref.shape == (tmpl._n_local // norder, norder, norder)
+    for blk in range(ref.shape[0]):
+        cond = np.linalg.cond(ref[blk])
+        assert np.abs(tmpl._precond[blk] - ref[blk]).max() <= F_INVERSE * EPS * cond * np.abs(ref[blk]).max(), (name, blk)
+    out = _amps(tmpl)
+    tmpl.apply_precond(amps, out)
+    bound = EPS * np.array([(F_INVERSE * np.linalg.cond(p) + norder) * np.abs(p).max() for p in ref]).repeat(norder) * \
+        np.abs(amps.local).reshape(-1, norder).sum(axis=1).repeat(norder)
+    assert np.all(np.abs(out.local - GOLD[f"{name}_precond_out"]) <= bound)
+
+
+@pytest.mark.parametrize("name", list(tc.PERIODIC_CASES))
+def test_periodic_host_matches_reference(name):
+    data, tmpl = _periodic(name)
+    assert tmpl._n_local == int(GOLD[f"{name}_n_local"])
+    assert np.array_equal([tmpl._det_offset[d] for d in tmpl.detectors()], GOLD[f"{name}_det_offset"])
+    n_obs = len(data.obs)
+    assert np.array_equal([tmpl._obs_min[i] for i in range(n_obs)], GOLD[f"{name}_obs_min"])
+    assert np.array_equal([tmpl._obs_max[i] for i in range(n_obs)], GOLD[f"{name}_obs_max"])
+    assert np.array_equal([tmpl._obs_incr[i] for i in range(n_obs)], GOLD[f"{name}_obs_incr"])
+    assert np.array_equal([tmpl._obs_nbins[i] for i in range(n_obs)], GOLD[f"{name}_obs_nbins"])
+    for iob, ob in enumerate(data.obs):
+        index = tmpl._host_index(iob, ob)
+        assert index.dtype == np.int32 and np.array_equal(index[0], GOLD[f"{name}_index_obs{iob}"])
+        # the overflow clamp is exercised: the largest key value lands in the last bin
+        assert index.max() == tmpl._obs_nbins[iob] - 1
+    assert tmpl._amp_hits.dtype == np.int32 and np.array_equal(tmpl._amp_hits, GOLD[f"{name}_hits"])
+    assert np.array_equal(tmpl._amp_flags.astype(np.uint8), GOLD[f"{name}_flags"])
+    # the reference's quirk: bins that reach the minimum only in a later view stay flagged
+    late = tmpl._amp_flags & (tmpl._amp_hits >= tmpl.minimum_bin_hits)
+    assert late.any()
+    assert np.array_equal(tmpl.zeros().local_flags, GOLD[f"{name}_flags"])
+    proj = _amps(tmpl, 0.5)
+    for det in tmpl.detectors():
+        tmpl.project_signal(det, proj)
+    assert np.array_equal(proj.local, GOLD[f"{name}_project"])
+    amps = _amps(tmpl, tc.amplitudes(tmpl._n_local, 2))
+    for det in tmpl.detectors():
+        tmpl.add_to_signal(det, amps)
+    for iob, ob in enumerate(data.obs):
+        assert np.array_equal(ob.detdata[tc.DET_DATA].data, GOLD[f"{name}_add_obs{iob}"]), (name, iob)
+    out = _amps(tmpl, -3.0)
+    tmpl.apply_precond(amps, out)
+    assert np.array_equal(out.local, GOLD[f"{name}_precond_out"])
+    assert np.all(out.local[tmpl._amp_flags] == -3.0)
+
+
+def test_layout_detector_missing_from_an_observation():
+    """detector-major; d1 is absent from the second observation and owns fewer amplitudes."""
+    data, sub = _subharmonic("sub3")
+    per_view = sub.order + 1
+    n_view = [len(ob.intervals[tc.VIEW]) for ob in data.obs]
+    assert sub.detectors() == ["d0", "d1", "d2"]
+    assert sub._det_start == {"d0": 0, "d1": per_view * sum(n_view), "d2": per_view * (sum(n_view) + n_view[0])}
+    assert sub._n_local == per_view * (2 * sum(n_view) + n_view[0])
+    data, per = _periodic("per_bins")
+    assert per._det_offset == {"d0": 0, "d1": 14, "d2": 21} and per._n_local == 35
+
+
+def test_template_matrix_runs_both_templates_in_both_directions():
+    from toast_amd.ops import TemplateMatrix
+    from toast_amd.templates import Periodic, SubHarmonic
+
+    def matrix(data):
+        tm = TemplateMatrix(templates=[SubHarmonic(name="sub", order=3), Periodic(name="per", **tc.PERIODIC_CASES["per_bins"][1])],
+                            amplitudes="amps", view=tc.VIEW, det_data=tc.DET_DATA, det_flags=tc.DET_FLAGS,
+                            det_flag_mask=tc.DET_FLAG_MASK, det_mask=1)
+        return tm
+
+    data = tc.build("long")
+    tm = matrix(data)
+    tm.transpose = True
+    tm.apply(data)
+    amps = data["amps"]
+    assert set(amps.keys()) == {"sub", "per"}
+    # the same through the templates one detector at a time
+    data2 = tc.build("long")
+    for tmpl in matrix(data2).templates:
+        tc.configure(tmpl)
+        tmpl.data = data2
+        z = tmpl.zeros()
+        for det in tmpl.detectors():
+            tmpl.project_signal(det, z)
+        assert np.array_equal(z.local, amps[tmpl.name].local) and np.any(z.local != 0)
+        assert np.array_equal(z.local_flags, amps[tmpl.name].local_flags)
+    # forward: the timestream is zeroed, then M a of both templates is added
+    for k, v in amps.items():
+        v.local[:] = tc.amplitudes(v.n_local, 5)
+    tm.transpose = False
+    tm.apply(data)
+    for tmpl in tm.templates:
+        for ob in data2.obs:
+            ob.detdata[tc.DET_DATA].data[:] = 0
+    for ob in data2.obs:
+        ob.detdata[tc.DET_DATA].data[:] = 0
+    for tmpl2, tmpl in zip(matrix(data2).templates, tm.templates):
+        tc.configure(tmpl2)
+        tmpl2.data = data2
+        z = tmpl2.zeros()
+        z.local[:] = amps[tmpl.name].local
+        for det in tmpl2.detectors():
+            tmpl2.add_to_signal(det, z)
+    for ob, ob2 in zip(data.obs, data2.obs):
+        assert np.array_equal(ob.detdata[tc.DET_DATA].data, ob2.detdata[tc.DET_DATA].data)
+        assert np.any(ob.detdata[tc.DET_DATA].data != 0)
+    # the preconditioner of the matrix reaches both templates
+    out = amps.duplicate()
+    out.reset()
+    tm.apply_precond(amps, out)
+    assert np.any(out["sub"].local != 0) and np.any(out["per"].local != 0)
+    assert tm.supports_accel()
+
+
+def test_periodic_initialize_errors():
+    from toast_amd.templates import Periodic
+
+    data = tc.build("tiny")
+    with pytest.raises(RuntimeError, match="You must set key"):
+        tc.configure(Periodic(name="p")).data = data
+    with pytest.raises(RuntimeError, match="Only one of bins and increment"):
+        tc.configure(Periodic(name="p", key=tc.KEY, bins=4, increment=2.0)).data = data
+    with pytest.raises(RuntimeError, match="zero amplitude bins"):
+        tc.configure(Periodic(name="p", key=tc.KEY, bins=None, increment=1.0e6)).data = data
+    with pytest.raises(RuntimeError, match="zero amplitude bins"):
+        tc.configure(Periodic(name="p", key=tc.KEY, bins=0)).data = data
+    data.obs[1].shared[tc.KEY].data[:] = 4.0
+    with pytest.raises(RuntimeError, match="is constant for observation obs1"):
+        tc.configure(Periodic(name="p", key=tc.KEY)).data = data
+    tmpl = Periodic(name="p", key=tc.KEY)
+    with pytest.raises(NotImplementedError):
+        tmpl.write(None, "amps.h5")
+    with pytest.raises(NotImplementedError):
+        tmpl.plot("amps.h5")
+
+
+def test_subharmonic_view_without_good_sample_raises():
+    from toast_amd.templates import SubHarmonic
+
+    data = tc.build("long")
+    first, last = tc.LAYOUTS["long"]["obs"][0]["views"][2]
+    data.obs[0].detdata[tc.DET_FLAGS].data[1, first:last] |= tc.DET_FLAG_MASK
+    with pytest.raises(np.linalg.LinAlgError, match="detector d1, observation obs0, view 2 has no unflagged sample"):
+        tc.configure(SubHarmonic(name="s", order=2)).data = data
+    # without solver flags every sample counts
+    tc.configure(SubHarmonic(name="s", order=2), det_flags=None).data = data
+
+
+def test_periodic_per_detector_key():
+    """is_detdata_key: every detector is binned by its own row of the key and flagged by its own row of the key flags."""
+    from toast_amd.templates import Periodic
+
+    data = tc.build("tiny")
+    for iob, ob in enumerate(data.obs):
+        ob.detdata.create("det_az", dtype=np.float64)
+        ob.detdata.create("det_az_flags", dtype=np.uint8)
+        rng = np.random.default_rng(90 + iob)
+        ob.detdata["det_az"].data[:] = ob.shared[tc.KEY].data[None, :] + 3.0 * np.arange(len(ob.local_detectors))[:, None]
+        ob.detdata["det_az_flags"].data[:] = (rng.random(ob.detdata["det_az"].data.shape) < 0.1) * tc.KEY_FLAG_MASK
+    tmpl = tc.configure(Periodic(name="p", key="det_az", flags="det_az_flags", flag_mask=tc.KEY_FLAG_MASK,
+                                 is_detdata_key=True, bins=6))
+    tmpl.data = data
+    assert tmpl._n_local == 5 * 6
+    ob = data.obs[0]
+    vals, flg = ob.detdata["det_az"].data, ob.detdata["det_az_flags"].data
+    inview = np.zeros(ob.n_local_samples, dtype=bool)
+    for first, last in tc.LAYOUTS["tiny"]["obs"][0]["views"]:
+        inview[first:last] = True
+    good = inview[None, :] & ((flg & tc.KEY_FLAG_MASK) == 0)
+    assert tmpl._obs_min[0] == vals[good].min() and tmpl._obs_max[0] == vals[good].max()
+    expect = np.minimum(((vals - tmpl._obs_min[0]) / tmpl._obs_incr[0]).astype(np.int32), 5)
+    assert np.array_equal(tmpl._host_index(0, ob), np.where(good, expect, -1))
+    hit_good = good & ((ob.detdata[tc.DET_FLAGS].data & tc.DET_FLAG_MASK) == 0)
+    for k, det in enumerate(ob.local_detectors):
+        off = tmpl._det_offset[det]
+        assert np.array_equal(tmpl._amp_hits[off:off + 6], np.bincount(expect[k][hit_good[k]], minlength=6))
+    amps = tmpl.zeros()
+    amps.local[:] = np.arange(tmpl._n_local) + 1.0
+    before = ob.detdata[tc.DET_DATA].data.copy()
+    tmpl.add_to_signal("d1", amps)
+    delta = ob.detdata[tc.DET_DATA].data - before
+    assert np.all(delta[[0, 2]] == 0)
+    assert np.array_equal(delta[1] != 0, good[1])
+
+
+def test_end_to_end_case_layout_and_flags():
+    """The templates of the end-to-end case, set up as ``SolveAmplitudes`` would without the solver's extra flag bits:
+    the sizes and the Periodic flags of the fixture (the key carries no flags and every bin is hit in the one view)."""
+    from toast_amd.data import defaults
+    from toast_amd.templates import Periodic, SubHarmonic
+
+    data, cfg = tc.build_e2e()
+    sub = SubHarmonic(name="subharmonic", order=cfg["order"], noise_model=defaults.noise_model)
+    per = Periodic(name="ground", key=tc.KEY, bins=cfg["bins"], minimum_bin_hits=cfg["minimum_bin_hits"])
+    for tmpl in (sub, per):
+        tmpl.view, tmpl.det_data, tmpl.det_flags = None, defaults.det_data, defaults.det_flags
+        tmpl.det_flag_mask = defaults.det_mask_nonscience
+        tmpl.data = data
+    assert sub._n_local == GOLD["e2e_amplitudes_subharmonic"].size == cfg["n_det"] * (cfg["order"] + 1)
+    assert per._n_local == GOLD["e2e_amplitudes_ground"].size == cfg["n_det"] * cfg["bins"]
+    assert np.array_equal(per.zeros().local_flags, GOLD["e2e_flags_ground"])
+    assert len(GOLD["e2e_history"]) == cfg["iters"] and GOLD["e2e_history"][-1] < GOLD["e2e_history"][0]

@@ -1273,6 +1273,102 @@ class _Dev:
             _i64(n_samp), _p(si), _p(d_signal), _p(fi), _p(d_det_flags), _u8(det_flag_mask), _p(d_shared_flags),
             _u8(shared_flag_mask), _i64(si.size), _p(d_mean), _p(d_hits), _p(stream)))
 
+    # ---- SubHarmonic / Periodic template kernels (csrc/template_basis.hip)
+    PERIODIC_PATH_RULE, PERIODIC_PATH_LDS, PERIODIC_PATH_ATOMIC = 0, 1, 2
+
+    def subharmonic_max_terms(self):
+        """Largest ``order + 1`` the SubHarmonic kernels take."""
+        return int(real_lib().toast_hip_subharmonic_max_terms())
+
+    def periodic_lds_bins(self):
+        """Most bins per detector the order-deterministic Periodic projection holds in LDS: the path rule's threshold."""
+        return int(real_lib().toast_hip_periodic_lds_bins())
+
+    def subharmonic_add_to_signal(self, norder, amp_offsets, d_amplitudes, data_index, d_det_data, n_samp, intervals,
+                                  stream=0):
+        ao = self._small(amp_offsets, np.int64)
+        di = self._small(data_index, np.int32)
+        iv = self._small(intervals, interval_dtype)
+        if ao.size != di.size:
+            raise RuntimeError("subharmonic_add_to_signal: one amplitude offset per detector row")
+        _check(lib().toast_hip_subharmonic_add_to_signal_dev(
+            _i64(norder), _p(ao), _p(d_amplitudes), _p(di), _i64(di.size), _p(d_det_data), _i64(n_samp), _p(iv),
+            _i64(iv.size), _p(stream)))
+
+    def subharmonic_project_signal(self, norder, amp_offsets, d_amplitudes, data_index, d_det_data, n_samp, intervals,
+                                   stream=0):
+        ao = self._small(amp_offsets, np.int64)
+        di = self._small(data_index, np.int32)
+        iv = self._small(intervals, interval_dtype)
+        if ao.size != di.size:
+            raise RuntimeError("subharmonic_project_signal: one amplitude offset per detector row")
+        _check(lib().toast_hip_subharmonic_project_signal_dev(
+            _i64(norder), _p(ao), _p(d_amplitudes), _p(di), _i64(di.size), _p(d_det_data), _i64(n_samp), _p(iv),
+            _i64(iv.size), _p(stream)))
+
+    def subharmonic_precond_build(self, norder, flag_index, d_det_flags, det_flag_mask, det_weights, n_samp, intervals,
+                                  d_gram, d_ngood, stream=0):
+        """``d_gram`` float64 [n_det][n_view][norder][norder], ``d_ngood`` int64 [n_det][n_view]."""
+        w = self._small(det_weights, np.float64)
+        fi = None if flag_index is None else self._small(flag_index, np.int32)
+        iv = self._small(intervals, interval_dtype)
+        if fi is not None and fi.size != w.size:
+            raise RuntimeError("subharmonic_precond_build: one flag row per detector weight")
+        _check(lib().toast_hip_subharmonic_precond_build_dev(
+            _i64(norder), _p(fi), _p(d_det_flags), _u8(det_flag_mask), _p(w), _i64(w.size), _i64(n_samp), _p(iv),
+            _i64(iv.size), _p(d_gram), _p(d_ngood), _p(stream)))
+
+    def subharmonic_apply_precond(self, norder, n_block, d_precond, d_amp_in, d_amp_out, stream=0):
+        _check(lib().toast_hip_subharmonic_apply_precond_dev(_i64(norder), _i64(n_block), _p(d_precond), _p(d_amp_in),
+                                                             _p(d_amp_out), _p(stream)))
+
+    def periodic_index(self, d_key, d_flags, flag_mask, n_row, n_samp, obs_min, incr, nbins, intervals, d_index, stream=0):
+        """``d_index`` int32 [n_row][n_samp]: the bin of every sample in view whose key flags are clear, -1 elsewhere."""
+        iv = self._small(intervals, interval_dtype)
+        _check(lib().toast_hip_periodic_index_dev(
+            _p(d_key), _p(d_flags), _u8(flag_mask), _i64(n_row), _i64(n_samp), C.c_double(float(obs_min)),
+            C.c_double(float(incr)), _i64(nbins), _p(iv), _i64(iv.size), _p(d_index), _p(stream)))
+
+    def periodic_hits(self, d_index, index_rows, flag_index, d_det_flags, det_flag_mask, amp_offsets, n_samp, nbins, first,
+                      last, d_hits, stream=0):
+        ao = self._small(amp_offsets, np.int64)
+        ir = None if index_rows is None else self._small(index_rows, np.int32)
+        fi = None if flag_index is None else self._small(flag_index, np.int32)
+        for a in (ir, fi):
+            if a is not None and a.size != ao.size:
+                raise RuntimeError("periodic_hits: one row index per amplitude offset")
+        _check(lib().toast_hip_periodic_hits_dev(
+            _p(d_index), _p(ir), _p(fi), _p(d_det_flags), _u8(det_flag_mask), _p(ao), _i64(ao.size), _i64(n_samp),
+            _i64(nbins), _i64(first), _i64(last), _p(d_hits), _p(stream)))
+
+    def periodic_add_to_signal(self, d_index, index_rows, amp_offsets, d_amplitudes, data_index, d_det_data, n_samp, nbins,
+                               stream=0):
+        ao = self._small(amp_offsets, np.int64)
+        di = self._small(data_index, np.int32)
+        ir = None if index_rows is None else self._small(index_rows, np.int32)
+        if di.size != ao.size or (ir is not None and ir.size != ao.size):
+            raise RuntimeError("periodic_add_to_signal: one row index per amplitude offset")
+        _check(lib().toast_hip_periodic_add_to_signal_dev(
+            _p(d_index), _p(ir), _p(ao), _p(d_amplitudes), _p(di), _i64(di.size), _p(d_det_data), _i64(n_samp),
+            _i64(nbins), _p(stream)))
+
+    def periodic_project_signal(self, d_index, index_rows, data_index, d_det_data, flag_index, d_det_flags, det_flag_mask,
+                                amp_offsets, d_amplitudes, n_samp, nbins, path=0, stream=0):
+        ao = self._small(amp_offsets, np.int64)
+        di = self._small(data_index, np.int32)
+        ir = None if index_rows is None else self._small(index_rows, np.int32)
+        fi = None if flag_index is None else self._small(flag_index, np.int32)
+        for a in (di, ir, fi):
+            if a is not None and a.size != ao.size:
+                raise RuntimeError("periodic_project_signal: one row index per amplitude offset")
+        _check(lib().toast_hip_periodic_project_signal_dev(
+            _p(d_index), _p(ir), _p(di), _p(d_det_data), _p(fi), _p(d_det_flags), _u8(det_flag_mask), _p(ao),
+            _p(d_amplitudes), _i64(di.size), _i64(n_samp), _i64(nbins), C.c_int(int(path)), _p(stream)))
+
+    def periodic_apply_precond(self, n_amp, d_hits, d_amp_flags, d_amp_in, d_amp_out, stream=0):
+        _check(lib().toast_hip_periodic_apply_precond_dev(_i64(n_amp), _p(d_hits), _p(d_amp_flags), _p(d_amp_in),
+                                                          _p(d_amp_out), _p(stream)))
+
     def combine_flags(self, d_out, out_index, d_det_flags, n_flag_samp, flag_index, det_flag_mask, d_shared_flags,
                       n_shared_flags, shared_flag_mask, n_samp, intervals, n_out_rows=0, outside_value=-1, stream=0):
         oi = self._small(out_index, np.int32)

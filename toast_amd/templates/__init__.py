@@ -1,4 +1,5 @@
-"""Template amplitudes and the Offset (destriping baseline) template.
+"""Template amplitudes and the destriping templates: Offset (baselines, below), SubHarmonic (templates/subharmonic.py)
+and Periodic (templates/periodic.py).
 
 Reference: src/toast/templates/amplitudes.py (Amplitudes, AmplitudesMap),
 src/toast/templates/template.py (Template), src/toast/templates/offset/offset.py (Offset,
@@ -891,3 +892,53 @@ class Offset(Template):
             if on_dev:
                 accel_data_delete(buf, f"{self.name}_solver_flags")
         self._flag_cache = {}
+
+
+# ---- shared by the templates with batched device sweeps (SubHarmonic, Periodic)
+def amps_to_device(amplitudes, name):
+    """Make the device copy of an amplitude vector the current one (created and uploaded when needed)."""
+    if not amplitudes.accel_exists():
+        amplitudes.accel_create(name)
+        amplitudes.accel_update_device()
+    elif not amplitudes.accel_in_use():
+        amplitudes.accel_update_device()
+
+
+def make_resident(obj, name, borrowed=None):
+    """Make the device copy of ``obj`` current.  ``borrowed``: a list that collects the objects this call had to upload,
+    for ``release_borrowed`` -- set-up code that only READS them hands the host side back as the current one."""
+    if not obj.accel_in_use():
+        if not obj.accel_exists():
+            obj.accel_create(name)
+        obj.accel_update_device()
+        if borrowed is not None:
+            borrowed.append(obj)
+    return obj
+
+
+def release_borrowed(borrowed):
+    """The objects were only read on the device: the host copy is still right and becomes the current side again, so a
+    later edit on the host is uploaded instead of being shadowed by a stale device copy."""
+    for obj in borrowed:
+        obj.accel_used(False)
+    del borrowed[:]
+
+
+def block_amp_offsets(cache, det_start, obs_dets, per_obs, iob, dets):
+    """First amplitude of each detector's block for observation ``iob`` in a detector-major layout where observation
+    ``job`` contributes ``per_obs[job]`` amplitudes to every detector it holds; cached in ``cache``."""
+    key = (iob, tuple(dets))
+    if key not in cache:
+        out = []
+        for d in dets:
+            off = det_start[d]
+            for job in range(iob):
+                if d in obs_dets[job]:
+                    off += per_obs[job]
+            out.append(off)
+        cache[key] = np.array(out, dtype=np.int64)
+    return cache[key]
+
+
+from .periodic import Periodic  # noqa: E402
+from .subharmonic import SubHarmonic  # noqa: E402

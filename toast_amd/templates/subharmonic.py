@@ -1,0 +1,345 @@
+"""SubHarmonic template: Legendre polynomials per detector and view, solved with the map.
+
+Reference: src/toast/templates/subharmonic.py (pure NumPy, one detector and one view at a time).  The amplitude layout
+is the reference's: detector-major; within a detector by observation, then by view, ``order + 1`` values per view.
+
+Two paths.  The host path (``use_accel`` false) is NumPy with the reference's own expressions.  The device path
+(``add_to_signal_multi`` / ``project_signal_multi``, what ``TemplateMatrix`` looks for, and ``_apply_precond`` on
+resident vectors) runs the kernels of csrc/template_basis.hip, which evaluate the basis per sample and never store it.
+
+Two properties of the reference are reproduced on both paths and matter to callers:
+
+* ``project_signal`` applies NO flags and ASSIGNS the amplitudes instead of accumulating (subharmonic.py:205-218);
+* the preconditioner is the inverse of ``detweight * sum_good T_r T_c`` with the detector flags applied (:157-179).
+
+A (detector, view) without a single good sample makes the reference fail inside ``np.linalg.inv``; here both paths raise
+``numpy.linalg.LinAlgError`` with the detector, observation and view in the message.
+"""
+
+import re
+
+import numpy as np
+
+from ..accel import accel_data_create, accel_data_delete, accel_data_update_device, accel_data_update_host, accel_device_ptr
+from ..data import defaults
+from ..traits import ImplementationType, Int, Unicode
+from . import Amplitudes, Template, amps_to_device, block_amp_offsets, make_resident, release_borrowed
+
+
+def legendre_basis(norder, view_len):
+    """[norder][view_len] templates of one view: subharmonic.py:143-155, the same array expressions."""
+    templates = np.zeros((norder, view_len), dtype=np.float64)
+    r = np.linspace(-1.0, 1.0, view_len)
+    for order in range(norder):
+        if order == 0:
+            templates[order] = 1.0
+        elif order == 1:
+            templates[order] = r
+        else:
+            templates[order] = ((2 * order - 1) * r * templates[order - 1] - (order - 1) * templates[order - 2]) / order
+    return templates
+
+
+class SubHarmonic(Template):
+    """Noise fluctuations slower than the length of a view: ``order + 1`` Legendre amplitudes per detector and view."""
+
+    times = Unicode(defaults.times, help="Observation shared key for timestamps")
+    order = Int(1, help="The filter order")
+    noise_model = Unicode(None, allow_none=True, help="Observation key containing the optional noise model")
+
+    def __init__(self, **kwargs):
+        self._precond_on_dev = False
+        super().__init__(**kwargs)
+
+    # ------------------------------------------------------------------ set-up
+    def _initialize(self, new_data):
+        from ..accel import accel_enabled
+
+        self.clear()
+        if self.order < 0:
+            raise RuntimeError("SubHarmonic: the order must not be negative")
+        norder = self.order + 1
+        all_dets = {}
+        self._obs_dets = {}
+        det_pat = re.compile(self.pattern) if self.pattern is not None else None
+        for iob, ob in enumerate(new_data.obs):
+            self._obs_dets[iob] = set()
+            have_data = set(ob.detdata[self.det_data].detectors) if self.det_data in ob.detdata else None
+            for d in ob.select_local_detectors(flagmask=self.det_mask):
+                if have_data is not None and d not in have_data:
+                    continue
+                if det_pat is not None and det_pat.match(d) is None:
+                    continue
+                self._obs_dets[iob].add(d)
+                all_dets.setdefault(d, None)
+        self._all_dets = list(all_dets.keys())
+        self._obs_nview = {iob: len(ob.intervals[self.view]) for iob, ob in enumerate(new_data.obs)}
+        self._det_start = {}
+        offset = 0
+        for det in self._all_dets:
+            self._det_start[det] = offset
+            for iob in range(len(new_data.obs)):
+                if det in self._obs_dets[iob]:
+                    offset += self._obs_nview[iob] * norder
+        self._n_local = offset
+        self._n_global = self._n_local
+        comm = new_data.comm
+        if comm.comm_world is not None:
+            self._n_global = int(comm.allreduce_scalar(self._n_local, op="sum"))
+        self._amp_offset_cache = {}
+        self._templates = {}
+        # inverse of the weighted Gram matrix of every (detector, observation, view) block, in amplitude order
+        self._precond = np.zeros((self._n_local // norder, norder, norder), dtype=np.float64)
+        if self._n_local == 0:
+            return
+        # (set-up runs on the device for a template that will be swept there; the flags it reads are handed back)
+        if accel_enabled() and self.supports_accel():
+            gram, ngood = self._gram_device(new_data)
+        else:
+            gram, ngood = self._gram_host(new_data)
+        self._invert(new_data, gram, ngood)
+
+    @staticmethod
+    def _max_terms():
+        from .. import capi
+
+        return capi.dev.subharmonic_max_terms()
+
+    def _view_templates(self, iob, ob):
+        """The basis of every view of one observation, built on first use by the host path."""
+        if iob not in self._templates:
+            self._templates[iob] = [legendre_basis(self.order + 1, int(vw.last - vw.first)) for vw in ob.intervals[self.view]]
+        return self._templates[iob]
+
+    def _det_weights(self, ob, dets):
+        if self.noise_model is not None and self.noise_model in ob:
+            return np.array([float(ob[self.noise_model].detector_weight(d)) for d in dets], dtype=np.float64)
+        return np.ones(len(dets), dtype=np.float64)
+
+    def _blocks(self, iob, dets):
+        """First block (amplitude index / norder) of each detector for observation ``iob``."""
+        return self.det_amp_offsets(iob, dets) // (self.order + 1)
+
+    def _gram_host(self, new_data):
+        """subharmonic.py:157-178 for every block -> ([n_block][norder][norder], good samples per block)."""
+        norder = self.order + 1
+        gram = np.zeros_like(self._precond)
+        ngood = np.zeros(gram.shape[0], dtype=np.int64)
+        for iob, ob in enumerate(new_data.obs):
+            dets = [d for d in self._all_dets if d in self._obs_dets[iob]]
+            if len(dets) == 0:
+                continue
+            weights = self._det_weights(ob, dets)
+            blocks = self._blocks(iob, dets)
+            for ivw, vw in enumerate(ob.intervals[self.view]):
+                templates = self._view_templates(iob, ob)[ivw]
+                for det, detweight, blk in zip(dets, weights, blocks):
+                    good = slice(0, templates.shape[1], 1)
+                    n_good = templates.shape[1]
+                    if self.det_flags is not None:
+                        flags = ob.detdata[self.det_flags][det, vw.first:vw.last]
+                        good = (flags & self.det_flag_mask) == 0
+                        n_good = int(np.count_nonzero(good))
+                    prec = gram[blk + ivw]
+                    for row in range(norder):
+                        for col in range(row, norder):
+                            prec[row, col] = np.dot(templates[row][good], templates[col][good])
+                            prec[row, col] *= detweight
+                            if row != col:
+                                prec[col, row] = prec[row, col]
+                    ngood[blk + ivw] = n_good
+        return gram, ngood
+
+    def _gram_device(self, new_data):
+        """The same sums by toast_hip_subharmonic_precond_build_dev: one call per observation."""
+        from .. import capi
+
+        norder = self.order + 1
+        gram = np.zeros_like(self._precond)
+        ngood = np.zeros(gram.shape[0], dtype=np.int64)
+        for iob, ob in enumerate(new_data.obs):
+            dets = [d for d in self._all_dets if d in self._obs_dets[iob]]
+            n_view = self._obs_nview[iob]
+            if len(dets) == 0 or n_view == 0:
+                continue
+            f_idx, f_ptr, borrowed = None, 0, []
+            if self.det_flags is not None:
+                fd = make_resident(ob.detdata[self.det_flags], self.det_flags, borrowed)
+                f_idx, f_ptr = fd.indices(dets), accel_device_ptr(fd.buffer)
+            g = np.zeros((len(dets), n_view, norder, norder), dtype=np.float64)
+            n = np.zeros((len(dets), n_view), dtype=np.int64)
+            g_name, n_name = f"{self.name}_gram", f"{self.name}_ngood"
+            accel_data_create(g, g_name)
+            accel_data_create(n, n_name)
+            try:
+                capi.dev.subharmonic_precond_build(norder, f_idx, f_ptr, self.det_flag_mask, self._det_weights(ob, dets),
+                                                   ob.n_local_samples, ob.intervals[self.view].data, accel_device_ptr(g),
+                                                   accel_device_ptr(n))
+                accel_data_update_host(g, g_name)
+                accel_data_update_host(n, n_name)
+            finally:
+                accel_data_delete(g, g_name)
+                accel_data_delete(n, n_name)
+                release_borrowed(borrowed)
+            for k, blk in enumerate(self._blocks(iob, dets)):
+                gram[blk:blk + n_view] = g[k]
+                ngood[blk:blk + n_view] = n[k]
+        return gram, ngood
+
+    def _invert(self, new_data, gram, ngood):
+        """subharmonic.py:179 for every block; a block without good samples has no inverse."""
+        empty = np.flatnonzero(ngood == 0)
+        if empty.size > 0:
+            raise np.linalg.LinAlgError(f"SubHarmonic template {self.name}: {self._describe_block(new_data, int(empty[0]))} has "
+                                        f"no unflagged sample ({empty.size} such blocks): its preconditioner is singular")
+        try:
+            self._precond[:] = np.linalg.inv(gram)
+        except np.linalg.LinAlgError:
+            for blk in range(gram.shape[0]):
+                try:
+                    np.linalg.inv(gram[blk])
+                except np.linalg.LinAlgError as err:
+                    raise np.linalg.LinAlgError(f"SubHarmonic template {self.name}: "
+                                                f"{self._describe_block(new_data, blk)} has a singular preconditioner "
+                                                f"({int(ngood[blk])} unflagged samples)") from err
+            raise
+        if not np.all(np.isfinite(self._precond)):
+            bad = int(np.flatnonzero(~np.isfinite(self._precond).all(axis=(1, 2)))[0])
+            raise np.linalg.LinAlgError(f"SubHarmonic template {self.name}: {self._describe_block(new_data, bad)} has a "
+                                        f"preconditioner that is not finite")
+
+    def _describe_block(self, new_data, blk):
+        norder = self.order + 1
+        for det in self._all_dets:
+            off = self._det_start[det] // norder
+            for iob, ob in enumerate(new_data.obs):
+                if det not in self._obs_dets[iob]:
+                    continue
+                if blk < off + self._obs_nview[iob]:
+                    return f"detector {det}, observation {ob.name}, view {blk - off}"
+                off += self._obs_nview[iob]
+        return f"block {blk}"
+
+    # ------------------------------------------------------------------ Template interface
+    def _detectors(self):
+        return self._all_dets
+
+    def _zeros(self):
+        # no explicit flagging of amplitudes in this template (subharmonic.py:184-188)
+        return Amplitudes(self.data.comm, self._n_global, self._n_local)
+
+    def _supports_accel(self):
+        return self.order + 1 <= self._max_terms()
+
+    def supports_accel(self):
+        return self._supports_accel()
+
+    def _implementations(self):
+        return [ImplementationType.DEFAULT, ImplementationType.COMPILED]
+
+    def det_amp_offsets(self, iob, dets):
+        """First amplitude of each detector's block for observation ``iob``, cached."""
+        per_obs = {job: n * (self.order + 1) for job, n in self._obs_nview.items()}
+        return block_amp_offsets(self._amp_offset_cache, self._det_start, self._obs_dets, per_obs, iob, dets)
+
+    def add_to_signal_multi(self, detectors, amplitudes, **kwargs):
+        """All detectors and all views of an observation in one launch (device-resident buffers only)."""
+        from .. import capi
+
+        if not self._check_enabled() or self._n_local == 0:
+            return
+        amps_to_device(amplitudes, f"{self.name}_amps")
+        for iob, ob in enumerate(self.data.obs):
+            dets = [d for d in detectors if d in self._obs_dets[iob]]
+            if len(dets) == 0:
+                continue
+            dd = ob.detdata[self.det_data]
+            capi.dev.subharmonic_add_to_signal(self.order + 1, self.det_amp_offsets(iob, dets),
+                                               accel_device_ptr(amplitudes.buffer), dd.indices(dets),
+                                               accel_device_ptr(dd.buffer), ob.n_local_samples, ob.intervals[self.view].data)
+
+    def project_signal_multi(self, detectors, amplitudes, **kwargs):
+        """No flags, and the amplitudes are assigned: see the module docstring."""
+        from .. import capi
+
+        if not self._check_enabled() or self._n_local == 0:
+            return
+        amps_to_device(amplitudes, f"{self.name}_amps")
+        for iob, ob in enumerate(self.data.obs):
+            dets = [d for d in detectors if d in self._obs_dets[iob]]
+            if len(dets) == 0:
+                continue
+            dd = ob.detdata[self.det_data]
+            capi.dev.subharmonic_project_signal(self.order + 1, self.det_amp_offsets(iob, dets),
+                                                accel_device_ptr(amplitudes.buffer), dd.indices(dets),
+                                                accel_device_ptr(dd.buffer), ob.n_local_samples, ob.intervals[self.view].data)
+        amplitudes.accel_used(True)
+
+    def _add_to_signal(self, detector, amplitudes, use_accel=None, **kwargs):
+        if detector not in self._all_dets:
+            return
+        if use_accel:
+            self.add_to_signal_multi([detector], amplitudes)
+            return
+        norder = self.order + 1
+        offset = self._det_start[detector]
+        local = amplitudes.local
+        for iob, ob in enumerate(self.data.obs):
+            if detector not in self._obs_dets[iob]:
+                continue
+            row = ob.detdata[self.det_data][detector]
+            for ivw, vw in enumerate(ob.intervals[self.view]):
+                templates = self._view_templates(iob, ob)[ivw]
+                amp_view = local[offset:offset + norder]
+                for order in range(norder):
+                    row[vw.first:vw.last] += templates[order] * amp_view[order]
+                offset += norder
+
+    def _project_signal(self, detector, amplitudes, use_accel=None, **kwargs):
+        if detector not in self._all_dets:
+            return
+        if use_accel:
+            self.project_signal_multi([detector], amplitudes)
+            return
+        norder = self.order + 1
+        offset = self._det_start[detector]
+        local = amplitudes.local
+        for iob, ob in enumerate(self.data.obs):
+            if detector not in self._obs_dets[iob]:
+                continue
+            row = ob.detdata[self.det_data][detector]
+            for ivw, vw in enumerate(ob.intervals[self.view]):
+                amp_view = local[offset:offset + norder]
+                for order, template in enumerate(self._view_templates(iob, ob)[ivw]):
+                    amp_view[order] = np.dot(row[vw.first:vw.last], template)
+                offset += norder
+
+    def _add_prior(self, amplitudes_in, amplitudes_out, **kwargs):
+        return      # no prior for this template (subharmonic.py:220-222)
+
+    def _apply_precond(self, amplitudes_in, amplitudes_out, use_accel=None, **kwargs):
+        if self._n_local == 0:
+            return
+        norder = self.order + 1
+        if amplitudes_in.accel_in_use() or amplitudes_out.accel_in_use():
+            from .. import capi
+
+            amplitudes_in.accel_resident()
+            amplitudes_out.accel_resident()
+            if not self._precond_on_dev:
+                accel_data_create(self._precond, f"{self.name}_precond", owner=self)
+                accel_data_update_device(self._precond, f"{self.name}_precond")
+                self._precond_on_dev = True
+            capi.dev.subharmonic_apply_precond(norder, self._n_local // norder, accel_device_ptr(self._precond),
+                                               accel_device_ptr(amplitudes_in.buffer), accel_device_ptr(amplitudes_out.buffer))
+            return
+        # subharmonic.py:224-236: one small dense product per block
+        a_in = amplitudes_in.local.reshape(-1, norder)
+        amplitudes_out.local.reshape(-1, norder)[:] = np.einsum("brc,bc->br", self._precond, a_in)
+
+    def clear(self):
+        """Release the device copy of the preconditioner and the host basis."""
+        if getattr(self, "_precond_on_dev", False):
+            accel_data_delete(self._precond, f"{self.name}_precond")
+        self._precond_on_dev = False
+        self._templates = {}

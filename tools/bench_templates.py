@@ -1,0 +1,127 @@
+#!/usr/bin/env python3
+"""Time the SubHarmonic / Periodic template sweeps on the GPU next to the stream ceiling of the same byte mix.
+
+Shape: 256 detectors x 720 000 samples at 200 Hz (one GPU's share of BASELINE configs[4]), the `scanning` intervals of an
+ops.SimGround constant-elevation scan (113 sweeps of 6000 samples), 8 % of the samples flagged.  Timed with device events,
+in one process:
+
+* toast_hip_noise_weight_dev over the same rows and views: 16 B per detector-sample read and written, the ceiling of
+  the two add_to_signal sweeps; the 8 B (read-only) sweeps are set against half of its bytes at the same rate;
+* toast_hip_subharmonic_add_to_signal_dev / _project_signal_dev / _precond_build_dev, order 1, 3 and 8;
+* toast_hip_periodic_add_to_signal_dev and _project_signal_dev (LDS path, and global atomics forced), 100 azimuth bins
+  on a shared key.
+
+Prints one JSON line: ms, algorithmic bytes, TB/s and the ratio of each rate to the ceiling's.
+
+    python tools/bench_templates.py [--ndet 256] [--minutes 60] [--rate 200] [--reps 5] [--bins 100]
+"""
+import argparse
+import json
+import os
+import sys
+
+import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+
+def scanning_intervals(minutes, rate):
+    """The sweeps between the turnarounds of a one-hour constant-elevation scan: 113 views of 6000 samples at 200 Hz."""
+    from toast_amd.data import defaults
+    from toast_amd.ops.sim_ground import create_ground_data_from_schedule
+    from toast_amd.schedule import make_ces_schedule
+
+    schedule = make_ces_schedule(1, scan_seconds=minutes * 60.0, az_min=40.0, az_max=70.0, el=50.0)
+    data = create_ground_data_from_schedule(schedule, n_det=2, rate=rate, fov_deg=8.0, scan_rate_az=1.0, scan_accel_az=1.0,
+                                            fix_rate_on_sky=False)
+    ob = data.obs[0]
+    ivl = ob.intervals[defaults.scanning_interval]
+    return ob.n_local_samples, np.array([iv.first for iv in ivl], dtype=np.int64), np.array([iv.last for iv in ivl],
+                                                                                             dtype=np.int64)
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--ndet", type=int, default=256)
+    ap.add_argument("--minutes", type=float, default=60.0)
+    ap.add_argument("--rate", type=float, default=200.0)
+    ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--bins", type=int, default=100)
+    args = ap.parse_args(argv)
+    import torch
+
+    from toast_amd import accel, capi
+    from toast_amd.capi import interval_dtype
+
+    assert accel.accel_enabled(), "no HIP device visible"
+    accel.accel_assign_device(1, 0, 1.0, False)
+    D = capi.dev
+    n_samp, starts, stops = scanning_intervals(args.minutes, args.rate)
+    n_det, n_view = args.ndet, int(starts.size)
+    covered = int(np.sum(stops - starts))
+    gen = torch.Generator(device="cuda").manual_seed(1)
+    sig = torch.randn((n_det, n_samp), dtype=torch.float64, device="cuda", generator=gen)
+    dflags = (torch.rand((n_det, n_samp), device="cuda", generator=gen) < 0.08).to(torch.uint8)
+    idx = np.arange(n_det, dtype=np.int32)
+    ivl = np.zeros(n_view, dtype=interval_dtype)
+    ivl["first"], ivl["last"] = starts, stops
+
+    def timed(fn):
+        fn()
+        torch.cuda.synchronize()
+        times = []
+        for _ in range(args.reps):
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            fn()
+            b.record()
+            torch.cuda.synchronize()
+            times.append(a.elapsed_time(b))
+        return float(np.median(times))
+
+    out = {"bench": "templates", "n_det": n_det, "n_samp": n_samp, "rate": args.rate, "n_view": n_view,
+           "samples_in_views": covered, "bins": args.bins, "reps": args.reps}
+    ms = timed(lambda: D.noise_weight(sig.data_ptr(), n_samp, idx, ivl, np.ones(n_det)))
+    ceiling_rate = 16 * n_det * covered / ms          # bytes per ms
+    out["noise_weight"] = {"ms": round(ms, 4), "bytes": 16 * n_det * covered, "tb_s": round(ceiling_rate / 1e9, 3)}
+
+    def entry(ms, nbytes):
+        return {"ms": round(ms, 4), "bytes": nbytes, "tb_s": round(nbytes / ms / 1e9, 3),
+                "rate_vs_ceiling": round(nbytes / ms / ceiling_rate, 3)}
+
+    for order in (1, 3, 8):
+        norder = order + 1
+        amps = 1.0e-3 * torch.randn(n_det * n_view * norder, dtype=torch.float64, device="cuda", generator=gen)
+        offs = np.arange(n_det, dtype=np.int64) * n_view * norder
+        ms = timed(lambda: D.subharmonic_add_to_signal(norder, offs, amps.data_ptr(), idx, sig.data_ptr(), n_samp, ivl))
+        out[f"subharmonic_add_order{order}"] = entry(ms, 16 * n_det * covered)
+        ms = timed(lambda: D.subharmonic_project_signal(norder, offs, amps.data_ptr(), idx, sig.data_ptr(), n_samp, ivl))
+        out[f"subharmonic_project_order{order}"] = entry(ms, 8 * n_det * covered)
+        gram = torch.zeros((n_det, n_view, norder, norder), dtype=torch.float64, device="cuda")
+        ngood = torch.zeros((n_det, n_view), dtype=torch.int64, device="cuda")
+        ms = timed(lambda: D.subharmonic_precond_build(norder, idx, dflags.data_ptr(), 1, np.ones(n_det), n_samp, ivl,
+                                                       gram.data_ptr(), ngood.data_ptr()))
+        out[f"subharmonic_precond_build_order{order}"] = entry(ms, 1 * n_det * covered)
+        assert int(ngood.min()) > 0
+    # a shared key swept back and forth like the azimuth of a constant-elevation scan
+    key = torch.zeros(n_samp, dtype=torch.float64, device="cuda")
+    for first, last in zip(starts, stops):
+        key[first:last] = torch.linspace(40.0, 70.0, int(last - first), dtype=torch.float64, device="cuda")
+    index = torch.zeros(n_samp, dtype=torch.int32, device="cuda")
+    nbins = args.bins
+    D.periodic_index(key.data_ptr(), 0, 0, 1, n_samp, 40.0, 30.0 / nbins, nbins, ivl, index.data_ptr())
+    amps = 1.0e-3 * torch.randn(n_det * nbins, dtype=torch.float64, device="cuda", generator=gen)
+    offs = np.arange(n_det, dtype=np.int64) * nbins
+    ms = timed(lambda: D.periodic_add_to_signal(index.data_ptr(), None, offs, amps.data_ptr(), idx, sig.data_ptr(), n_samp,
+                                                nbins))
+    # the sweeps cover the whole row; only the samples in view are read and written as signal, the index everywhere
+    out["periodic_add"] = entry(ms, 16 * n_det * covered + 4 * n_samp)
+    for name, path in (("lds", D.PERIODIC_PATH_LDS), ("atomic", D.PERIODIC_PATH_ATOMIC)):
+        ms = timed(lambda: D.periodic_project_signal(index.data_ptr(), None, idx, sig.data_ptr(), idx, dflags.data_ptr(), 1,
+                                                     offs, amps.data_ptr(), n_samp, nbins, path=path))
+        out[f"periodic_project_{name}"] = entry(ms, 9 * n_det * n_samp + 4 * n_samp)
+    print(json.dumps(out))
+
+
+if __name__ == "__main__":
+    main()

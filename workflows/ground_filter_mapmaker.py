@@ -8,6 +8,7 @@ configs[4] is upstream of this path and is not part of
     python workflows/ground_filter_mapmaker.py [--ndet 256] [--minutes 60] [--rate 200] [--nside 2048]
                                                [--iter 10] [--split] [--filter-order 5] [--trend-order 5]
                                                [--polyfilter ORDER] [--common-mode] [--save-map FILE]
+                                               [--subharmonic ORDER] [--periodic-az BINS]
 """
 import argparse
 import os
@@ -22,7 +23,7 @@ from toast_amd import ops  # noqa: E402
 from toast_amd.accel import native  # noqa: E402
 from toast_amd.data import defaults  # noqa: E402
 from toast_amd.sim import create_ground_data  # noqa: E402
-from toast_amd.templates import Offset  # noqa: E402
+from toast_amd.templates import Offset, Periodic, SubHarmonic  # noqa: E402
 
 
 def main(argv=None):
@@ -47,6 +48,12 @@ def main(argv=None):
     ap.add_argument("--polyfilter", type=int, default=None, metavar="ORDER",
                     help="run ops.PolyFilter(order=ORDER, view='throw') before GroundFilter (off by default)")
     ap.add_argument("--common-mode", action="store_true", help="run ops.CommonModeFilter() before GroundFilter (off by default)")
+    ap.add_argument("--subharmonic", type=int, default=None, metavar="ORDER",
+                    help="solve for Legendre polynomials up to ORDER per detector and sweep next to the baselines "
+                         "(templates.SubHarmonic; off by default)")
+    ap.add_argument("--periodic-az", type=int, default=None, metavar="BINS",
+                    help="solve for a ground template of BINS azimuth bins per detector and observation next to the "
+                         "baselines (templates.Periodic, key = azimuth; off by default)")
     ap.add_argument("--save-map", default=None, metavar="FILE", help="save the binned map as a .npy file")
     args = ap.parse_args(argv)
     n_samp = int(args.minutes * 60 * args.rate)
@@ -108,8 +115,12 @@ def main(argv=None):
                                view=defaults.scanning_interval)
     weights = ops.StokesWeights(detector_pointing=det_pointing, mode="IQU", view=defaults.scanning_interval)
     binner = ops.BinMap(pixel_dist="pixel_dist", pixel_pointing=pixels, stokes_weights=weights, full_pointing=True)
-    tmatrix = ops.TemplateMatrix(templates=[Offset(step_time=args.step_time, noise_model=defaults.noise_model,
-                                                   name="baselines")], view=defaults.scanning_interval)
+    templates = [Offset(step_time=args.step_time, noise_model=defaults.noise_model, name="baselines")]
+    if args.subharmonic is not None:
+        templates.append(SubHarmonic(order=args.subharmonic, noise_model=defaults.noise_model, name="subharmonic"))
+    if args.periodic_az is not None:
+        templates.append(Periodic(key=defaults.azimuth, bins=args.periodic_az, name="ground"))
+    tmatrix = ops.TemplateMatrix(templates=templates, view=defaults.scanning_interval)
     mapper = ops.MapMaker(name="mapmaker", det_data=defaults.det_data, binning=binner, template_matrix=tmatrix,
                           iter_min=args.iter, iter_max=args.iter, convergence=1e-30, keep_solver_products=True)
     mapper.apply(data)
