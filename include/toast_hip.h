@@ -1070,6 +1070,98 @@ int toast_hip_fft_r1d_dev(int forward, int64_t length, int64_t count, const doub
                           double scale, void * stream);
 
 /* ------------------------------------------------------------------------------------
+ * Counter-based random streams and PSD noise simulation (toast_amd/csrc/sim_noise.hip).
+ *
+ * Streams are Threefry2x64-20 keyed by (key1, key2); element i of a stream is the first output word at counter
+ * (counter1, counter2 + i), so any part of a stream can be generated anywhere.  uint64: the word; uniform_01:
+ * (0, 1]; uniform_11: [-1, 1]; normal: sqrt(2) erfinv(2 u - 1) with Giles' polynomial erfinv in the reference's
+ * operation order.  The integer and uniform streams are bit-identical to the reference on host and device; the
+ * Gaussian is on the host, and within the device `log` on the device.
+ *
+ * Host entries (no device needed; libm, the reference's operation order):
+ * toast_hip_rng_dist_* [ref: src/toast/_libtoast/math_rng.cpp rng_dist_uint64 / rng_dist_uniform_01 /
+ * rng_dist_uniform_11 / rng_dist_normal -> src/libtoast/src/toast_math_rng.cpp:22-131],
+ * toast_hip_rng_multi_dist_* [ref: math_rng.cpp rng_multi_dist_* -> toast_math_rng.cpp:138-219],
+ * toast_hip_tod_sim_noise_timestream[_batch] [ref: src/toast/_libtoast/tod_simnoise.cpp tod_sim_noise_timestream /
+ * tod_sim_noise_timestream_batch -> src/libtoast/src/toast_tod_simnoise.cpp:154-319] and the interpolation they share,
+ * toast_hip_tod_sim_noise_psd_interp [ref: toast_tod_simnoise.cpp:14-152]: fftlen = the first power of two above
+ * oversample * samples, increment = rate / (fftlen - 1), linear interpolation of log10(sqrt(psd norm) + 0.01 psdmin)
+ * in log10(f + increment), bin 0 forced to 0; interp_psds is [n_batch][fftlen / 2 + 1] amplitudes.  The timestream is
+ * the middle `samples` of (1 / fftlen) hc2r of the scaled Gaussians minus its own mean.  The host transform is a
+ * radix-2 FFT in extended precision (toast_hip_fft_r1d needs a device).
+ * ---------------------------------------------------------------------------------- */
+int toast_hip_rng_dist_uint64(size_t n, uint64_t key1, uint64_t key2, uint64_t counter1, uint64_t counter2,
+                              uint64_t * data);
+int toast_hip_rng_dist_uniform_01(size_t n, uint64_t key1, uint64_t key2, uint64_t counter1, uint64_t counter2,
+                                  double * data);
+int toast_hip_rng_dist_uniform_11(size_t n, uint64_t key1, uint64_t key2, uint64_t counter1, uint64_t counter2,
+                                  double * data);
+int toast_hip_rng_dist_normal(size_t n, uint64_t key1, uint64_t key2, uint64_t counter1, uint64_t counter2,
+                              double * data);
+int toast_hip_rng_multi_dist_uint64(size_t nstream, const size_t * ndata, const uint64_t * key1, const uint64_t * key2,
+                                    const uint64_t * counter1, const uint64_t * counter2, uint64_t ** data);
+int toast_hip_rng_multi_dist_uniform_01(size_t nstream, const size_t * ndata, const uint64_t * key1,
+                                        const uint64_t * key2, const uint64_t * counter1, const uint64_t * counter2,
+                                        double ** data);
+int toast_hip_rng_multi_dist_uniform_11(size_t nstream, const size_t * ndata, const uint64_t * key1,
+                                        const uint64_t * key2, const uint64_t * counter1, const uint64_t * counter2,
+                                        double ** data);
+int toast_hip_rng_multi_dist_normal(size_t nstream, const size_t * ndata, const uint64_t * key1, const uint64_t * key2,
+                                    const uint64_t * counter1, const uint64_t * counter2, double ** data);
+/* Transform length of a simulation: 2, doubled while <= oversample * samples (0 for invalid arguments). */
+int64_t toast_hip_sim_noise_fft_length(int64_t samples, int64_t oversample);
+int toast_hip_tod_sim_noise_psd_interp(double rate, int64_t samples, int64_t oversample, int64_t n_batch,
+                                       int64_t n_binned, const double * binned_freq, const double * binned_psds,
+                                       double * interp_psds);
+int toast_hip_tod_sim_noise_timestream(uint64_t realization, uint64_t telescope, uint64_t component, uint64_t obsindx,
+                                       uint64_t detindx, double rate, int64_t firstsamp, int64_t samples,
+                                       int64_t oversample, const double * freq, const double * psd, int64_t psdlen,
+                                       double * noise);
+int toast_hip_tod_sim_noise_timestream_batch(uint64_t realization, uint64_t telescope, uint64_t component,
+                                             uint64_t obsindx, double rate, int64_t firstsamp, int64_t samples,
+                                             int64_t oversample, int64_t ndet, const uint64_t * detindices,
+                                             int64_t psdlen, const double * freq, const double * psds, double * noise);
+/* Device streams, multi-stream form [ref: toast_math_rng.cpp:138-219]: stream s has ndata[s] elements starting at
+ * element offsets[s] of d_out (offsets NULL: packed one after the other); all per-stream arrays are host arrays,
+ * d_out holds out_len elements.  stream NULL = the manager's stream. */
+int toast_hip_rng_dist_uint64_dev(int64_t n_stream, const size_t * ndata, const uint64_t * key1, const uint64_t * key2,
+                                  const uint64_t * counter1, const uint64_t * counter2, const int64_t * offsets,
+                                  uint64_t * d_out, int64_t out_len, void * stream);
+int toast_hip_rng_dist_uniform_01_dev(int64_t n_stream, const size_t * ndata, const uint64_t * key1,
+                                      const uint64_t * key2, const uint64_t * counter1, const uint64_t * counter2,
+                                      const int64_t * offsets, double * d_out, int64_t out_len, void * stream);
+int toast_hip_rng_dist_uniform_11_dev(int64_t n_stream, const size_t * ndata, const uint64_t * key1,
+                                      const uint64_t * key2, const uint64_t * counter1, const uint64_t * counter2,
+                                      const int64_t * offsets, double * d_out, int64_t out_len, void * stream);
+int toast_hip_rng_dist_normal_dev(int64_t n_stream, const size_t * ndata, const uint64_t * key1, const uint64_t * key2,
+                                  const uint64_t * counter1, const uint64_t * counter2, const int64_t * offsets,
+                                  double * d_out, int64_t out_len, void * stream);
+/* The interpolated amplitudes on the device, d_interp [n_stream][fftlen / 2 + 1] [ref: toast_tod_simnoise.cpp:14-152];
+ * freq / psds are host arrays (one frequency grid, psds [n_stream][n_binned]).  The binned log tables are made on the
+ * host with libm; every bin is evaluated by one thread (bisection instead of the forward walk: freq must not decrease). */
+int toast_hip_sim_noise_psd_interp_dev(double rate, int64_t samples, int64_t oversample, int64_t n_stream,
+                                       int64_t n_binned, const double * freq, const double * psds,
+                                       double * d_interp, void * stream);
+/* SimNoise of one observation on the device [ref: tod_sim_noise_timestream_batch, toast_tod_simnoise.cpp:230-319, and
+ * the mixing loop of src/toast/ops/sim_tod_noise.py:392-398]: for every noise stream s (RNG index detindices[s], PSD
+ * psds[s]) the timestream x_s is simulated and det_data[row] += weight * x_s for every entry e in
+ * [mix_ptr[s], mix_ptr[s + 1]) of the CSR mixing matrix (mix_row[e], mix_weight[e]); all three NULL: stream s goes to
+ * row s with weight 1.  d_det_data is [n_rows][row_stride] on the device, row_stride >= samples.  Streams go through
+ * the spectrum kernel, the cached rocFFT plans and the crop kernels in batches of at most max_batch (0: 64, less when
+ * two work buffers of 8 fftlen bytes per stream would pass 8 GB or 80 % of what the device and the arena can still give);
+ * the result does not depend on the batch size.  Streams
+ * that share a row are added in stream order. */
+int toast_hip_sim_noise_dev(uint64_t realization, uint64_t telescope, uint64_t component, uint64_t obsindx, double rate,
+                            int64_t firstsamp, int64_t samples, int64_t oversample, int64_t n_stream,
+                            const uint64_t * detindices, int64_t n_binned, const double * freq, const double * psds,
+                            const int64_t * mix_ptr, const int32_t * mix_row, const double * mix_weight,
+                            double * d_det_data, int64_t n_rows, int64_t row_stride, int64_t max_batch, void * stream);
+/* Timing switch of toast_hip_sim_noise_dev (bench tool): with on != 0 every later call brackets the spectrum kernel, the
+ * transform and the crop / mix kernels of each batch with events on its stream, synchronises at its end and keeps the
+ * three sums; phase_ms (may be NULL) receives those of the last timed call [ms]: spectrum, transform, crop + mix. */
+int toast_hip_sim_noise_timing(int on, double * phase_ms);
+
+/* ------------------------------------------------------------------------------------
  * Deterministic debug mode (TOAST_HIP_DETERMINISTIC=1 in the environment, or this switch).
  * The production A^T kernels add run-reduced partial sums with fp64 atomics, so zmap / the
  * inverse covariance differ from run to run in the last bits.  With the mode on,

@@ -116,6 +116,7 @@ def lib():
         _lib = C.CDLL(LIB_PATH)
         _lib.toast_hip_last_error.restype = C.c_char_p
         _lib.toast_hip_version.restype = C.c_char_p
+        _lib.toast_hip_sim_noise_fft_length.restype = C.c_int64
     return _lib
 
 
@@ -684,6 +685,110 @@ class OtfPointing(C.Structure):
         ("compact_index", C.c_void_p),
         ("d_hwp_table", C.c_void_p),
     ]
+
+
+# --------------------------------------------------------------------------- random streams / noise simulation (host)
+_RNG_HOST = {"uint64": np.uint64, "uniform_01": np.float64, "uniform_11": np.float64, "normal": np.float64}
+
+
+def _u64(x):
+    x = int(x)
+    if x < 0 or x >= 1 << 64:
+        raise OverflowError(f"{x} is not an unsigned 64-bit integer")
+    return C.c_uint64(x)
+
+
+def _rng_dist(kind, key1, key2, counter1, counter2, data):
+    a = _buf(data, "data", _RNG_HOST[kind], 1)
+    fn = getattr(real_lib(), "toast_hip_rng_dist_" + kind)
+    _check(fn(C.c_size_t(a.size), _u64(key1), _u64(key2), _u64(counter1), _u64(counter2), _p(a)))
+
+
+def rng_dist_uint64(key1, key2, counter1, counter2, data):
+    """``toast._libtoast.rng_dist_uint64``: fills ``data`` (uint64) in place.  Host arithmetic, no device."""
+    _rng_dist("uint64", key1, key2, counter1, counter2, data)
+
+
+def rng_dist_uniform_01(key1, key2, counter1, counter2, data):
+    _rng_dist("uniform_01", key1, key2, counter1, counter2, data)
+
+
+def rng_dist_uniform_11(key1, key2, counter1, counter2, data):
+    _rng_dist("uniform_11", key1, key2, counter1, counter2, data)
+
+
+def rng_dist_normal(key1, key2, counter1, counter2, data):
+    _rng_dist("normal", key1, key2, counter1, counter2, data)
+
+
+def _rng_multi_dist(kind, key1, key2, counter1, counter2, lengths):
+    k1, k2, c1, c2 = (np.ascontiguousarray(x, dtype=np.uint64) for x in (key1, key2, counter1, counter2))
+    n = k1.size
+    if not (k2.size == n and c1.size == n and c2.size == n and len(lengths) == n):
+        raise RuntimeError("rng_multi_dist: one key pair, counter pair and length per stream")
+    out = [np.empty(int(m), dtype=_RNG_HOST[kind]) for m in lengths]
+    nd = (C.c_size_t * max(n, 1))(*[a.size for a in out])
+    ptrs = (C.c_void_p * max(n, 1))(*[a.ctypes.data for a in out])
+    fn = getattr(real_lib(), "toast_hip_rng_multi_dist_" + kind)
+    _check(fn(C.c_size_t(n), nd, _p(k1), _p(k2), _p(c1), _p(c2), ptrs))
+    return out
+
+
+def rng_multi_dist_uint64(key1, key2, counter1, counter2, lengths):
+    """``toast._libtoast.rng_multi_dist_uint64``: a list with one new array per stream."""
+    return _rng_multi_dist("uint64", key1, key2, counter1, counter2, lengths)
+
+
+def rng_multi_dist_uniform_01(key1, key2, counter1, counter2, lengths):
+    return _rng_multi_dist("uniform_01", key1, key2, counter1, counter2, lengths)
+
+
+def rng_multi_dist_uniform_11(key1, key2, counter1, counter2, lengths):
+    return _rng_multi_dist("uniform_11", key1, key2, counter1, counter2, lengths)
+
+
+def rng_multi_dist_normal(key1, key2, counter1, counter2, lengths):
+    return _rng_multi_dist("normal", key1, key2, counter1, counter2, lengths)
+
+
+def sim_noise_fft_length(samples, oversample=2):
+    return int(real_lib().toast_hip_sim_noise_fft_length(_i64(samples), _i64(oversample)))
+
+
+def tod_sim_noise_psd_interp(rate, samples, oversample, freq, psds):
+    """Interpolated amplitudes ``sqrt(psd norm)`` [n_batch][fftlen / 2 + 1] of toast_tod_simnoise.cpp:14-152 (host)."""
+    f = _buf(np.ascontiguousarray(freq, dtype=np.float64), "freq", np.float64, 1)
+    p = _buf(np.ascontiguousarray(psds, dtype=np.float64), "psds", np.float64, 2, (-1, f.size))
+    fftlen = sim_noise_fft_length(samples, oversample)
+    if fftlen <= 0:
+        raise RuntimeError("tod_sim_noise_psd_interp: samples and oversample must be positive")
+    out = np.empty((p.shape[0], fftlen // 2 + 1))
+    _check(real_lib().toast_hip_tod_sim_noise_psd_interp(C.c_double(float(rate)), _i64(samples), _i64(oversample),
+                                                        _i64(p.shape[0]), _i64(f.size), _p(f), _p(p), _p(out)))
+    return out
+
+
+def tod_sim_noise_timestream(realization, telescope, component, obsindx, detindx, rate, firstsamp, oversample, freq,
+                             psd, noise):
+    """``toast._libtoast.tod_sim_noise_timestream``: fills ``noise`` (its length is ``samples``).  Host arithmetic."""
+    f = _buf(freq, "freq", np.float64, 1)
+    p = _buf(psd, "psd", np.float64, 1, (f.size,))
+    out = _buf(noise, "noise", np.float64, 1)
+    _check(real_lib().toast_hip_tod_sim_noise_timestream(
+        _u64(realization), _u64(telescope), _u64(component), _u64(obsindx), _u64(detindx), C.c_double(float(rate)),
+        _i64(firstsamp), _i64(out.size), _i64(oversample), _p(f), _p(p), _i64(f.size), _p(out)))
+
+
+def tod_sim_noise_timestream_batch(realization, telescope, component, obsindx, rate, firstsamp, oversample, detindices,
+                                   freq, psds, noise):
+    """``toast._libtoast.tod_sim_noise_timestream_batch``: ``psds`` [ndet][psdlen], ``noise`` [ndet][samples]."""
+    di = _buf(detindices, "detindices", np.uint64, 1)
+    f = _buf(freq, "freq", np.float64, 1)
+    p = _buf(psds, "psds", np.float64, 2, (di.size, f.size))
+    out = _buf(noise, "noise", np.float64, 2, (di.size, -1))
+    _check(real_lib().toast_hip_tod_sim_noise_timestream_batch(
+        _u64(realization), _u64(telescope), _u64(component), _u64(obsindx), C.c_double(float(rate)), _i64(firstsamp),
+        _i64(out.shape[1]), _i64(oversample), _i64(di.size), _p(di), _i64(f.size), _p(f), _p(p), _p(out)))
 
 
 def otf_pointing(d_boresight, focalplane, nside, nest, nnz, d_shared_flags=0, n_shared_flags=0, shared_flag_mask=0,
@@ -1554,6 +1659,57 @@ class _Dev:
 
     def comm_cov_mult(self, n_px, nnz, d_cov1, d_cov2, stream=0):
         _check(lib().toast_hip_comm_cov_mult_dev(_i64(n_px), _i64(nnz), _p(d_cov1), _p(d_cov2), _p(stream)))
+
+    # ---- random streams and noise simulation (csrc/sim_noise.hip)
+    def rng_multi(self, sampler, lengths, key1, key2, counter1, counter2, d_out, out_len, offsets=None, stream=0):
+        """Streams of ``sampler`` ("uint64", "uniform_01", "uniform_11", "normal") into ``d_out`` (``out_len`` elements):
+        stream s is ``lengths[s]`` elements from ``offsets[s]`` (None: packed)."""
+        if sampler not in _RNG_HOST:
+            raise ValueError(f"unknown sampler {sampler!r}")
+        k1, k2, c1, c2 = (self._small(x, np.uint64) for x in (key1, key2, counter1, counter2))
+        n = k1.size
+        nd = (C.c_size_t * max(n, 1))(*[int(m) for m in lengths])
+        off = None if offsets is None else self._small(offsets, np.int64)
+        if not (k2.size == n and c1.size == n and c2.size == n and len(lengths) == n and (off is None or off.size == n)):
+            raise RuntimeError("rng_multi: one key pair, counter pair, length and offset per stream")
+        fn = getattr(lib(), f"toast_hip_rng_dist_{sampler}_dev")
+        _check(fn(_i64(n), nd, _p(k1), _p(k2), _p(c1), _p(c2), _p(off), _p(d_out), _i64(out_len), _p(stream)))
+
+    def sim_noise_psd_interp(self, rate, samples, oversample, freq, psds, d_interp, stream=0):
+        """``d_interp`` float64 [n_stream][fftlen / 2 + 1]: the interpolated amplitudes."""
+        f = self._small(freq, np.float64)
+        p = self._small(psds, np.float64).reshape(-1, f.size)
+        _check(lib().toast_hip_sim_noise_psd_interp_dev(C.c_double(float(rate)), _i64(samples), _i64(oversample),
+                                                        _i64(p.shape[0]), _i64(f.size), _p(f), _p(p), _p(d_interp),
+                                                        _p(stream)))
+
+    def sim_noise(self, realization, telescope, component, obsindx, rate, firstsamp, samples, oversample, detindices, freq,
+                  psds, d_det_data, n_rows, row_stride=None, mix_ptr=None, mix_row=None, mix_weight=None, max_batch=0,
+                  stream=0):
+        """Simulate one noise stream per entry of ``detindices`` and add them into ``d_det_data`` [n_rows][row_stride]
+        through the CSR mixing matrix (None: stream s -> row s, weight 1).  toast_hip_sim_noise_dev."""
+        di = self._small(detindices, np.uint64)
+        f = self._small(freq, np.float64)
+        p = self._small(psds, np.float64).reshape(-1, f.size)
+        if p.shape[0] != di.size:
+            raise RuntimeError("sim_noise: one PSD per stream index")
+        mp = mr = mw = None
+        if mix_ptr is not None:
+            mp, mr, mw = self._small(mix_ptr, np.int64), self._small(mix_row, np.int32), self._small(mix_weight, np.float64)
+            if mp.size != di.size + 1 or mr.size != mw.size or (mp.size and mp[-1] != mr.size):
+                raise RuntimeError("sim_noise: inconsistent CSR mixing matrix")
+        _check(lib().toast_hip_sim_noise_dev(
+            _u64(realization), _u64(telescope), _u64(component), _u64(obsindx), C.c_double(float(rate)), _i64(firstsamp),
+            _i64(samples), _i64(oversample), _i64(di.size), _p(di), _i64(f.size), _p(f), _p(p), _p(mp), _p(mr), _p(mw),
+            _p(d_det_data), _i64(n_rows), _i64(samples if row_stride is None else row_stride), _i64(max_batch),
+            _p(stream)))
+
+    def sim_noise_timing(self, on):
+        """Switch the phase timing of ``sim_noise`` on / off; returns (spectrum, transform, crop + mix) [ms] of the last
+        timed call (toast_hip_sim_noise_timing)."""
+        ms = (C.c_double * 3)()
+        _check(real_lib().toast_hip_sim_noise_timing(C.c_int(1 if on else 0), ms))
+        return tuple(float(x) for x in ms)
 
     def test_math(self, op, n, d_a, d_b, d_out, stream=0):
         _check(lib().toast_hip_test_math_dev(C.c_int(op), _i64(n), _p(d_a), _p(d_b), _p(d_out), _p(stream)))

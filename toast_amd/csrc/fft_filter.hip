@@ -537,6 +537,14 @@ inline dim3 grid2(int64_t n, int64_t batch) {
 
 }  // namespace
 
+namespace toast_hip {
+// sim_noise.hip: `count` unscaled inverse real transforms of `length` through the cached rocFFT plans, straight from
+// hermitian-interleaved bins [count][length / 2 + 1] (which rocFFT may overwrite) to [count][length] reals.
+void fft_c2r_exec(int64_t length, int64_t count, double2 * d_freq, double * d_time, hipStream_t st) {
+    exec_plan(get_plan(length, count, false), d_freq, d_time, st);
+}
+}  // namespace toast_hip
+
 extern "C" {
 
 int64_t toast_hip_fft_length(int64_t n_samp) {

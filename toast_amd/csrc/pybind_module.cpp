@@ -8,6 +8,7 @@
 // Built with g++ only (no HIP headers): everything device-side sits behind include/toast_hip.h.
 #include <pybind11/numpy.h>
 #include <pybind11/pybind11.h>
+#include <pybind11/stl.h>
 
 #include <cstdint>
 #include <map>
@@ -952,4 +953,84 @@ PYBIND11_MODULE(_libtoast_hip, m) {
         .def("cache", &HipFFTPlanReal1DStore::cache, py::arg("length"), py::arg("n"))
         .def("forward", &HipFFTPlanReal1DStore::forward, py::arg("length"), py::arg("n"))
         .def("backward", &HipFFTPlanReal1DStore::backward, py::arg("length"), py::arg("n"));
+
+    // ---- random streams and noise simulation: the host entries of csrc/sim_noise.hip under the names and argument
+    // order of toast._libtoast (src/toast/_libtoast/math_rng.cpp:9-420, tod_simnoise.cpp:9-170).  No device needed.
+    m.def("rng_dist_uint64", [](uint64_t key1, uint64_t key2, uint64_t counter1, uint64_t counter2, py::buffer data) {
+        Shape s;
+        uint64_t * raw = extract<uint64_t>(data, "data", 1, s, {-1});
+        check(toast_hip_rng_dist_uint64((size_t)s[0], key1, key2, counter1, counter2, raw));
+    }, py::arg("key1"), py::arg("key2"), py::arg("counter1"), py::arg("counter2"), py::arg("data"));
+    m.def("rng_dist_uniform_01", [](uint64_t key1, uint64_t key2, uint64_t counter1, uint64_t counter2, py::buffer data) {
+        Shape s;
+        double * raw = extract<double>(data, "data", 1, s, {-1});
+        check(toast_hip_rng_dist_uniform_01((size_t)s[0], key1, key2, counter1, counter2, raw));
+    }, py::arg("key1"), py::arg("key2"), py::arg("counter1"), py::arg("counter2"), py::arg("data"));
+    m.def("rng_dist_uniform_11", [](uint64_t key1, uint64_t key2, uint64_t counter1, uint64_t counter2, py::buffer data) {
+        Shape s;
+        double * raw = extract<double>(data, "data", 1, s, {-1});
+        check(toast_hip_rng_dist_uniform_11((size_t)s[0], key1, key2, counter1, counter2, raw));
+    }, py::arg("key1"), py::arg("key2"), py::arg("counter1"), py::arg("counter2"), py::arg("data"));
+    m.def("rng_dist_normal", [](uint64_t key1, uint64_t key2, uint64_t counter1, uint64_t counter2, py::buffer data) {
+        Shape s;
+        double * raw = extract<double>(data, "data", 1, s, {-1});
+        check(toast_hip_rng_dist_normal((size_t)s[0], key1, key2, counter1, counter2, raw));
+    }, py::arg("key1"), py::arg("key2"), py::arg("counter1"), py::arg("counter2"), py::arg("data"));
+
+    // multi-stream forms: one new array per stream (the reference returns a list of aligned vectors)
+    auto def_multi = [&m](const char * name, auto fn, auto zero) {
+        using T = decltype(zero);
+        m.def(name, [fn](py::buffer key1, py::buffer key2, py::buffer counter1, py::buffer counter2,
+                         std::vector<size_t> lengths) {
+            const int64_t n = (int64_t)lengths.size();
+            Shape s;
+            const uint64_t * k1 = extract<uint64_t>(key1, "key1", 1, s, {n});
+            const uint64_t * k2 = extract<uint64_t>(key2, "key2", 1, s, {n});
+            const uint64_t * c1 = extract<uint64_t>(counter1, "counter1", 1, s, {n});
+            const uint64_t * c2 = extract<uint64_t>(counter2, "counter2", 1, s, {n});
+            py::list out;
+            std::vector<T *> raw;
+            for (size_t len : lengths) {
+                py::array_t<T> a((py::ssize_t)len);
+                raw.push_back(a.mutable_data());
+                out.append(a);
+            }
+            check(fn((size_t)n, lengths.data(), k1, k2, c1, c2, raw.data()));
+            return out;
+        }, py::arg("key1"), py::arg("key2"), py::arg("counter1"), py::arg("counter2"), py::arg("lengths"));
+    };
+    def_multi("rng_multi_dist_uint64", &toast_hip_rng_multi_dist_uint64, uint64_t(0));
+    def_multi("rng_multi_dist_uniform_01", &toast_hip_rng_multi_dist_uniform_01, double(0));
+    def_multi("rng_multi_dist_uniform_11", &toast_hip_rng_multi_dist_uniform_11, double(0));
+    def_multi("rng_multi_dist_normal", &toast_hip_rng_multi_dist_normal, double(0));
+
+    m.def("tod_sim_noise_timestream", [](uint64_t realization, uint64_t telescope, uint64_t component, uint64_t obsindx,
+                                         uint64_t detindx, double rate, int64_t firstsamp, int64_t oversample,
+                                         py::buffer freq, py::buffer psd, py::buffer noise) {
+        Shape sf, sp, sn;
+        const double * f = extract<double>(freq, "freq", 1, sf, {-1});
+        const double * p = extract<double>(psd, "psd", 1, sp, {-1});
+        double * out = extract<double>(noise, "noise", 1, sn, {-1});
+        if (sp[0] != sf[0]) throw std::runtime_error("Buffer sizes are not consistent.");
+        check(toast_hip_tod_sim_noise_timestream(realization, telescope, component, obsindx, detindx, rate, firstsamp, sn[0],
+                                                 oversample, f, p, sf[0], out));
+    }, py::arg("realization"), py::arg("telescope"), py::arg("component"), py::arg("obsindx"), py::arg("detindx"),
+       py::arg("rate"), py::arg("firstsamp"), py::arg("oversample"), py::arg("freq"), py::arg("psd"), py::arg("noise"));
+    m.def("tod_sim_noise_timestream_batch", [](uint64_t realization, uint64_t telescope, uint64_t component,
+                                               uint64_t obsindx, double rate, int64_t firstsamp, int64_t oversample,
+                                               py::buffer detindices, py::buffer freq, py::buffer psds, py::buffer noise) {
+        Shape sd, sf, sp, sn;
+        const uint64_t * di = extract<uint64_t>(detindices, "detindices", 1, sd, {-1});
+        const double * f = extract<double>(freq, "freq", 1, sf, {-1});
+        if (psds.request().ndim != 2 || noise.request().ndim != 2) throw std::runtime_error("psds and noise should be 2D arrays.");
+        const double * p = extract<double>(psds, "psds", 2, sp, {-1, -1});
+        double * out = extract<double>(noise, "noise", 2, sn, {-1, -1});
+        if (sp[0] != sd[0] || sn[0] != sd[0]) {
+            throw std::runtime_error("First dimension of psds and noise should match the number of detector indices.");
+        }
+        if (sp[1] != sf[0]) throw std::runtime_error("Number of psd points does not match frequency array.");
+        check(toast_hip_tod_sim_noise_timestream_batch(realization, telescope, component, obsindx, rate, firstsamp, sn[1],
+                                                       oversample, sd[0], di, sf[0], f, p, out));
+    }, py::arg("realization"), py::arg("telescope"), py::arg("component"), py::arg("obsindx"), py::arg("rate"),
+       py::arg("firstsamp"), py::arg("oversample"), py::arg("detindices"), py::arg("freq"), py::arg("psds"), py::arg("noise"));
 }

@@ -850,20 +850,42 @@ class Focalplane:
         return groups
 
 
+class Session:
+    """Observing session of an observation: a name and its ``uid`` (reference: src/toast/instrument.py Session)."""
+
+    def __init__(self, name, uid=None):
+        from .noise import name_UID
+
+        self.name = name
+        self.uid = name_UID(name) if uid is None else uid
+
+
 class Telescope:
-    def __init__(self, name, focalplane):
+    def __init__(self, name, focalplane, uid=None):
+        from .noise import name_UID
+
         self.name = name
         self.focalplane = focalplane
+        self.uid = name_UID(name) if uid is None else uid   # instrument.py Telescope: defaults to name_UID(name)
 
 
 class Observation(MutableMapping):
     """One observation: telescope, ``n_local_samples``, ``detdata``, ``shared``, ``intervals``
     and a dict of metadata (e.g. the noise model)."""
 
-    def __init__(self, comm, telescope, n_samples, name="obs", detectors=None):
+    #: whole detectors per process, all samples local (there is no sample-distributed process grid in this data model)
+    local_index_offset = 0
+    is_distributed_by_detector = True
+
+    def __init__(self, comm, telescope, n_samples, name="obs", detectors=None, uid=None, session=None):
+        from .noise import name_UID
+
         self.comm = comm
         self.telescope = telescope
         self.name = name
+        # observation.py:213-236: uid defaults to name_UID(name), the session to one with the observation's name and uid
+        self.uid = name_UID(name) if uid is None else uid
+        self.session = Session(name, uid=self.uid) if session is None else session
         self.n_local_samples = int(n_samples)
         self.local_detectors = list(telescope.focalplane.detectors if detectors is None else detectors)
         self.local_detector_flags = {d: 0 for d in self.local_detectors}

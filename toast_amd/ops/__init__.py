@@ -23,3 +23,4 @@ from .pipeline import Pipeline
 from .poly_filter import CommonModeFilter, PolyFilter
 from .pointing import BuildPixelDistribution, PixelsHealpix, PointingDetectorSimple, StokesWeights
 from .sim_ground import SimGround
+from .sim_tod_noise import SimNoise

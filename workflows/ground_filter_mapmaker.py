@@ -54,6 +54,9 @@ def main(argv=None):
     ap.add_argument("--periodic-az", type=int, default=None, metavar="BINS",
                     help="solve for a ground template of BINS azimuth bins per detector and observation next to the "
                          "baselines (templates.Periodic, key = azimuth; off by default)")
+    ap.add_argument("--sim-noise", action="store_true",
+                    help="draw the detector noise on the device with ops.SimNoise from the observation's AnalyticNoise "
+                         "instead of host white noise (off by default)")
     ap.add_argument("--save-map", default=None, metavar="FILE", help="save the binned map as a .npy file")
     args = ap.parse_args(argv)
     n_samp = int(args.minutes * 60 * args.rate)
@@ -88,11 +91,16 @@ def main(argv=None):
         ground = 20.0 * (np.sin(3 * phase) + 0.5 * phase ** 2)
         sig = ob.detdata[defaults.det_data].data
         for d in range(sig.shape[0]):
-            sig[d] = rng.standard_normal(sig.shape[1]) + ground * (1.0 + 0.1 * rng.standard_normal())
+            white = 0.0 if args.sim_noise else rng.standard_normal(sig.shape[1])
+            sig[d] = white + ground * (1.0 + 0.1 * rng.standard_normal())
     ob = data.obs[0]
     sig = ob.detdata[defaults.det_data].data
     n_samp = ob.n_local_samples
     lap("simulate (host)")
+    if args.sim_noise:
+        ops.SimNoise(noise_model=defaults.noise_model).apply(data, use_accel=True)
+        lap("SimNoise")
+        sig = ob.detdata[defaults.det_data].data
     good = (ob.shared[defaults.shared_flags].data & 1) == 0
     rms_before = float(np.std(sig[0][good]))
     if args.polyfilter is not None:

@@ -68,6 +68,9 @@ def main(argv=None):
                          "the solver keep its packed pointing cache (18-20 B/det-sample, expanded from the boresight in "
                          "batches of detectors) for the duration of the solve")
     ap.add_argument("--profile", action="store_true", help="cProfile of the MapMaker call (top functions by own time)")
+    ap.add_argument("--sim-noise", action="store_true",
+                    help="draw the detector noise on the device with ops.SimNoise from the observation's AnalyticNoise "
+                         "instead of host white noise (off by default)")
     ap.add_argument("--mem-gb", type=float, default=None,
                     help="device memory the arena takes at accel_assign_device (the reference's TOAST_GPU_MEM_GB); default: "
                          "76 B per local detector-sample + 2 GB -- cached pointing, timestreams, the solver's packed cache "
@@ -78,6 +81,9 @@ def main(argv=None):
     mem_gb = args.mem_gb
     if mem_gb is None:
         mem_gb = float(os.environ.get("TOAST_GPU_MEM_GB", 76.0 * args.ndet * n_samp / 2.0 ** 30 + 2.0))
+        if args.sim_noise:
+            # SimNoise's two work buffers: 64 streams x (8 + 8) bytes x fftlen, fftlen <= 4 (n_samp + 1)
+            mem_gb += 64 * 16.0 * 4 * (n_samp + 1) / 2.0 ** 30
     # one process per GPU: rank r owns detectors [r * ndet, (r + 1) * ndet) of one focalplane
     world, rank = int(os.environ.get("WORLD_SIZE", "1")), int(os.environ.get("RANK", "0"))
     comm = None
@@ -119,10 +125,13 @@ def main(argv=None):
     for d in range(sig.shape[0]):  # white noise + one random-walk-ish drift per detector
         # (seeded by the detector's index in the whole focalplane: the same problem however it is sharded)
         rng = np.random.default_rng(1 + args.ndet * rank + d)
-        sig[d] = rng.standard_normal(n_samp)
+        sig[d] = 0.0 if args.sim_noise else rng.standard_normal(n_samp)
         sig[d] += np.repeat(rng.standard_normal((n_samp + 1999) // 2000), 2000)[:n_samp]
         ob.detdata[defaults.det_flags].data[d] = (rng.random(n_samp) < 0.01).astype(np.uint8) * defaults.det_mask_invalid
     ph.lap("simulate (host)")
+    if args.sim_noise:
+        ops.SimNoise(noise_model=defaults.noise_model).apply(data, use_accel=True)
+        ph.lap("SimNoise")
     if not args.no_filter:
         ops.NoiseFilter(noise_model=defaults.noise_model).apply(data)
         ph.lap("NoiseFilter")

@@ -7,7 +7,7 @@ configs[0] (4 detectors x 10 min @ 100 Hz, Nside 64) by default, configs[1] with
 ``--ndet 64 --minutes 60 --nside 512``.  Everything numerical runs on the MI355X.
 
     python workflows/sim_satellite_simple.py [--ndet 4] [--minutes 10] [--rate 100] [--nside 64]
-                                             [--destripe] [--out map.npz]
+                                             [--destripe] [--sim-noise] [--out map.npz]
 """
 import argparse
 import os
@@ -32,6 +32,9 @@ def main(argv=None):
     ap.add_argument("--nside", type=int, default=64)
     ap.add_argument("--destripe", action="store_true", help="solve for baseline offsets (MapMaker PCG)")
     ap.add_argument("--full-pointing", action="store_true", help="cache pixels / weights instead of recomputing")
+    ap.add_argument("--sim-noise", action="store_true",
+                    help="draw the detector noise on the device with ops.SimNoise from the observation's AnalyticNoise "
+                         "(1/f included) instead of host white noise")
     ap.add_argument("--out", default=None)
     args = ap.parse_args(argv)
 
@@ -42,9 +45,13 @@ def main(argv=None):
     rng = np.random.default_rng(1)
     for ob in data.obs:
         sig = ob.detdata[defaults.det_data].data
-        sig[:] = rng.standard_normal(sig.shape)
+        sig[:] = 0.0 if args.sim_noise else rng.standard_normal(sig.shape)
         if args.destripe:
             sig += (rng.standard_normal((sig.shape[0], 1)) * 5.0)  # one offset per detector
+    if args.sim_noise:
+        from toast_amd.accel import accel_enabled
+
+        ops.SimNoise(noise_model=defaults.noise_model).apply(data, use_accel=accel_enabled())
     det_pointing = ops.PointingDetectorSimple()
     pixels = ops.PixelsHealpix(detector_pointing=det_pointing, nside=args.nside, nest=True)
     weights = ops.StokesWeights(detector_pointing=det_pointing, mode="IQU", hwp_angle=defaults.hwp_angle)
