@@ -1162,6 +1162,71 @@ int toast_hip_sim_noise_dev(uint64_t realization, uint64_t telescope, uint64_t c
 int toast_hip_sim_noise_timing(int on, double * phase_ms);
 
 /* ------------------------------------------------------------------------------------
+ * Noise estimation: lagged covariance sums and the prewhitening high-pass (toast_amd/csrc/noise_estim.hip).
+ *
+ * Host entries (no device needed) [ref: src/toast/_libtoast/fod_psd.cpp fod_autosums / fod_crosssums ->
+ * src/libtoast/src/toast_fod_psd.cpp:12-47, :49-93]: plain sequential loops in the reference's order, so the sums are
+ * bit-identical to the reference's.  Samples with good == 0 count as zero in sums and hits; lag l runs over
+ * i < (all_sums ? n - l : n - lagmax) (nothing when that is <= 0; lagmax > n is legal); sums / hits are accumulated
+ * into; symmetric adds the swapped products x[i + l] y[i] and doubles the hits of every lag except 0.
+ * ---------------------------------------------------------------------------------- */
+int toast_hip_fod_autosums(int64_t n, const double * x, const uint8_t * good, int64_t lagmax, double * sums,
+                           int64_t * hits, int64_t all_sums);
+int toast_hip_fod_crosssums(int64_t n, const double * x, const double * y, const uint8_t * good, int64_t lagmax,
+                            double * sums, int64_t * hits, int64_t all_sums, int64_t symmetric);
+/* Running average over the unflagged samples [ref: src/toast/ops/noise_estimation_utils.py:13-66
+ * flagged_running_average]: average[i] = mean of signal[k], bad[k] == 0, over k in [i - window / 2, i + (window - 1) / 2]
+ * clipped to the row -- the window of fftconvolve(..., ones(window), mode="same") -- and 0 where no such sample exists;
+ * hits[i] (may be NULL) is their number.  Host arithmetic: a sliding sum in extended precision. */
+int toast_hip_flagged_running_average(int64_t n, const double * signal, const uint8_t * bad, int64_t window,
+                                      double * average, int64_t * hits);
+/* The lagged sums of a batch of pairs over a table of segments [ref: toast_fod_psd.cpp:12-93 as driven by
+ * src/toast/ops/noise_estimation_utils.py:325-373].  Pair p correlates rows row1[p] and row2[p] (equal: auto) of
+ * d_data [n_rows][stride] under row good_row[p] of d_good [n_good_rows][good_stride] (non-zero = use).  Segment s is
+ * the samples [seg_first[s], seg_last[s]) with its own all_sums flag; its sums go to realization seg_realization[s].
+ * d_sums (fp64) and d_hits (int64) are [n_pair][n_real][lagmax] and are accumulated into.  Hits are exact.  Sums are
+ * partial sums of fixed 8192-sample chunks of each segment, added in chunk order: bit-reproducible, independent of
+ * max_batch (0: bounded by 1 GB of scratch) and of the order of the pairs.  All index arrays are host arrays. */
+int toast_hip_fod_sums_dev(int64_t n_pair, const int32_t * row1, const int32_t * row2, const int32_t * good_row,
+                           const double * d_data, int64_t n_rows, int64_t stride, const uint8_t * d_good,
+                           int64_t n_good_rows, int64_t good_stride, int64_t n_seg, const int64_t * seg_first,
+                           const int64_t * seg_last, const int32_t * seg_all_sums, const int32_t * seg_realization,
+                           int64_t n_real, int64_t lagmax, int symmetric, double * d_sums, int64_t * d_hits,
+                           int64_t max_batch, void * stream);
+/* highpass_flagged_signal on the device [ref: noise_estimation_utils.py:69-101]: d_out[r] = x - running average of the
+ * good samples of x = row in_row[r] of d_in under row good_row[r] of d_good, for all n samples (flagged ones included);
+ * zeros when the row has no good sample.  d_in is not modified.  Window sums are exact integers (counts) and
+ * double-double (values). */
+int toast_hip_noise_estim_highpass_dev(int64_t n_row, int64_t n, int64_t window, const double * d_in, int64_t n_in_rows,
+                                       int64_t in_stride, const int32_t * in_row, const uint8_t * d_good,
+                                       int64_t n_good_rows, int64_t good_stride, const int32_t * good_row,
+                                       double * d_out, int64_t out_stride, void * stream);
+/* The good mask of pair p [ref: src/toast/ops/noise_estimation.py:443-447, :482-494]:
+ * d_good[p][i] = !((shared[i] & shared_flag_mask) | ((det_flags[row1[p]][i] | det_flags[row2[p]][i]) & det_flag_mask));
+ * either flag array may be NULL. */
+int toast_hip_noise_estim_pair_good_dev(int64_t n_pair, int64_t n, const uint8_t * d_shared_flags, uint8_t shared_flag_mask,
+                                        const uint8_t * d_det_flags, int64_t n_flag_rows, int64_t flag_stride,
+                                        uint8_t det_flag_mask, const int32_t * row1, const int32_t * row2,
+                                        uint8_t * d_good, int64_t good_stride, void * stream);
+/* Decimation [::step] [ref: noise_estimation.py:550-553 after noise_estimation_utils.py:318-320]: row r of d_out is
+ * every step-th sample of row r of d_in, zero where row good_row[r] of d_good is zero; every row of d_good is decimated
+ * into d_good_out. */
+int toast_hip_noise_estim_decimate_dev(int64_t n_row, int64_t n, int64_t step, const double * d_in, int64_t in_stride,
+                                       const int32_t * good_row, const uint8_t * d_good, int64_t n_good_rows,
+                                       int64_t good_stride, double * d_out, int64_t out_stride, uint8_t * d_good_out,
+                                       int64_t good_out_stride, void * stream);
+/* Download of `count` sums and hits (the only data ops.NoiseEstim brings back from the device). */
+int toast_hip_noise_estim_fetch(int64_t count, const double * d_sums, double * sums, const int64_t * d_hits,
+                                int64_t * hits, void * stream);
+/* The register-only FP64 FMA loop of the sums kernel in its launch shape (bench tool): n_block workgroups of 256 lanes,
+ * 8 x iterations FMAs per lane; *ms receives the kernel time. */
+int toast_hip_noise_estim_fma_ceiling(int64_t n_block, int64_t iterations, double * ms, void * stream);
+/* Timing switch (bench tool): with on != 0 the device entries above time their phases with events and synchronise;
+ * phase_ms (may be NULL) receives the sums since the last call of this switch [ms]: high-pass, sums (with hits),
+ * reduction, download.  Every call clears them. */
+int toast_hip_noise_estim_timing(int on, double * phase_ms);
+
+/* ------------------------------------------------------------------------------------
  * Deterministic debug mode (TOAST_HIP_DETERMINISTIC=1 in the environment, or this switch).
  * The production A^T kernels add run-reduced partial sums with fp64 atomics, so zmap / the
  * inverse covariance differ from run to run in the last bits.  With the mode on,

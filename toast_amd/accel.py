@@ -110,7 +110,8 @@ KIND_DEFAULT, KIND_STREAMED, KIND_SCATTER = 0, 1, 2
 
 
 def accel_data_create(data, name="None", zero_out=False, owner=None, kind=KIND_DEFAULT):
-    """reference accel.py:147-176.  ``owner``: object whose lifetime bounds the device copy.  ``kind``: KIND_STREAMED for
+    """reference accel.py:147-176.  ``owner``: object whose lifetime bounds the device copy (None: the array itself
+    when it owns its memory).  ``kind``: KIND_STREAMED for
     a timestream that kernels read and write in their sweeps, KIND_SCATTER for the target of a scatter with atomics (a
     map, an amplitude vector); toast_hip_accel_create_kind."""
     import weakref
@@ -132,8 +133,16 @@ def accel_data_create(data, name="None", zero_out=False, owner=None, kind=KIND_D
         native().accel_create(arr, name, int(kind))
     if zero_out:
         native().accel_reset(arr, name)
+    if owner is None and arr is data and arr.flags.owndata:
+        # an array that owns its memory and has no other owner bounds its device copy itself: when it is dropped
+        # without accel_data_delete (an exception between create and delete), its memory goes back to the allocator
+        # and the entry would be mistaken for the next array at that address
+        owner = arr
     if owner is not None:
         ptr = arr.ctypes.data
+        stale = _finalizers.pop(ptr, None)
+        if stale is not None:
+            stale.detach()
         _finalizers[ptr] = weakref.finalize(owner, _release, ptr, arr.nbytes, name)
     return data
 

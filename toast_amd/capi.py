@@ -791,6 +791,41 @@ def tod_sim_noise_timestream_batch(realization, telescope, component, obsindx, r
         _i64(out.shape[1]), _i64(oversample), _i64(di.size), _p(di), _i64(f.size), _p(f), _p(p), _p(out)))
 
 
+def fod_autosums(x, good, lagmax, sums, hits, all_sums):
+    """``toast._libtoast.fod_autosums``: accumulate the lagged sums and hits of ``x`` (host, the reference's loops)."""
+    xx = _buf(x, "x", np.float64, 1)
+    g = _buf(good, "good", np.uint8, 1)
+    s = _buf(sums, "sums", np.float64, 1)
+    h = _buf(hits, "hits", np.int64, 1)
+    if g.size != xx.size or s.size != int(lagmax) or h.size != int(lagmax):
+        raise RuntimeError("Buffer sizes are not consistent.")
+    _check(real_lib().toast_hip_fod_autosums(_i64(xx.size), _p(xx), _p(g), _i64(lagmax), _p(s), _p(h),
+                                             _i64(1 if all_sums else 0)))
+
+
+def fod_crosssums(x, y, good, lagmax, sums, hits, all_sums, symmetric):
+    """``toast._libtoast.fod_crosssums``: accumulate the lagged sums and hits of ``x`` against ``y`` (host)."""
+    xx = _buf(x, "x", np.float64, 1)
+    yy = _buf(y, "y", np.float64, 1)
+    g = _buf(good, "good", np.uint8, 1)
+    s = _buf(sums, "sums", np.float64, 1)
+    h = _buf(hits, "hits", np.int64, 1)
+    if yy.size != xx.size or g.size != xx.size or s.size != int(lagmax) or h.size != int(lagmax):
+        raise RuntimeError("Buffer sizes are not consistent.")
+    _check(real_lib().toast_hip_fod_crosssums(_i64(xx.size), _p(xx), _p(yy), _p(g), _i64(lagmax), _p(s), _p(h),
+                                              _i64(1 if all_sums else 0), _i64(1 if symmetric else 0)))
+
+
+def flagged_running_average(signal, bad, window):
+    """(average, hits) of toast_hip_flagged_running_average: the mean of the unflagged samples in the window of
+    ``fftconvolve(..., ones(window), mode="same")`` and their number (host)."""
+    x = _buf(np.ascontiguousarray(signal, dtype=np.float64), "signal", np.float64, 1)
+    b = _buf(np.ascontiguousarray(bad, dtype=np.uint8), "flag", np.uint8, 1, (x.size,))
+    avg, hits = np.zeros(x.size), np.zeros(x.size, dtype=np.int64)
+    _check(real_lib().toast_hip_flagged_running_average(_i64(x.size), _p(x), _p(b), _i64(window), _p(avg), _p(hits)))
+    return avg, hits
+
+
 def otf_pointing(d_boresight, focalplane, nside, nest, nnz, d_shared_flags=0, n_shared_flags=0, shared_flag_mask=0,
                  d_hwp=0, n_hwp=0, epsilon=None, gamma=None, cal=None, IAU=False, d_compact_pixels=0,
                  compact_index=None, d_hwp_table=0):
@@ -1709,6 +1744,74 @@ class _Dev:
         timed call (toast_hip_sim_noise_timing)."""
         ms = (C.c_double * 3)()
         _check(real_lib().toast_hip_sim_noise_timing(C.c_int(1 if on else 0), ms))
+        return tuple(float(x) for x in ms)
+
+    # ---- noise estimation (csrc/noise_estim.hip)
+    def fod_sums(self, row1, row2, good_row, d_data, n_rows, stride, d_good, n_good_rows, good_stride, seg_first,
+                 seg_last, seg_all_sums, seg_realization, n_real, lagmax, symmetric, d_sums, d_hits, max_batch=0,
+                 stream=0):
+        """Lagged sums of a batch of pairs over a table of segments into ``d_sums`` / ``d_hits``
+        [n_pair][n_real][lagmax] (accumulated).  toast_hip_fod_sums_dev."""
+        r1, r2, rg = (self._small(x, np.int32) for x in (row1, row2, good_row))
+        sf, sl = self._small(seg_first, np.int64), self._small(seg_last, np.int64)
+        sa, sr = self._small(seg_all_sums, np.int32), self._small(seg_realization, np.int32)
+        if not (r2.size == r1.size and rg.size == r1.size and sl.size == sf.size and sa.size == sf.size and sr.size == sf.size):
+            raise RuntimeError("fod_sums: inconsistent pair or segment tables")
+        _check(lib().toast_hip_fod_sums_dev(
+            _i64(r1.size), _p(r1), _p(r2), _p(rg), _p(d_data), _i64(n_rows), _i64(stride), _p(d_good), _i64(n_good_rows),
+            _i64(good_stride), _i64(sf.size), _p(sf), _p(sl), _p(sa), _p(sr), _i64(n_real), _i64(lagmax),
+            C.c_int(1 if symmetric else 0), _p(d_sums), _p(d_hits), _i64(max_batch), _p(stream)))
+
+    def noise_estim_highpass(self, n, window, d_in, n_in_rows, in_stride, in_row, d_good, n_good_rows, good_stride,
+                             good_row, d_out, out_stride, stream=0):
+        """``d_out[r]`` = row ``in_row[r]`` of ``d_in`` minus its flagged running average under row ``good_row[r]`` of
+        ``d_good``.  toast_hip_noise_estim_highpass_dev."""
+        ir, gr = self._small(in_row, np.int32), self._small(good_row, np.int32)
+        if ir.size != gr.size:
+            raise RuntimeError("noise_estim_highpass: one flag row per signal row")
+        _check(lib().toast_hip_noise_estim_highpass_dev(
+            _i64(ir.size), _i64(n), _i64(window), _p(d_in), _i64(n_in_rows), _i64(in_stride), _p(ir), _p(d_good),
+            _i64(n_good_rows), _i64(good_stride), _p(gr), _p(d_out), _i64(out_stride), _p(stream)))
+
+    def noise_estim_pair_good(self, n, d_shared_flags, shared_flag_mask, d_det_flags, n_flag_rows, flag_stride,
+                              det_flag_mask, row1, row2, d_good, good_stride, stream=0):
+        """The good mask of every pair from the resident flags.  toast_hip_noise_estim_pair_good_dev."""
+        r1, r2 = self._small(row1, np.int32), self._small(row2, np.int32)
+        if r1.size != r2.size:
+            raise RuntimeError("noise_estim_pair_good: two rows per pair")
+        _check(lib().toast_hip_noise_estim_pair_good_dev(
+            _i64(r1.size), _i64(n), _p(d_shared_flags or None), C.c_uint8(int(shared_flag_mask) & 255),
+            _p(d_det_flags or None), _i64(n_flag_rows), _i64(flag_stride), C.c_uint8(int(det_flag_mask) & 255), _p(r1),
+            _p(r2), _p(d_good), _i64(good_stride), _p(stream)))
+
+    def noise_estim_decimate(self, n, step, d_in, in_stride, good_row, d_good, n_good_rows, good_stride, d_out,
+                             out_stride, d_good_out, good_out_stride, stream=0):
+        """Every ``step``-th sample of the rows of ``d_in`` (zero where flagged) and of ``d_good``.
+        toast_hip_noise_estim_decimate_dev."""
+        gr = self._small(good_row, np.int32)
+        _check(lib().toast_hip_noise_estim_decimate_dev(
+            _i64(gr.size), _i64(n), _i64(step), _p(d_in), _i64(in_stride), _p(gr), _p(d_good), _i64(n_good_rows),
+            _i64(good_stride), _p(d_out), _i64(out_stride), _p(d_good_out), _i64(good_out_stride), _p(stream)))
+
+    def noise_estim_fetch(self, d_sums, sums, d_hits, hits, stream=0):
+        """Download sums (float64) and hits (int64) of equal size.  toast_hip_noise_estim_fetch."""
+        s = _buf(sums, "sums", np.float64, sums.ndim)
+        h = _buf(hits, "hits", np.int64, hits.ndim)
+        if s.size != h.size:
+            raise RuntimeError("noise_estim_fetch: sums and hits differ in size")
+        _check(real_lib().toast_hip_noise_estim_fetch(_i64(s.size), _p(d_sums), _p(s), _p(d_hits), _p(h), _p(stream)))
+
+    def noise_estim_fma_ceiling(self, n_block, iterations, stream=0):
+        """Kernel time [ms] of the register-only FMA loop of the sums kernel (toast_hip_noise_estim_fma_ceiling)."""
+        ms = C.c_double(0.0)
+        _check(real_lib().toast_hip_noise_estim_fma_ceiling(_i64(n_block), _i64(iterations), C.byref(ms), _p(stream)))
+        return float(ms.value)
+
+    def noise_estim_timing(self, on):
+        """Switch the phase timing of the noise estimation entries on / off; returns (high-pass, sums, reduction,
+        download) [ms] summed since the last call of this switch (toast_hip_noise_estim_timing)."""
+        ms = (C.c_double * 4)()
+        _check(real_lib().toast_hip_noise_estim_timing(C.c_int(1 if on else 0), ms))
         return tuple(float(x) for x in ms)
 
     def test_math(self, op, n, d_a, d_b, d_out, stream=0):

@@ -1033,4 +1033,31 @@ PYBIND11_MODULE(_libtoast_hip, m) {
                                                        oversample, sd[0], di, sf[0], f, p, out));
     }, py::arg("realization"), py::arg("telescope"), py::arg("component"), py::arg("obsindx"), py::arg("rate"),
        py::arg("firstsamp"), py::arg("oversample"), py::arg("detindices"), py::arg("freq"), py::arg("psds"), py::arg("noise"));
+
+    // ---- lagged covariance sums: the host entries of csrc/noise_estim.hip under the names, argument order and size
+    // checks of toast._libtoast (src/toast/_libtoast/fod_psd.cpp:10-124).  No device needed.
+    m.def("fod_crosssums", [](py::buffer x, py::buffer y, py::buffer good, int64_t lagmax, py::buffer sums,
+                              py::buffer hits, int64_t all_sums, int64_t symmetric) {
+        Shape sx, sy, sg, ss, sh;
+        const double * rx = extract<double>(x, "x", 1, sx, {-1});
+        const double * ry = extract<double>(y, "y", 1, sy, {-1});
+        const uint8_t * rg = extract<uint8_t>(good, "good", 1, sg, {-1});
+        double * rs = extract<double>(sums, "sums", 1, ss, {-1});
+        int64_t * rh = extract<int64_t>(hits, "hits", 1, sh, {-1});
+        if (sy[0] != sx[0] || sg[0] != sx[0]) throw std::runtime_error("Buffer sizes are not consistent.");
+        if (ss[0] != lagmax || sh[0] != lagmax) throw std::runtime_error("Buffer sizes are not consistent.");
+        check(toast_hip_fod_crosssums(sx[0], rx, ry, rg, lagmax, rs, rh, all_sums, symmetric));
+    }, py::arg("x"), py::arg("y"), py::arg("good"), py::arg("lagmax"), py::arg("sums"), py::arg("hits"),
+       py::arg("all_sums"), py::arg("symmetric"));
+    m.def("fod_autosums", [](py::buffer x, py::buffer good, int64_t lagmax, py::buffer sums, py::buffer hits,
+                             int64_t all_sums) {
+        Shape sx, sg, ss, sh;
+        const double * rx = extract<double>(x, "x", 1, sx, {-1});
+        const uint8_t * rg = extract<uint8_t>(good, "good", 1, sg, {-1});
+        double * rs = extract<double>(sums, "sums", 1, ss, {-1});
+        int64_t * rh = extract<int64_t>(hits, "hits", 1, sh, {-1});
+        if (sg[0] != sx[0]) throw std::runtime_error("Buffer sizes are not consistent.");
+        if (ss[0] != lagmax || sh[0] != lagmax) throw std::runtime_error("Buffer sizes are not consistent.");
+        check(toast_hip_fod_autosums(sx[0], rx, rg, lagmax, rs, rh, all_sums));
+    }, py::arg("x"), py::arg("good"), py::arg("lagmax"), py::arg("sums"), py::arg("hits"), py::arg("all_sums"));
 }

@@ -7,7 +7,7 @@ configs[0] (4 detectors x 10 min @ 100 Hz, Nside 64) by default, configs[1] with
 ``--ndet 64 --minutes 60 --nside 512``.  Everything numerical runs on the MI355X.
 
     python workflows/sim_satellite_simple.py [--ndet 4] [--minutes 10] [--rate 100] [--nside 64]
-                                             [--destripe] [--sim-noise] [--out map.npz]
+                                             [--destripe] [--sim-noise] [--estimate-noise] [--out map.npz]
 """
 import argparse
 import os
@@ -35,6 +35,9 @@ def main(argv=None):
     ap.add_argument("--sim-noise", action="store_true",
                     help="draw the detector noise on the device with ops.SimNoise from the observation's AnalyticNoise "
                          "(1/f included) instead of host white noise")
+    ap.add_argument("--estimate-noise", action="store_true",
+                    help="measure the noise PSDs from the timestreams with ops.NoiseEstim; the measured model replaces "
+                         "the analytic one for what follows (detector weights)")
     ap.add_argument("--out", default=None)
     args = ap.parse_args(argv)
 
@@ -52,6 +55,20 @@ def main(argv=None):
         from toast_amd.accel import accel_enabled
 
         ops.SimNoise(noise_model=defaults.noise_model).apply(data, use_accel=accel_enabled())
+    if args.estimate_noise:
+        ops.NoiseEstim(out_model="measured_noise", lagmax=min(10000, n_samp // 4)).apply(data)
+        for ob in data.obs:
+            truth, measured = ob[defaults.noise_model], ob["measured_noise"]
+            ratios = {}
+            for det in measured.keys:
+                f, p = measured.freq(det), measured.psd(det)
+                band = f > args.rate / 4                      # the upper half of the band
+                ratios.setdefault(truth.NET(det), []).append(
+                    float(np.mean(p[band] / np.interp(f[band], truth.freq(det), truth.psd(det)))))
+            for net, r in sorted(ratios.items()):
+                print(f"NoiseEstim, {len(r)} detectors with NET {net:g}: estimated / input PSD over the upper half band "
+                      f"{np.mean(r):.4f} (min {np.min(r):.4f}, max {np.max(r):.4f})")
+            ob[defaults.noise_model] = measured
     det_pointing = ops.PointingDetectorSimple()
     pixels = ops.PixelsHealpix(detector_pointing=det_pointing, nside=args.nside, nest=True)
     weights = ops.StokesWeights(detector_pointing=det_pointing, mode="IQU", hwp_angle=defaults.hwp_angle)
