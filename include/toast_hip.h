@@ -1227,6 +1227,49 @@ int toast_hip_noise_estim_fma_ceiling(int64_t n_block, int64_t iterations, doubl
 int toast_hip_noise_estim_timing(int on, double * phase_ms);
 
 /* ------------------------------------------------------------------------------------
+ * Half-wave-plate demodulation (csrc/demod.hip) [ref: src/toast/ops/demodulation.py].
+ *
+ * toast_hip_demod_fir_dev: batched FIR "same" convolution with modulation of the input and decimation of the output,
+ * i.e. fftconvolve(m * x, taps, mode="same")[offset % nskip :: nskip] of Lowpass.__call__ / Bandpass.__call__
+ * [ref: demodulation.py:58-61, :87-89] evaluated in direct form:
+ *     out[e][j] = sum_{k < n_taps} taps[k] y[i_j + c - k],  i_j = offset % nskip + j nskip,  c = (n_taps - 1) / 2,
+ *     y[i] = m[i] x[i] for 0 <= i < n and 0 elsewhere,
+ * x = row in_row[e] of d_in, out = row out_row[e] of d_out (ceil((n - offset % nskip) / nskip) samples).  m is
+ *     TOAST_HIP_DEMOD_MOD_NONE     1 (demod0, the band-pass),
+ *     TOAST_HIP_DEMOD_MOD_WEIGHTS  2 w_c / sqrt(w_q^2 + w_u^2) from row mod_row[e] of the Stokes weights d_mod
+ *                                  [row][n][nnz] with Q at component comp_q, U at comp_q + 1 and c = mod_comp[e] one of
+ *                                  the two [ref: demodulation.py:726-740]; never stored,
+ *     TOAST_HIP_DEMOD_MOD_ARRAY    row mod_row[e] of d_mod [row][n] (the 2f factors) [ref: demodulation.py:762-765].
+ * mod_stride counts the doubles of one row of d_mod.  taps is a host array.  Any n, n_taps, nskip >= 1.  fp64, explicit
+ * FMAs in the fixed order (k mod nskip, k / nskip) without atomics: the bits of an output do not depend on the batch,
+ * the order of the entries or the launch.  d_out must not overlap d_in / d_mod. */
+#define TOAST_HIP_DEMOD_MOD_NONE 0
+#define TOAST_HIP_DEMOD_MOD_WEIGHTS 1
+#define TOAST_HIP_DEMOD_MOD_ARRAY 2
+/* taps of one phase staged at a time: tap counts above nskip times this take more than one pass over the staging */
+#define TOAST_HIP_DEMOD_TAP_CHUNK 512
+int toast_hip_demod_fir_dev(int64_t n_entry, int64_t n, int64_t n_taps, const double * taps, int64_t nskip, int64_t offset,
+                            const double * d_in, int64_t n_in_rows, int64_t in_stride, const int32_t * in_row,
+                            int mod_mode, const double * d_mod, int64_t n_mod_rows, int64_t mod_stride,
+                            const int32_t * mod_row, const int32_t * mod_comp, int64_t nnz, int64_t comp_q,
+                            double * d_out, int64_t n_out_rows, int64_t out_stride, const int32_t * out_row,
+                            void * stream);
+/* _demodulate_flag [ref: demodulation.py:700-705]: row out_row[e] of d_out = row in_row[e] of d_in with demod_flag_mask
+ * raised in the first and the last wkernel samples (all of them when n <= wkernel), then [offset % nskip :: nskip]. */
+int toast_hip_demod_flags_dev(int64_t n_entry, int64_t n, int64_t wkernel, uint8_t demod_flag_mask, int64_t nskip,
+                              int64_t offset, const uint8_t * d_in, int64_t n_in_rows, int64_t in_stride,
+                              const int32_t * in_row, uint8_t * d_out, int64_t n_out_rows, int64_t out_stride,
+                              const int32_t * out_row, void * stream);
+/* The weights of demodulated pseudo-detectors [ref: demodulation.py:1060-1114]: d_weights[out_row[e]][s][:] =
+ * values[e][:] (host, [n_entry][nnz]) for all n_samp samples; d_weights is float64, or float32 with single_precision. */
+int toast_hip_stokes_weights_demod_dev(int64_t n_entry, int64_t n_samp, int64_t nnz, const double * values,
+                                       const int32_t * out_row, void * d_weights, int64_t n_weight_rows,
+                                       int single_precision, void * stream);
+/* Timing switch (bench tool): with on != 0 the entries above time themselves with events and synchronise; phase_ms (may
+ * be NULL) receives the sums since the last call of this switch [ms]: plain FIR, modulated FIR, flags, weights. */
+int toast_hip_demod_timing(int on, double * phase_ms);
+
+/* ------------------------------------------------------------------------------------
  * Deterministic debug mode (TOAST_HIP_DETERMINISTIC=1 in the environment, or this switch).
  * The production A^T kernels add run-reduced partial sums with fp64 atomics, so zmap / the
  * inverse covariance differ from run to run in the last bits.  With the mode on,

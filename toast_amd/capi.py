@@ -31,6 +31,10 @@ interval_dtype = np.dtype(
 )
 
 MAP_F64, MAP_F32, MAP_I64, MAP_I32 = 0, 1, 2, 3
+#: modulation of toast_hip_demod_fir_dev: none, from Stokes weights, an explicit array
+DEMOD_MOD_NONE, DEMOD_MOD_WEIGHTS, DEMOD_MOD_ARRAY = 0, 1, 2
+#: TOAST_HIP_DEMOD_TAP_CHUNK: taps of one decimation phase that the FIR kernel stages at a time
+DEMOD_TAP_CHUNK = 512
 _MAP_CODES = {
     np.dtype(np.float64): MAP_F64,
     np.dtype(np.float32): MAP_F32,
@@ -1812,6 +1816,53 @@ class _Dev:
         download) [ms] summed since the last call of this switch (toast_hip_noise_estim_timing)."""
         ms = (C.c_double * 4)()
         _check(real_lib().toast_hip_noise_estim_timing(C.c_int(1 if on else 0), ms))
+        return tuple(float(x) for x in ms)
+
+    # ---- half-wave-plate demodulation (csrc/demod.hip)
+    def demod_fir(self, n, taps, nskip, offset, d_in, n_in_rows, in_stride, in_row, d_out, n_out_rows, out_stride,
+                  out_row, mod_mode=DEMOD_MOD_NONE, d_mod=0, n_mod_rows=0, mod_stride=0, mod_row=None, mod_comp=None,
+                  nnz=0, comp_q=0, stream=0):
+        """``fftconvolve(m * x, taps, "same")[offset % nskip :: nskip]`` in direct form for a batch of entries: x = row
+        ``in_row[e]`` of ``d_in``, the result goes to row ``out_row[e]`` of ``d_out``; m by ``mod_mode`` (DEMOD_MOD_*).
+        toast_hip_demod_fir_dev."""
+        h = self._small(taps, np.float64).reshape(-1)
+        ri, ro = self._small(in_row, np.int32), self._small(out_row, np.int32)
+        rm = None if mod_row is None else self._small(mod_row, np.int32)
+        rc = None if mod_comp is None else self._small(mod_comp, np.int32)
+        if ro.size != ri.size or (rm is not None and rm.size != ri.size) or (rc is not None and rc.size != ri.size):
+            raise RuntimeError("demod_fir: one input, modulation and output row per entry")
+        _check(lib().toast_hip_demod_fir_dev(
+            _i64(ri.size), _i64(n), _i64(h.size), _p(h), _i64(nskip), _i64(offset), _p(d_in), _i64(n_in_rows),
+            _i64(in_stride), _p(ri), C.c_int(int(mod_mode)), _p(d_mod or None), _i64(n_mod_rows), _i64(mod_stride), _p(rm),
+            _p(rc), _i64(nnz), _i64(comp_q), _p(d_out), _i64(n_out_rows), _i64(out_stride), _p(ro), _p(stream)))
+
+    def demod_flags(self, n, wkernel, demod_flag_mask, nskip, offset, d_in, n_in_rows, in_stride, in_row, d_out,
+                    n_out_rows, out_stride, out_row, stream=0):
+        """Flags with ``demod_flag_mask`` raised in the first and last ``wkernel`` samples, decimated
+        ``[offset % nskip :: nskip]``.  toast_hip_demod_flags_dev."""
+        ri, ro = self._small(in_row, np.int32), self._small(out_row, np.int32)
+        if ro.size != ri.size:
+            raise RuntimeError("demod_flags: one input and one output row per entry")
+        _check(lib().toast_hip_demod_flags_dev(
+            _i64(ri.size), _i64(n), _i64(wkernel), C.c_uint8(int(demod_flag_mask) & 255), _i64(nskip), _i64(offset),
+            _p(d_in), _i64(n_in_rows), _i64(in_stride), _p(ri), _p(d_out), _i64(n_out_rows), _i64(out_stride), _p(ro),
+            _p(stream)))
+
+    def stokes_weights_demod(self, n_samp, values, out_row, d_weights, n_weight_rows, single_precision=False, stream=0):
+        """``d_weights[out_row[e]][s][:] = values[e][:]`` for every sample.  toast_hip_stokes_weights_demod_dev."""
+        v = self._small(values, np.float64)
+        ro = self._small(out_row, np.int32)
+        if v.ndim != 2 or v.shape[0] != ro.size:
+            raise RuntimeError("stokes_weights_demod: one row of weights per entry")
+        _check(lib().toast_hip_stokes_weights_demod_dev(
+            _i64(ro.size), _i64(n_samp), _i64(v.shape[1]), _p(v), _p(ro), _p(d_weights), _i64(n_weight_rows),
+            C.c_int(1 if single_precision else 0), _p(stream)))
+
+    def demod_timing(self, on):
+        """Switch the timing of the demodulation entries on / off; returns (plain FIR, modulated FIR, flags, weights)
+        [ms] summed since the last call of this switch (toast_hip_demod_timing)."""
+        ms = (C.c_double * 4)()
+        _check(real_lib().toast_hip_demod_timing(C.c_int(1 if on else 0), ms))
         return tuple(float(x) for x in ms)
 
     def test_math(self, op, n, d_a, d_b, d_out, stream=0):

@@ -1060,4 +1060,55 @@ PYBIND11_MODULE(_libtoast_hip, m) {
         if (ss[0] != lagmax || sh[0] != lagmax) throw std::runtime_error("Buffer sizes are not consistent.");
         check(toast_hip_fod_autosums(sx[0], rx, rg, lagmax, rs, rh, all_sums));
     }, py::arg("x"), py::arg("good"), py::arg("lagmax"), py::arg("sums"), py::arg("hits"), py::arg("all_sums"));
+
+    // ---- half-wave-plate demodulation (csrc/demod.hip): the large arrays are device addresses (accel_device_ptr), the
+    // per-entry tables and the taps NumPy arrays
+    m.def("demod_fir", [](int64_t n, py::buffer taps, int64_t nskip, int64_t offset, uintptr_t d_in, int64_t n_in_rows,
+                          int64_t in_stride, py::buffer in_row, int mod_mode, uintptr_t d_mod, int64_t n_mod_rows,
+                          int64_t mod_stride, py::buffer mod_row, py::buffer mod_comp, int64_t nnz, int64_t comp_q,
+                          uintptr_t d_out, int64_t n_out_rows, int64_t out_stride, py::buffer out_row) {
+        Shape st, si, sm, sc, so;
+        const double * h = extract<double>(taps, "taps", 1, st, {-1});
+        const int32_t * ri = extract<int32_t>(in_row, "in_row", 1, si, {-1});
+        const int32_t * rm = extract<int32_t>(mod_row, "mod_row", 1, sm, {-1});
+        const int32_t * rc = extract<int32_t>(mod_comp, "mod_comp", 1, sc, {-1});
+        const int32_t * ro = extract<int32_t>(out_row, "out_row", 1, so, {-1});
+        // the modulation tables only where the mode reads them (empty arrays otherwise)
+        const bool need_rows = mod_mode != TOAST_HIP_DEMOD_MOD_NONE, need_comp = mod_mode == TOAST_HIP_DEMOD_MOD_WEIGHTS;
+        if (so[0] != si[0] || (need_rows && sm[0] != si[0]) || (need_comp && sc[0] != si[0])) {
+            throw std::runtime_error("Buffer sizes are not consistent.");
+        }
+        if (!need_rows) rm = nullptr;
+        if (!need_comp) rc = nullptr;
+        check(toast_hip_demod_fir_dev(si[0], n, st[0], h, nskip, offset, reinterpret_cast<const double *>(d_in), n_in_rows,
+                                      in_stride, ri, mod_mode, reinterpret_cast<const double *>(d_mod), n_mod_rows,
+                                      mod_stride, rm, rc, nnz, comp_q, reinterpret_cast<double *>(d_out), n_out_rows,
+                                      out_stride, ro, nullptr));
+    }, py::arg("n"), py::arg("taps"), py::arg("nskip"), py::arg("offset"), py::arg("d_in"), py::arg("n_in_rows"),
+       py::arg("in_stride"), py::arg("in_row"), py::arg("mod_mode"), py::arg("d_mod"), py::arg("n_mod_rows"),
+       py::arg("mod_stride"), py::arg("mod_row"), py::arg("mod_comp"), py::arg("nnz"), py::arg("comp_q"), py::arg("d_out"),
+       py::arg("n_out_rows"), py::arg("out_stride"), py::arg("out_row"));
+    m.def("demod_flags", [](int64_t n, int64_t wkernel, int demod_flag_mask, int64_t nskip, int64_t offset, uintptr_t d_in,
+                            int64_t n_in_rows, int64_t in_stride, py::buffer in_row, uintptr_t d_out, int64_t n_out_rows,
+                            int64_t out_stride, py::buffer out_row) {
+        Shape si, so;
+        const int32_t * ri = extract<int32_t>(in_row, "in_row", 1, si, {-1});
+        const int32_t * ro = extract<int32_t>(out_row, "out_row", 1, so, {-1});
+        if (so[0] != si[0]) throw std::runtime_error("Buffer sizes are not consistent.");
+        check(toast_hip_demod_flags_dev(si[0], n, wkernel, (uint8_t)(demod_flag_mask & 255), nskip, offset,
+                                        reinterpret_cast<const uint8_t *>(d_in), n_in_rows, in_stride, ri,
+                                        reinterpret_cast<uint8_t *>(d_out), n_out_rows, out_stride, ro, nullptr));
+    }, py::arg("n"), py::arg("wkernel"), py::arg("demod_flag_mask"), py::arg("nskip"), py::arg("offset"), py::arg("d_in"),
+       py::arg("n_in_rows"), py::arg("in_stride"), py::arg("in_row"), py::arg("d_out"), py::arg("n_out_rows"),
+       py::arg("out_stride"), py::arg("out_row"));
+    m.def("stokes_weights_demod", [](int64_t n_samp, py::buffer values, py::buffer out_row, uintptr_t d_weights,
+                                     int64_t n_weight_rows, bool single_precision) {
+        Shape sv, so;
+        const double * v = extract<double>(values, "values", 2, sv, {-1, -1});
+        const int32_t * ro = extract<int32_t>(out_row, "out_row", 1, so, {-1});
+        if (sv[0] != so[0]) throw std::runtime_error("Buffer sizes are not consistent.");
+        check(toast_hip_stokes_weights_demod_dev(so[0], n_samp, sv[1], v, ro, reinterpret_cast<void *>(d_weights),
+                                                 n_weight_rows, single_precision ? 1 : 0, nullptr));
+    }, py::arg("n_samp"), py::arg("values"), py::arg("out_row"), py::arg("d_weights"), py::arg("n_weight_rows"),
+       py::arg("single_precision"));
 }

@@ -16,6 +16,7 @@ from .mapmaker_ops import (
     ScanMask,
 )
 from .mapmaker_solve import SolverLHS, SolverRHS, TemplateMatrix, solve
+from .demodulation import Demodulate, StokesWeightsDemod
 from .ground_filter import GroundFilter
 from .noise_estimation import NoiseEstim
 from .noise_filter import NoiseFilter
