@@ -1,0 +1,319 @@
+"""GPU: the map-domain kernels at every Stokes count (nnz = 1 "I", 2 "QU", 3 "IQU", 4) and launch variant -- detector
+pairs on / off, two samples per lane on / off, the detector-major grid -- against the extended-precision references and
+the derived rounding bounds of tests/nnz_reference.py (which tests/test_nnz_reference_host.py holds the CPU oracle to).
+The bounds are per map element / per sample, not "1e-12 of the largest value": one dropped sample of a faint pixel is far
+outside them.  Kernel instantiations and the tests that launch them:
+
+  k_scan_map<T, 1 | 0 | 3>, k_scan_map_v2<T>, both grids      test_scan_map (nnz 1 | 2, 4 | 3)
+  k_build_noise_weighted_pair<1 | 3>, _v2<1 | 2>              test_build_noise_weighted (pair on)
+  k_build_noise_weighted<1 | 2 | 3>, both grids; _any         test_build_noise_weighted (pair off / det_major; nnz 4)
+  k_build_cov<1 | 2 | 3, 1>, k_build_cov<1, 0>, _pair*        test_inverse_covariance_and_hits
+  k_offset_accumulate<1 | 3, 1 | 2>, k_offset_scan_project<1 | 3, false | true>, their _v2 and on-the-fly forms
+                                                              test_fused_halves"""
+import numpy as np
+import pytest
+
+import nnz_reference as R
+
+pytestmark = pytest.mark.gpu
+
+STEP = 37
+
+
+@pytest.fixture(scope="module")
+def hip():
+    from toast_amd import capi
+
+    assert capi.accel_enabled(), "no HIP device visible"
+    capi.accel_assign_device(1, 0, 1.0, False)
+    yield capi
+    capi.set_tuning("pair", 1)
+    capi.set_tuning("vec2", 1)
+    capi.set_tuning("det_major", 0)
+
+
+def tune(hip, pair=1, vec2=1, det_major=0):
+    hip.set_tuning("pair", pair)
+    hip.set_tuning("vec2", vec2)
+    hip.set_tuning("det_major", det_major)
+
+
+# ------------------------------------------------------------------------------------------ build_noise_weighted
+def bnw_args(c, pt, w):
+    return (c["pixel_index"], pt["pixels"], c["weight_index"], w, c["data_index"], c["tod"], c["flag_index"],
+            c["det_flags"], c["det_scale"], 1, c["intervals"], c["shared_flags"], 1, False)
+
+
+@pytest.mark.parametrize("nnz", R.NNZ)
+@pytest.mark.parametrize("name", list(R.CASES))
+def test_build_noise_weighted(hip, oracle, name, nnz):
+    c, pt = R.pointing(oracle, name)
+    w = R.weights_nnz(pt["weights"], nnz)
+    zmap0 = R.seeded_map((pt["n_local"], c["n_pix_submap"], nnz), np.float64, seed=5)   # the kernel accumulates
+    ref = R.build_noise_weighted(c, pt, w, nnz, zmap0)
+    for pair in (1, 0):
+        for det_major in (0, 1):
+            tune(hip, pair=pair, det_major=det_major)
+            z = zmap0.copy()
+            hip.build_noise_weighted(pt["g2l"], z, *bnw_args(c, pt, w))
+            worst = ref.excess(z)
+            print(f"build_noise_weighted {name} nnz={nnz} pair={pair} det_major={det_major}: {worst:.3g} of the bound")
+            assert worst <= 1.0, (pair, det_major)
+
+
+@pytest.mark.parametrize("nnz", R.NNZ)
+def test_build_noise_weighted_pybind(hip, oracle, nnz):
+    from toast_amd.accel import native
+
+    tune(hip)
+    c, pt = R.pointing(oracle, "broken_pairs_indirect")
+    w = R.weights_nnz(pt["weights"], nnz)
+    zmap0 = R.seeded_map((pt["n_local"], c["n_pix_submap"], nnz), np.float64, seed=5)
+    z = zmap0.copy()
+    native().build_noise_weighted(pt["g2l"], z, *bnw_args(c, pt, w))
+    assert R.build_noise_weighted(c, pt, w, nnz, zmap0).excess(z) <= 1.0
+
+
+# ------------------------------------------------------------------------------------------ scan_map
+def scan(hip, dtype, c, pt, g2l, w, m, tod, scale, mode):
+    fn = getattr(hip, {"f64": "ops_scan_map_float64", "f32": "ops_scan_map_float32", "i64": "ops_scan_map_int64",
+                       "i32": "ops_scan_map_int32"}[dtype])
+    fn(g2l, c["n_pix_submap"], m, tod, c["data_index"], pt["pixels"], c["pixel_index"], w, c["weight_index"],
+       c["intervals"], scale, *R.SCAN_MODES[mode], False)
+
+
+@pytest.mark.parametrize("dtype", list(R.MAP_DTYPES))
+@pytest.mark.parametrize("nnz", R.NNZ)
+@pytest.mark.parametrize("name", list(R.CASES))
+def test_scan_map(hip, oracle, name, nnz, dtype):
+    """Every mode against the per-sample bound (samples outside the views and rows outside the call: untouched, the
+    reference's magnitude is 0 there), and the same bits from every launch variant: the arithmetic is per sample."""
+    c, pt = R.pointing(oracle, name)
+    w = R.weights_nnz(pt["weights"], nnz)
+    m = R.seeded_map((pt["n_local"], c["n_pix_submap"], nnz), R.MAP_DTYPES[dtype])
+    for mode, (zero, sub, mult) in R.SCAN_MODES.items():
+        ref = R.scan_map(c, pt, w, nnz, m, c["tod"], 0.37, zero, sub, mult)
+        outs = {}
+        for variant in (dict(), dict(det_major=1), dict(vec2=0), dict(pair=0), dict(vec2=0, det_major=1)):
+            tune(hip, **variant)
+            t = c["tod"].copy()
+            scan(hip, dtype, c, pt, pt["g2l"], w, m, t, 0.37, mode)
+            outs[tuple(sorted(variant.items()))] = t
+        for variant, t in outs.items():
+            worst = R.scan_excess(t, ref, nnz)
+            print(f"scan_map {name} nnz={nnz} {dtype} {mode} {dict(variant)}: {worst:.3g} of the bound")
+            assert worst <= 1.0, (mode, variant)
+            assert np.array_equal(t, outs[()]), (mode, variant)
+
+
+@pytest.mark.parametrize("nnz", R.NNZ)
+def test_scan_map_leaves_non_local_submaps_alone(hip, oracle, nnz):
+    """global2local = -1 for a submap that samples do point at: they are left alone, in both grids."""
+    c, pt = R.pointing(oracle, "odd_dets_odd_starts")
+    w = R.weights_nnz(pt["weights"], nnz)
+    m = R.seeded_map((pt["n_local"], c["n_pix_submap"], nnz), np.float64)
+    g2l = pt["g2l"].copy()
+    victim = int(np.flatnonzero(g2l >= 0)[1])
+    g2l[victim] = -1
+    pt2 = dict(pt, g2l=g2l)
+    ref = R.scan_map(c, pt2, w, nnz, m, c["tod"], 0.37, False, True, False)
+    inside = np.zeros(c["tod"].shape, dtype=bool)
+    s = R.view_samples(c)
+    for d in range(c["n_det"]):
+        inside[c["data_index"][d], s] = pt["pixels"][c["pixel_index"][d]][s] // c["n_pix_submap"] == victim
+    assert inside.any()
+    for det_major in (0, 1):
+        for vec2 in (1, 0):
+            tune(hip, vec2=vec2, det_major=det_major)
+            t = c["tod"].copy()
+            scan(hip, "f64", c, pt, g2l, w, m, t, 0.37, "subtract")
+            assert R.scan_excess(t, ref, nnz) <= 1.0
+            assert np.array_equal(t[inside], c["tod"][inside])
+            assert not np.array_equal(t, c["tod"])
+
+
+# ------------------------------------------------------------------------------------------ inverse covariance, hits
+@pytest.mark.parametrize("nnz", (1, 2, 3))
+@pytest.mark.parametrize("name", list(R.CASES))
+def test_inverse_covariance_and_hits(hip, oracle, name, nnz):
+    from toast_amd.accel import native
+
+    nat = native()
+    c, pt = R.pointing(oracle, name)
+    w = R.weights_nnz(pt["weights"], nnz)
+    blk = nnz * (nnz + 1) // 2
+    shape = (pt["n_local"], c["n_pix_submap"])
+    cov0 = R.seeded_map(shape + (blk,), np.float64, seed=6)
+    hits0 = np.random.default_rng(7).integers(0, 9, shape + (1,)).astype(np.int64)
+    ref = R.inverse_covariance(c, pt, w, nnz, cov0)
+    want_hits = hits0.reshape(-1) + ref.counts()
+    flags = (c["flag_index"], c["det_flags"], c["det_scale"], 1, c["intervals"], c["shared_flags"], 1)
+    for pair in (1, 0):
+        for vec2 in (1, 0):
+            tune(hip, pair=pair, vec2=vec2)
+            cov, hits = cov0.copy(), hits0.copy()
+            nat.build_hit_map(pt["g2l"], hits, c["pixel_index"], pt["pixels"], flags[0], flags[1], 1, flags[4], flags[5], 1,
+                              False)
+            nat.build_inverse_covariance(pt["g2l"], cov, c["pixel_index"], pt["pixels"], c["weight_index"], w, *flags, False)
+            assert np.array_equal(hits.reshape(-1), want_hits), (pair, vec2)
+            worst = ref.excess(cov)
+            print(f"inverse covariance {name} nnz={nnz} pair={pair} vec2={vec2} separate: {worst:.3g} of the bound")
+            assert worst <= 1.0, (pair, vec2)
+            cov, hits = cov0.copy(), hits0.copy()
+            nat.build_inverse_covariance_and_hits(pt["g2l"], cov, hits, c["pixel_index"], pt["pixels"], c["weight_index"], w,
+                                                  *flags, False)
+            assert np.array_equal(hits.reshape(-1), want_hits), (pair, vec2)
+            worst = ref.excess(cov)
+            print(f"inverse covariance {name} nnz={nnz} pair={pair} vec2={vec2} combined: {worst:.3g} of the bound")
+            assert worst <= 1.0, (pair, vec2)
+
+
+# ------------------------------------------------------------------------------------------ fused PCG halves
+def dev(torch, a):
+    return torch.from_numpy(np.array(a)).cuda()
+
+
+def fused_setup(torch, hip, c, pt, nnz, otf):
+    """Device buffers of one fused call and the pointing the reference has to use: the oracle's cached pixels / weights, or
+    -- on the fly -- what the library's own expansion of the same descriptor gives (pixels are the oracle's bit for bit,
+    IQU weights agree with it to 1e-12 only, and the bounds here are tighter than that)."""
+    n_samp = c["n_samp"]
+    s = dict(g2l=dev(torch, pt["g2l"]), dfl=dev(torch, c["det_flags"]), sfl=dev(torch, c["shared_flags"]))
+    s["n_flag"] = n_samp if c["det_flags"].shape[1] == n_samp else 0
+    if not otf:
+        w = R.weights_nnz(pt["weights"], nnz)
+        s.update(pix=dev(torch, pt["pixels"]), wts=dev(torch, w))
+        return s, pt, w
+    s.update(bore=dev(torch, c["boresight"]), hwp=dev(torch, c["hwp"]))
+    desc = hip.otf_pointing(s["bore"].data_ptr(), c["focalplane"], c["nside"], True, nnz, d_shared_flags=s["sfl"].data_ptr(),
+                            n_shared_flags=c["shared_flags"].size, shared_flag_mask=1, d_hwp=s["hwp"].data_ptr(),
+                            n_hwp=c["hwp"].size, epsilon=c["epsilon"], gamma=c["gamma"], cal=c["cal"], IAU=False)
+    s["pt"] = desc
+    pix = torch.full((c["rows"], n_samp), -7, dtype=torch.int64, device="cuda")
+    hsub = torch.zeros(c["n_submap"], dtype=torch.uint8, device="cuda")
+    wts = torch.zeros((c["rows"], n_samp) + ((3,) if nnz == 3 else ()), dtype=torch.float64, device="cuda")
+    hip.dev.otf_pixels_healpix(desc, c["pixel_index"], pix.data_ptr(), n_samp, c["intervals"], hsub.data_ptr(),
+                               c["n_submap"], c["n_pix_submap"])
+    hip.dev.otf_stokes_weights(desc, c["weight_index"], wts.data_ptr(), n_samp, c["intervals"])
+    torch.cuda.synchronize()
+    pixels = pix.cpu().numpy()
+    assert np.array_equal(pixels, pt["pixels"])
+    return s, pt, wts.cpu().numpy()
+
+
+def fused_accumulate(hip, s, c, nnz, otf, lay, d_amps, d_afl, d_z):
+    n_amp_views, amp_offsets, _ = lay
+    n_samp = c["n_samp"]
+    if otf:
+        hip.dev.otf_offset_accumulate(s["pt"], STEP, amp_offsets, n_amp_views, d_amps.data_ptr(), d_afl.data_ptr(),
+                                      s["g2l"].data_ptr(), d_z.data_ptr(), c["n_pix_submap"], c["flag_index"],
+                                      s["dfl"].data_ptr(), s["n_flag"], c["det_scale"], 1, n_samp, c["intervals"],
+                                      s["sfl"].data_ptr(), c["shared_flags"].size, 1)
+    else:
+        hip.dev.offset_accumulate(STEP, amp_offsets, n_amp_views, d_amps.data_ptr(), d_afl.data_ptr(), s["g2l"].data_ptr(),
+                                  d_z.data_ptr(), c["n_pix_submap"], nnz, c["pixel_index"], s["pix"].data_ptr(),
+                                  c["weight_index"], s["wts"].data_ptr(), c["flag_index"], s["dfl"].data_ptr(), s["n_flag"],
+                                  c["det_scale"], 1, n_samp, c["intervals"], s["sfl"].data_ptr(), c["shared_flags"].size, 1)
+
+
+def fused_scan_project(hip, s, c, nnz, otf, lay, d_amps, d_afl, d_out, d_map):
+    n_amp_views, amp_offsets, _ = lay
+    n_samp = c["n_samp"]
+    if otf:
+        hip.dev.otf_offset_scan_project(s["pt"], STEP, amp_offsets, n_amp_views, d_amps.data_ptr(), d_out.data_ptr(),
+                                        d_afl.data_ptr(), s["g2l"].data_ptr(), d_map.data_ptr(), c["n_pix_submap"],
+                                        c["flag_index"], s["dfl"].data_ptr(), s["n_flag"], 4, c["det_scale"], n_samp,
+                                        c["intervals"])
+    else:
+        hip.dev.offset_scan_project(STEP, amp_offsets, n_amp_views, d_amps.data_ptr(), d_out.data_ptr(), d_afl.data_ptr(),
+                                    s["g2l"].data_ptr(), d_map.data_ptr(), c["n_pix_submap"], nnz, c["pixel_index"],
+                                    s["pix"].data_ptr(), c["weight_index"], s["wts"].data_ptr(), c["flag_index"],
+                                    s["dfl"].data_ptr(), 4, c["det_scale"], n_samp, c["intervals"])
+
+
+def fused_scan_project_signal(hip, s, c, nnz, otf, lay, d_sig, d_afl, d_out, d_map):
+    n_amp_views, amp_offsets, _ = lay
+    n_samp = c["n_samp"]
+    if otf:
+        hip.dev.otf_offset_scan_project_signal(s["pt"], STEP, amp_offsets, n_amp_views, c["data_index"], d_sig.data_ptr(),
+                                               d_out.data_ptr(), d_afl.data_ptr(), s["g2l"].data_ptr(), d_map.data_ptr(),
+                                               c["n_pix_submap"], c["flag_index"], s["dfl"].data_ptr(), s["n_flag"], 4,
+                                               c["det_scale"], n_samp, c["intervals"])
+    else:
+        hip.dev.offset_scan_project_signal(STEP, amp_offsets, n_amp_views, c["data_index"], d_sig.data_ptr(), d_out.data_ptr(),
+                                           d_afl.data_ptr(), s["g2l"].data_ptr(), d_map.data_ptr(), c["n_pix_submap"], nnz,
+                                           c["pixel_index"], s["pix"].data_ptr(), c["weight_index"], s["wts"].data_ptr(),
+                                           c["flag_index"], s["dfl"].data_ptr(), 4, c["det_scale"], n_samp, c["intervals"])
+
+
+FUSED_CASES = ["odd_dets_odd_starts", "single_det", "odd_n_samp"]
+
+
+@pytest.mark.parametrize("otf", [False, True], ids=["cached", "on_the_fly"])
+@pytest.mark.parametrize("nnz", (1, 3))
+@pytest.mark.parametrize("name", FUSED_CASES)
+def test_fused_halves(hip, oracle, name, nnz, otf):
+    """offset_accumulate, zmap += A^T N^-1 M a, offset_scan_project, out += M^T N^-1 (M a - A z), and its right-hand-side
+    form on a timestream, out += M^T N^-1 (d - A z), with baselines of 37 samples, the first amplitude at offset 5, flagged
+    amplitudes, a map and amplitudes that hold something already."""
+    import torch
+
+    c, pt = R.pointing(oracle, name)
+    tune(hip)
+    s, pt, w = fused_setup(torch, hip, c, pt, nnz, otf)
+    lay = R.offset_layout(c, STEP)
+    n_amp_views, amp_offsets, n_amp = lay
+    rng = np.random.default_rng(8)
+    amps = rng.standard_normal(n_amp)
+    aflags = (rng.random(n_amp) < 0.05).astype(np.uint8)
+    out0 = rng.standard_normal(n_amp)
+    zmap0 = R.seeded_map((pt["n_local"], c["n_pix_submap"], nnz), np.float64, seed=5)
+    m = R.seeded_map(zmap0.shape, np.float64, seed=9)
+    ref_z = R.offset_accumulate(c, pt, w, nnz, zmap0, STEP, n_amp_views, amp_offsets, amps, aflags)
+    ref_a = R.offset_scan_project(c, pt, w, nnz, m, STEP, n_amp_views, amp_offsets, amps, aflags, out0, c["det_scale"], 4)
+    ref_s = R.offset_scan_project(c, pt, w, nnz, m, STEP, n_amp_views, amp_offsets, amps, aflags, out0, c["det_scale"], 4,
+                                  signal=c["tod"])
+    assert ref_z.n.sum() > 0 and ref_a.n.sum() > 0 and ref_s.n.sum() > 0
+    d_amps, d_afl, d_map, d_sig = dev(torch, amps), dev(torch, aflags), dev(torch, m), dev(torch, c["tod"])
+    for pair in (1, 0):
+        for vec2 in (1, 0):
+            tune(hip, pair=pair, vec2=vec2)
+            d_z, d_out = dev(torch, zmap0), dev(torch, out0)
+            fused_accumulate(hip, s, c, nnz, otf, lay, d_amps, d_afl, d_z)
+            fused_scan_project(hip, s, c, nnz, otf, lay, d_amps, d_afl, d_out, d_map)
+            d_rhs = dev(torch, out0)
+            fused_scan_project_signal(hip, s, c, nnz, otf, lay, d_sig, d_afl, d_rhs, d_map)
+            torch.cuda.synchronize()
+            z, out, rhs = d_z.cpu().numpy(), d_out.cpu().numpy(), d_rhs.cpu().numpy()
+            wz, wa, ws = ref_z.excess(z), ref_a.excess(out, extra=nnz + 2), ref_s.excess(rhs, extra=nnz + 2)
+            print(f"fused {name} nnz={nnz} otf={otf} pair={pair} vec2={vec2}: accumulate {wz:.3g}, scan_project {wa:.3g}, "
+                  f"scan_project_signal {ws:.3g} of the bound")
+            assert wz <= 1.0 and wa <= 1.0 and ws <= 1.0, (pair, vec2)
+            assert np.array_equal(d_sig.cpu().numpy(), c["tod"])      # the signal is read only
+
+
+@pytest.mark.parametrize("otf", [False, True], ids=["cached", "on_the_fly"])
+def test_fused_halves_refuse_two_components(hip, oracle, otf):
+    """nnz = 2 has no fused kernel: the calls raise and nothing is written."""
+    import torch
+
+    c, pt = R.pointing(oracle, "odd_dets_odd_starts")
+    tune(hip)
+    s, _, _ = fused_setup(torch, hip, c, pt, 1, otf)
+    if otf:
+        s["pt"].nnz = 2
+    else:
+        s["wts"] = dev(torch, R.weights_nnz(pt["weights"], 2))
+    lay = R.offset_layout(c, STEP)
+    rng = np.random.default_rng(8)
+    amps, out0 = rng.standard_normal(lay[2]), rng.standard_normal(lay[2])
+    zmap0 = R.seeded_map((pt["n_local"], c["n_pix_submap"], 2), np.float64, seed=5)
+    d_amps, d_afl = dev(torch, amps), dev(torch, np.zeros(lay[2], dtype=np.uint8))
+    d_z, d_out = dev(torch, zmap0), dev(torch, out0)
+    message = "nnz must be 1" if otf else "nnz must be 1 or 3"
+    with pytest.raises(RuntimeError, match=message):
+        fused_accumulate(hip, s, c, 2, otf, lay, d_amps, d_afl, d_z)
+    with pytest.raises(RuntimeError, match=message):
+        fused_scan_project(hip, s, c, 2, otf, lay, d_amps, d_afl, d_out, d_z)
+    torch.cuda.synchronize()
+    assert np.array_equal(d_z.cpu().numpy(), zmap0) and np.array_equal(d_out.cpu().numpy(), out0)

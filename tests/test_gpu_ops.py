@@ -210,20 +210,21 @@ def test_scan_map_operator():
     assert np.all(ob.detdata[defaults.det_data].data == 0)
 
 
-def make_solver_setup(n_det=4, n_samp=6000, step_time=20.0, seed=11, noise_rms=0.0):
+def make_solver_setup(n_det=4, n_samp=6000, step_time=20.0, seed=11, noise_rms=0.0, mode="IQU"):
     data = create_satellite_data(n_det=n_det, n_samp=n_samp, rate=10.0, spin_angle_deg=25.0, prec_angle_deg=35.0)
-    dp, pix, sw = pointing_ops(nside=16, create_dist=None)
+    dp, pix, sw = pointing_ops(nside=16, mode=mode, create_dist=None)
     pix.nside_submap = 4
     rng = np.random.default_rng(seed)
     # sky signal + per-detector baseline offsets
     ops.Pipeline(operators=[pix, sw]).apply(data)
     ob = data.obs[0]
     sky = rng.standard_normal((12 * 16 * 16, 3)) * np.array([1.0, 0.1, 0.1])
+    sky = sky[:, {"I": [0], "QU": [1, 2], "IQU": [0, 1, 2]}[mode]]   # (the same draws whatever the mode)
     truth = {}
     step = int(step_time * 10.0 + 0.5)
     for det in ob.local_detectors:
         p = ob.detdata[defaults.pixels][det]
-        w = ob.detdata[defaults.weights][det]
+        w = ob.detdata[defaults.weights][det].reshape(n_samp, len(mode))
         good = p >= 0
         sig = np.zeros(n_samp)
         sig[good] = np.einsum("ij,ij->i", w[good], sky[p[good]])
@@ -239,10 +240,12 @@ def make_solver_setup(n_det=4, n_samp=6000, step_time=20.0, seed=11, noise_rms=0
     return data, pix, sw, truth, sky
 
 
+@pytest.mark.parametrize("mode", ["I", "QU", "IQU"])
 @pytest.mark.parametrize("full_pointing", [True, False])
-def test_lhs_equals_rhs_of_projected_amplitudes(full_pointing):
-    """LHS(a) == RHS(M a) without a prior (reference test_lhs, tests/ops_mapmaker_solve.py:151-265)."""
-    data, pix, sw, truth, sky = make_solver_setup()
+def test_lhs_equals_rhs_of_projected_amplitudes(full_pointing, mode):
+    """LHS(a) == RHS(M a) without a prior (reference test_lhs, tests/ops_mapmaker_solve.py:151-265), for every Stokes
+    mode: I and IQU through the fused kernels (cached or on-the-fly pointing), QU through the operator sequence."""
+    data, pix, sw, truth, sky = make_solver_setup(mode=mode)
     ops.CovarianceAndHits(pixel_dist="dist", covariance="cov", pixel_pointing=pix, stokes_weights=sw,
                           save_pointing=full_pointing).apply(data)
     binner = ops.BinMap(pixel_dist="dist", covariance="cov", binned="solve_bin", pixel_pointing=pix,
@@ -271,7 +274,12 @@ def test_lhs_equals_rhs_of_projected_amplitudes(full_pointing):
     tm_lhs.amplitudes = "amps_in"
     data["lhs_out"] = data["amps_in"].duplicate()
     data["lhs_out"].reset()
-    ops.SolverLHS(binning=lhs_bin, template_matrix=tm_lhs, out="lhs_out").apply(data)
+    lhs = ops.SolverLHS(binning=lhs_bin, template_matrix=tm_lhs, out="lhs_out")
+    lhs.apply(data)
+    # the route that ran: the operator sequence for QU; for I the fused kernels on the pointing as it is, for IQU those
+    # or the sweeps of the packed pointing cache
+    fused = {"fused" if full_pointing else "fused-otf"} | ({"packed"} if mode == "IQU" else set())
+    assert lhs.last_route and set(lhs.last_route) <= ({"sequence"} if mode == "QU" else fused), lhs.last_route
     a = data["rhs_out"]["baselines"].local
     b = data["lhs_out"]["baselines"].local
     assert np.max(np.abs(a)) > 0
@@ -758,6 +766,34 @@ def test_fused_lhs_equals_operator_sequence():
     a, b = results[False], results[True]
     assert np.max(np.abs(a)) > 0
     assert np.max(np.abs(a - b)) < 1e-11 * np.max(np.abs(a))
+
+
+@pytest.mark.parametrize("full_pointing", [True, False])
+def test_mapmaker_intensity_only_fused_equals_operator_sequence(full_pointing):
+    """MapMaker with StokesWeights(mode="I") and an Offset template: the fused left-hand side (k_offset_accumulate<1, *>,
+    k_offset_scan_project<1, *>; on the fly with full_pointing=False) against the operator sequence -- the same solve:
+    residual history, amplitudes and map at the tolerances of the IQU route comparison in test_gpu_packed, hits exactly."""
+    res = {}
+    for fused in (True, False):
+        data, pix, sw, truth, sky = make_solver_setup(noise_rms=0.1, mode="I")
+        binner = ops.BinMap(pixel_dist="dist", pixel_pointing=pix, stokes_weights=sw, full_pointing=full_pointing)
+        tmpl = Offset(step_time=20.0, noise_model=defaults.noise_model, name="baselines", good_fraction=0.2,
+                      precond_width=10)
+        mapper = ops.MapMaker(name="mm", keep_solver_products=True, det_data=defaults.det_data, binning=binner,
+                              template_matrix=ops.TemplateMatrix(templates=[tmpl]), solve_rcond_threshold=1e-3,
+                              map_rcond_threshold=1e-3, iter_max=12, convergence=1e-30, fused_lhs=fused)
+        lhs_probe = ops.SolverLHS(binning=binner, template_matrix=mapper.template_matrix, fused=fused)
+        assert lhs_probe._can_fuse(data) == fused
+        mapper.apply(data)
+        assert data["mm_map"].data.shape[-1] == 1
+        res[fused] = (np.array(mapper.history), data["mm_solve_amplitudes"]["baselines"].local.copy(),
+                      data["mm_map"].data.copy(), data["mm_hits"].data.copy())
+    (h1, a1, m1, n1), (h0, a0, m0, n0) = res[True], res[False]
+    assert len(h1) == len(h0) and len(h1) > 1
+    np.testing.assert_allclose(h1, h0, rtol=1e-7)
+    assert np.max(np.abs(a0)) > 0 and np.max(np.abs(a1 - a0)) < 1e-9 * np.max(np.abs(a0))
+    assert np.max(np.abs(m1 - m0)) < 1e-9 * np.max(np.abs(m0))
+    assert n0.sum() > 0 and np.array_equal(n1, n0)
 
 
 def test_amplitudes_device_algebra_matches_host():
