@@ -851,10 +851,14 @@ int toast_hip_template_subtract_dev(
  * reference kernel -- with good[i] = !(shared_flags[i] & shared_flag_mask) && !(det_flags[d][i] & det_flag_mask):
  *   ngood == 0 leaves the interval untouched; norder = min(ngood, order + 1); the Legendre templates of
  *   x_i = (0.5 dx - 1) + i dx, dx = 2 / scanlen (same recurrence) are fitted to the good samples by least squares
- *   (normal equations, Cholesky in fp64) and the fit is subtracted from ALL samples of the interval.
- * d_coeff [n_det][n_interval][order + 1] receives the coefficients (zero beyond norder), d_status
- * [n_det][n_interval] one of TOAST_HIP_POLY_*; both are required.  With TOAST_HIP_POLY_NOT_POSITIVE (a Cholesky
- * pivot was not positive) the signal is left untouched.  Nothing throws from the device.  order < 0 is a no-op;
+ *   and the fit is subtracted from ALL samples of the interval.  The solve: normal equations and Cholesky in fp64
+ *   while every pivot keeps at least 5 % of its diagonal entry (scattered flags); otherwise (good samples in a
+ *   contiguous stretch) the polynomials orthogonal on the good samples by their three-term recurrence, one
+ *   projection and one subtraction per term, which stays as close to the exact residual as an SVD solve.
+ * d_coeff [n_det][n_interval][order + 1] receives the Legendre coefficients (zero beyond norder) from either
+ * solve, d_status [n_det][n_interval] one of TOAST_HIP_POLY_*; both are required.  TOAST_HIP_POLY_NOT_FINITE: a
+ * good sample of the interval is NaN or infinite and the signal is left untouched; it does not occur for finite
+ * input.  Nothing throws from the device.  order < 0 is a no-op;
  * order + 1 > 16 is an error.  d_det_flags / d_shared_flags may be NULL.
  * path: 0 = by the rule -- an interval of at most toast_hip_filter_polynomial_stage_cap() samples is filtered by
  * one workgroup that stages it in LDS (one read and one write of the signal), a longer one in two passes (partial
@@ -874,7 +878,8 @@ int toast_hip_template_subtract_dev(
 #define TOAST_HIP_POLY_FITTED 0
 #define TOAST_HIP_POLY_NO_GOOD 1
 #define TOAST_HIP_POLY_REDUCED 2
-#define TOAST_HIP_POLY_NOT_POSITIVE 3
+#define TOAST_HIP_POLY_NOT_FINITE 3
+#define TOAST_HIP_POLY_NOT_POSITIVE TOAST_HIP_POLY_NOT_FINITE /* the name this value had while it also reported a failed Cholesky */
 int toast_hip_filter_polynomial_stage_cap(void);
 int toast_hip_filter_polynomial_dev(
     int64_t order, int64_t n_samp, const int32_t * signal_index /*host*/, double * d_signal,

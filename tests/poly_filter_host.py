@@ -5,7 +5,7 @@ subtracted from ALL samples.  The least-squares problem is solved by `numpy.lina
 reference's DGELSS.  Also the reference's `sum_detectors` / `subtract_mean` (src/toast/_libtoast/tod_filter.cpp:9-97)."""
 import numpy as np
 
-FITTED, NO_GOOD, REDUCED, NOT_POSITIVE = 0, 1, 2, 3
+FITTED, NO_GOOD, REDUCED, NOT_FINITE = 0, 1, 2, 3     # 3: a good sample is NaN or infinite, interval left untouched
 
 
 def legendre(scanlen, norder):
@@ -89,3 +89,22 @@ def poly_case_signals(seed, n_det, n_samp):
 
 def common_mode_signals(seed, n_rows, n_samp):
     return (hashed_uniform(seed, n_rows * n_samp).reshape(n_rows, n_samp) - 0.5) * 20.0
+
+
+# The operator-level case of the conditioning tests (tests/test_gpu_poly_filter_edges.py and the fixture generator
+# tests/golden/make_golden_poly_filter_edges.py build the same inputs from here).
+EDGE_OPERATOR_SIM = dict(n_det=3, n_samp=6000, rate=20.0, n_obs=1, flag_samples=False, seed=0)
+EDGE_OPERATOR_ORDER = 5
+EDGE_OPERATOR_DET = 1
+EDGE_OPERATOR_MASKS = (1, 1)        # shared_flag_mask (the sim's invalid bit), det_flag_mask
+
+
+def edge_operator_inputs(starts, stops, n_samp):
+    """(signal [3][n_samp], detector flags [3][n_samp]): detector EDGE_OPERATOR_DET keeps only the first 10 % of every
+    [start, stop) good, the others lose 10 % of their samples at random."""
+    signal = poly_case_signals(900, 3, n_samp)
+    det_flags = (hashed_uniform(901, 3 * n_samp).reshape(3, n_samp) < 0.1).astype(np.uint8)
+    det_flags[EDGE_OPERATOR_DET] = 0
+    for a, b in zip(starts, stops):
+        det_flags[EDGE_OPERATOR_DET, a + int(0.1 * (b - a)):b] = 1
+    return signal, det_flags

@@ -10,6 +10,7 @@ import pytest
 import poly_filter_host as H
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "poly_filter.npz")
+EDGES = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "poly_filter_edges.npz")
 TOL = 1e-12     # of max|input signal|: the bound of the device tests (tests/test_gpu_poly_filter.py)
 
 
@@ -17,6 +18,81 @@ TOL = 1e-12     # of max|input signal|: the bound of the device tests (tests/tes
 def golden():
     z = np.load(GOLDEN, allow_pickle=False)
     return {k: z[k] for k in z.files}
+
+
+@pytest.fixture(scope="module")
+def edges():
+    z = np.load(EDGES, allow_pickle=False)
+    return {k: z[k] for k in z.files}
+
+
+def edge_case(g, i):
+    """(order, signal of the interval, good mask, case dict) of case i of the conditioning fixture."""
+    c = {k[len(f"c{i}_"):]: g[k] for k in g if k.startswith(f"c{i}_")}
+    a, b = int(c["start"]), int(c["stop"])
+    signal = H.poly_case_signals(int(c["seed"]), 3, int(c["n_samp"]))[int(c["row"])]
+    flags = H.combined_flags(c["shared"], int(g["shared_mask"]), c["det"], int(g["det_mask"]))
+    return int(c["order"]), signal, flags, c
+
+
+def test_edges_fixture_classes(edges):
+    """The class conditions of tests/golden/make_golden_poly_filter_edges.py, from the committed file: the caps are
+    conditions on the cases (the reference alone meets them), the counts are what the device tests lean on."""
+    g = edges
+    assert os.path.getsize(EDGES) < 1_000_000
+    assert all(v.dtype.kind in "iufb" for v in g.values())
+    n = int(g["n_cases"])
+    cls = np.array([int(g[f"c{i}_cls"]) for i in range(n)])
+    cond = np.array([float(g[f"c{i}_cond"]) for i in range(n)])
+    err_good = np.array([float(g[f"c{i}_ref_err_good"]) for i in range(n)])
+    err_all = np.array([float(g[f"c{i}_ref_err_all"]) for i in range(n)])
+    good, both, rank = (cls & 1) != 0, (cls & 2) != 0, (cls & 4) != 0
+    assert np.array_equal(good, err_good <= 1e-9) and np.array_equal(both, good & (err_all <= 1e-9))
+    assert np.array_equal(rank, ~good & (cond >= 1e12))
+    assert np.count_nonzero(good) >= 30 and np.count_nonzero(good & (cond >= 1e4)) >= 10
+    assert np.count_nonzero(both & (cond >= 1e2)) >= 8 and np.count_nonzero(rank) >= 3
+    assert sorted({int(g[f"c{i}_order"]) for i in range(n)}) == [1, 3, 5, 8, 12, 15]
+    assert sorted({int(g[f"c{i}_mask"]) for i in range(n)}) == list(range(8))
+    lengths = np.array([int(g[f"c{i}_stop"]) - int(g[f"c{i}_start"]) for i in range(n)])
+    assert lengths.min() >= 400 and np.count_nonzero(lengths > 7424) >= 1
+    for i in range(n):
+        order, signal, flags, c = edge_case(g, i)
+        a, b = int(c["start"]), int(c["stop"])
+        ok = flags[a:b] == 0
+        # the stored figures are what the stored arrays give; both flag inputs matter
+        scale = np.max(np.abs(signal[a:b]))
+        assert float(c["ref_err_good"]) == np.max(np.abs(c["ref"] - c["truth"])[ok]) / scale
+        assert float(c["ref_err_all"]) == np.max(np.abs(c["ref"] - c["truth"])) / scale
+        # (a double SVD resolves the smallest singular value to about cond x 1e-16 only: compared where that is small)
+        assert cond[i] > 1e10 or np.isclose(cond[i], np.linalg.cond(H.legendre(b - a, order + 1)[:, ok].T), rtol=1e-3)
+        only_shared = ((c["shared"] & int(g["shared_mask"])) != 0) & ((c["det"] & int(g["det_mask"])) == 0)
+        only_det = ((c["shared"] & int(g["shared_mask"])) == 0) & ((c["det"] & int(g["det_mask"])) != 0)
+        assert np.any(only_shared[a:b]) and np.any(only_det[a:b])
+        # the truth is a least-squares residual: orthogonal to every template on the good samples
+        if good[i]:
+            t = H.legendre(b - a, order + 1)[:, ok]
+            assert np.max(np.abs(t @ c["truth"][ok])) < 1e-6 * np.sqrt(np.count_nonzero(ok)) * scale
+
+
+def test_restatement_stays_within_the_reference_error_of_the_truth(edges):
+    """`filter_polynomial` (double lstsq) on every good-checked case: no further from the 120-digit truth than 4 x the
+    reference's own kernel is (floor 1e-12, the suite's bound), on the good samples and -- all-checked -- on all."""
+    g = edges
+    for i in range(int(g["n_cases"])):
+        order, signal, flags, c = edge_case(g, i)
+        if not int(c["cls"]) & 1:
+            continue
+        a, b = int(c["start"]), int(c["stop"])
+        got = signal.copy()
+        _, status = H.filter_polynomial(order, flags, got, [a], [b])
+        assert status[0] == H.FITTED
+        assert np.array_equal(got[:a], signal[:a]) and np.array_equal(got[b:], signal[b:])
+        ok = flags[a:b] == 0
+        scale = np.max(np.abs(signal[a:b]))
+        err = np.abs(got[a:b] - c["truth"]) / scale
+        assert np.max(err[ok]) <= max(TOL, 4 * float(c["ref_err_good"])), (i, order, np.max(err[ok]))
+        if int(c["cls"]) & 2:
+            assert np.max(err) <= max(TOL, 4 * float(c["ref_err_all"])), (i, order, np.max(err))
 
 
 def test_fixture_is_plain_numeric_and_small(golden):

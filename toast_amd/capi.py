@@ -1373,7 +1373,8 @@ class _Dev:
             _i64(si.size), _p(stream)))
 
     # ---- PolyFilter / CommonModeFilter kernels (csrc/poly_filter.hip)
-    POLY_FITTED, POLY_NO_GOOD, POLY_REDUCED, POLY_NOT_POSITIVE = 0, 1, 2, 3
+    POLY_FITTED, POLY_NO_GOOD, POLY_REDUCED, POLY_NOT_FINITE = 0, 1, 2, 3
+    POLY_NOT_POSITIVE = POLY_NOT_FINITE     # the name this value had while it also reported a failed Cholesky
     POLY_PATH_RULE, POLY_PATH_SINGLE, POLY_PATH_TWO_PASS = 0, 1, 2
 
     def filter_polynomial_stage_cap(self):

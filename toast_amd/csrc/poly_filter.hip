@@ -16,6 +16,14 @@
 //   k_poly_solve      Gram / projection of its kPolyChunk samples to a scratch buffer; one wave per (detector,
 //   k_poly_subtract   interval) adds them up in chunk order (no atomics) and solves; pass 2 subtracts: 25-26 B.
 //
+// The normal equations square the condition number of the templates on the good samples, so they are only the FAST
+// path: the Cholesky compares every pivot with the diagonal entry it started from, and when one falls below
+// kPolyPivotFloor of it (good samples in a contiguous stretch: a detector cut for most of a scan) the job is fitted by
+// `poly_forsythe` instead -- the polynomials orthogonal ON THE GOOD SAMPLES by their three-term recurrence, one
+// projection and one subtraction per term, no linear system.  In the single pass it sweeps the LDS copy; in the two
+// passes k_poly_solve leaves a mark in the scratch buffer and the workgroup of the interval's first chunk sweeps global
+// memory in k_poly_subtract.  Status 3 is left for input that is not finite.
+//
 // The path is chosen per interval by ONE threshold: an interval of at most kPolyStageCap samples (what two workgroups
 // per CU can stage in the 160 KB of LDS) takes the single pass, a longer one the two passes.
 //
@@ -33,7 +41,16 @@ constexpr int kPolyMaxTerms = 16;      // order + 1 supported by the entry point
 constexpr int kPolyStageCap = 7424;    // samples staged in LDS by one workgroup: 10 B each, two workgroups per CU
 constexpr int kPolyChunk = 4096;       // samples per workgroup of the two-pass path
 
-enum PolyStatus : int32_t { kPolyFitted = 0, kPolyNoGood = 1, kPolyReduced = 2, kPolyNotPositive = 3 };
+// kPolyNotFinite (3): a good sample is NaN or infinite; the interval is left untouched.
+enum PolyStatus : int32_t { kPolyFitted = 0, kPolyNoGood = 1, kPolyReduced = 2, kPolyNotFinite = 3 };
+enum PolySolve : int { kSolveDirect = 0, kSolveRobust = 1, kSolveNotFinite = 2 };
+
+// A Cholesky pivot below this fraction of the diagonal entry it started from sends the job to poly_forsythe.  The
+// normal equations lose about 1e-14 / ratio of max|signal| on ALL samples of the interval (host emulation on
+// tests/golden/poly_filter_edges.npz: 5e-13 at a ratio of 0.015, 2e-14 at 0.036, 3e-15 at 0.25), and the bound of the
+// suite is 1e-12: 0.05 keeps the direct solve a factor of five inside it.  Scattered flags never get there -- 10 % at
+// random leave every ratio above 0.9 at all supported orders --, half an interval flagged in one block does.
+constexpr double kPolyPivotFloor = 0.05;
 
 template <int N>
 struct PolyAcc {
@@ -90,10 +107,11 @@ __device__ __forceinline__ void poly_wave_totals(PolyAcc<N> & a, double * out /*
 
 // Solve the leading n x n block of the packed system `tot` (NV values: Gram upper triangle, projection) by Cholesky.
 // Every wave that calls this does the same work in its own registers: lane r < N holds row r of the lower triangle,
-// the columns travel by shuffles, nothing goes through memory.  Returns false when a pivot is not positive;
-// otherwise lane k < n holds coefficient k in `x`.
+// the columns travel by shuffles, nothing goes through memory.  kSolveDirect: lane k < n holds coefficient k in `x`;
+// kSolveRobust: a pivot fell below kPolyPivotFloor of its diagonal entry (or is not positive); kSolveNotFinite: the
+// projection holds a NaN or an infinity (the Gram matrix cannot: |x| < 1).
 template <int N>
-__device__ __forceinline__ bool poly_cholesky(const double * tot, int n, double & x) {
+__device__ __forceinline__ PolySolve poly_cholesky(const double * tot, int n, double & x) {
     constexpr int NP = PolyAcc<N>::NP;
     const int lane = threadIdx.x & 63;
     double a[N], u[N];
@@ -106,6 +124,10 @@ __device__ __forceinline__ bool poly_cholesky(const double * tot, int n, double 
         u[c] = 0.0;
     }
     double b = (lane < N) ? tot[NP + lane] : 0.0;
+    const bool finite = fabs(b) <= 1.7976931348623157e308;
+    // this lane's diagonal entry as it was, and its pivot's square root: compared after the loop, off its chain
+    const double diag = (lane < N) ? tot[lane * N - (lane * (lane - 1)) / 2] : 1.0;
+    double lmine = 1.0;
     bool ok = true;
 #pragma unroll
     for (int k = 0; k < N; ++k) {
@@ -116,6 +138,7 @@ __device__ __forceinline__ bool poly_cholesky(const double * tot, int n, double 
             } else {
                 const double lkk = f_sqrt(akk);
                 a[k] = (lane == k) ? lkk : a[k] / lkk;        // L[lane][k]
+                if (lane == k) lmine = lkk;
 #pragma unroll
                 for (int c = k + 1; c < N; ++c) {
                     if (c < n) {
@@ -127,7 +150,8 @@ __device__ __forceinline__ bool poly_cholesky(const double * tot, int n, double 
             }
         }
     }
-    if (!ok) return false;
+    if (__any(!finite)) return kSolveNotFinite;
+    if (!ok || __any(lane < n && !(lmine * lmine > kPolyPivotFloor * diag))) return kSolveRobust;
     // L y = b
 #pragma unroll
     for (int k = 0; k < N; ++k) {
@@ -147,7 +171,102 @@ __device__ __forceinline__ bool poly_cholesky(const double * tot, int n, double 
         }
     }
     x = b;
-    return true;
+    return kSolveDirect;
+}
+
+__device__ __forceinline__ bool poly_good(uint8_t s, uint8_t smask, uint8_t d, uint8_t dmask) {
+    return ((s & smask) == 0) && ((d & dmask) == 0);
+}
+
+// ------------------------------------------------------------------------------------ the robust fit
+// The monic polynomials orthogonal on the good samples (Forsythe): p_-1 = 0, p_0 = 1,
+// p_{k+1} = (x - a_k) p_k - b_k p_{k-1} with a_k = <x p_k, p_k> / <p_k, p_k>, b_k = <p_k, p_k> / <p_{k-1}, p_{k-1}>,
+// the inner products over the good samples; c_k = <r, p_k> / <p_k, p_k> and r -= c_k p_k on ALL samples.  Sweep k
+// subtracts term k - 1 and projects on p_k in one pass over r: n + 1 sweeps, three sums each, reduced in a fixed
+// order (lanes by xor butterflies, the waves in wave order) so that two runs give the same bits.  No sample's p_k is
+// stored: each lane runs the recurrence up to k from the a_j, b_j in LDS.  The coefficients come out in the Legendre
+// basis of the direct solve: lanes 0..15 carry the Legendre expansion of p_k along (x P_j = ((j + 1) P_{j+1} +
+// j P_{j-1}) / (2j + 1)) and add c_k times it to coefficient `lane`.
+struct PolyRobustLds {
+    double a[kPolyMaxTerms], b[kPolyMaxTerms];
+    double q[3][kPolyMaxTerms];       // Legendre expansions of p_{k-1}, p_k, p_{k+1}, rotating
+    double red[kThreads / 64][3];
+    double c;                         // coefficient of the term the next sweep subtracts
+    int stop;                         // <p_k, p_k> underflowed to zero: no further term is fitted
+};
+
+// All kThreads threads of a workgroup; `r`, `df`, `sf` point at the interval's first sample (LDS or global memory; `df`
+// or `sf` may be null).  In place on r[0, len).  Threads 0..order write `crow`.
+__device__ __forceinline__ void poly_forsythe(double * r, const uint8_t * df, uint8_t det_mask, const uint8_t * sf,
+                                              uint8_t shared_mask, int64_t len, int n, int order, PolyRobustLds & w,
+                                              double * __restrict__ crow) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int t = threadIdx.x;
+    const double dx = 2. / (double)len;
+    const double xstart = 0.5 * dx - 1;
+    if (t < kPolyMaxTerms) {
+        w.q[0][t] = (t == 0) ? 1.0 : 0.0;
+        w.q[2][t] = 0.0;                  // p_-1
+    }
+    if (t == 0) w.stop = 0, w.c = 0.0;
+    __syncthreads();
+    double g_prev = 1.0, coeff = 0.0;
+    for (int k = 0; k <= n; ++k) {
+        const double c_prev = w.c;
+        double s0 = 0.0, s1 = 0.0, s2 = 0.0;
+        for (int64_t i = t; i < len; i += kThreads) {
+            const double x = xstart + (double)i * dx;
+            double pm = 0.0, p = 1.0;
+            for (int j = 0; j < k; ++j) {
+                const double pn = (x - w.a[j]) * p - w.b[j] * pm;
+                pm = p;
+                p = pn;
+            }
+            double ri = r[i];
+            if (k > 0) {
+                ri -= c_prev * pm;
+                r[i] = ri;
+            }
+            const uint8_t fd = (df != nullptr) ? df[i] : (uint8_t)0;
+            const uint8_t fs = (sf != nullptr) ? sf[i] : (uint8_t)0;
+            if (k < n && poly_good(fs, shared_mask, fd, det_mask)) {
+                const double pp = p * p;
+                s0 += pp;
+                s1 += x * pp;
+                s2 += ri * p;
+            }
+        }
+        if (k == n) break;
+#pragma unroll
+        for (int off = 32; off >= 1; off >>= 1) {
+            s0 += __shfl_xor(s0, off, 64);
+            s1 += __shfl_xor(s1, off, 64);
+            s2 += __shfl_xor(s2, off, 64);
+        }
+        if (lane == 0) w.red[wave][0] = s0, w.red[wave][1] = s1, w.red[wave][2] = s2;
+        __syncthreads();
+        if (t < kPolyMaxTerms) {      // every one of these lanes adds the waves up in the same order
+            double g = 0.0, xg = 0.0, rp = 0.0;
+            for (int v = 0; v < kThreads / 64; ++v) g += w.red[v][0], xg += w.red[v][1], rp += w.red[v][2];
+            if (!(g > 0.0)) {
+                if (t == 0) w.stop = 1, w.c = 0.0;
+            } else {
+                const double ak = xg / g, bk = (k > 0) ? g / g_prev : 0.0, ck = rp / g;
+                const double * qc = w.q[k % 3];
+                const double * qp = w.q[(k + 2) % 3];
+                coeff += ck * qc[t];
+                // x * p_k in the Legendre basis, entry t
+                const double below = (t > 0) ? qc[t - 1] * ((double)t / (double)(2 * t - 1)) : 0.0;
+                const double above = (t + 1 < kPolyMaxTerms) ? qc[t + 1] * ((double)(t + 1) / (double)(2 * t + 3)) : 0.0;
+                w.q[(k + 1) % 3][t] = (below + above) - ak * qc[t] - bk * qp[t];
+                if (t == 0) w.a[k] = ak, w.b[k] = bk, w.c = ck;
+                g_prev = g;
+            }
+        }
+        __syncthreads();
+        if (w.stop != 0) break;
+    }
+    if (t <= order) crow[t] = coeff;
 }
 
 // signal[i] -= sum_k coeff[k] P_k(x_i), one order after the other like toast_tod_filter.cpp:144-156
@@ -166,10 +285,6 @@ struct PolyJob {
     int32_t view;    // index into the caller's interval list
     int32_t chunk0;  // two-pass: first slot of this interval in the chunk list
 };
-
-__device__ __forceinline__ bool poly_good(uint8_t s, uint8_t smask, uint8_t d, uint8_t dmask) {
-    return ((s & smask) == 0) && ((d & dmask) == 0);
-}
 
 // Bytes [src, src + n) -> LDS dst[pad + i] with pad = src & 15, so that aligned 16-byte granules of global memory are
 // aligned granules of LDS; partial granules at both ends go byte by byte.
@@ -198,6 +313,7 @@ __global__ __launch_bounds__(kThreads) void k_poly_single(
     extern __shared__ double2 lds2[];
     __shared__ double wave_tot[4 * (NV + 1)];
     __shared__ double tot[NV + 1];
+    __shared__ PolyRobustLds robust;
     // [stage_samples + 2 doubles][stage_samples + 32 bytes of detector flags][the same of shared flags]
     double * s_sig = reinterpret_cast<double *>(lds2);
     uint8_t * s_df = reinterpret_cast<uint8_t *>(s_sig + stage_samples + 2);
@@ -263,10 +379,27 @@ __global__ __launch_bounds__(kThreads) void k_poly_single(
     }
     const int n = (ngood < order + 1) ? ngood : order + 1;
     double xk = 0.0;
-    const bool ok = poly_cholesky<N>(tot, n, xk);
-    if (!ok) {
-        if (threadIdx.x == 0) *srow = kPolyNotPositive;
+    const PolySolve solve = poly_cholesky<N>(tot, n, xk);
+    if (solve == kSolveNotFinite) {
+        if (threadIdx.x == 0) *srow = kPolyNotFinite;
         if ((int)threadIdx.x <= order) crow[threadIdx.x] = 0.0;
+        return;
+    }
+    if (solve == kSolveRobust) {
+        // the LDS copy becomes the residual; it goes back out as it is
+        poly_forsythe(s_sig + pad_s, (df != nullptr) ? s_df + pad_d : nullptr, det_mask, (sf != nullptr) ? s_sf + pad_f : nullptr,
+                      shared_mask, len, n, order, robust, crow);
+        if (threadIdx.x == 0) *srow = (n < order + 1) ? kPolyReduced : kPolyFitted;
+        __syncthreads();
+        for (int p = threadIdx.x; p < n_pair; p += kThreads) {
+            const int i0 = 2 * p;
+            if (i0 >= pad_s && i0 + 2 <= pad_s + len) {
+                *reinterpret_cast<double2 *>(sig - pad_s + i0) = lds2[p];
+            } else {
+                if (i0 >= pad_s && i0 < pad_s + len) sig[i0 - pad_s] = s_sig[i0];
+                if (i0 + 1 >= pad_s && i0 + 1 < pad_s + len) sig[i0 + 1 - pad_s] = s_sig[i0 + 1];
+            }
+        }
         return;
     }
     double coeff[N];
@@ -342,7 +475,7 @@ __global__ __launch_bounds__(kThreads) void k_poly_partial(
 // One wave per (detector, two-pass interval): partial sums in chunk order, then the solve.
 template <int N>
 __global__ __launch_bounds__(64) void k_poly_solve(const PolyJob * __restrict__ jobs, int64_t n_chunk,
-                                                   const double * __restrict__ partial, int order, int64_t n_interval,
+                                                   double * __restrict__ partial, int order, int64_t n_interval,
                                                    double * __restrict__ coeff_out, int32_t * __restrict__ status_out) {
     constexpr int NV = PolyAcc<N>::NV;
     __shared__ double tot[NV + 1];
@@ -364,7 +497,15 @@ __global__ __launch_bounds__(64) void k_poly_solve(const PolyJob * __restrict__ 
     int n = 0;
     if (ngood > 0) {
         n = (ngood < order + 1) ? ngood : order + 1;
-        status = poly_cholesky<N>(tot, n, xk) ? ((n < order + 1) ? kPolyReduced : kPolyFitted) : kPolyNotPositive;
+        const PolySolve solve = poly_cholesky<N>(tot, n, xk);
+        status = (solve == kSolveNotFinite) ? kPolyNotFinite : ((n < order + 1) ? kPolyReduced : kPolyFitted);
+        // The robust fit is left to k_poly_subtract: the good-sample count of the interval's first chunk, which has
+        // been added up above, becomes -n.  That mark does not change while k_poly_subtract runs, so every workgroup
+        // of the interval sees the same thing whenever it is scheduled (the status and the coefficients do change).
+        if (solve == kSolveRobust) {
+            if (threadIdx.x == 0) partial[(d * n_chunk + job.chunk0) * (NV + 1) + NV] = -(double)n;
+            xk = 0.0;
+        }
     }
     const bool fitted = (status == kPolyFitted || status == kPolyReduced);
     if ((int)threadIdx.x <= order) crow[threadIdx.x] = (fitted && (int)threadIdx.x < n) ? xk : 0.0;
@@ -373,15 +514,32 @@ __global__ __launch_bounds__(64) void k_poly_solve(const PolyJob * __restrict__ 
 
 template <int N>
 __global__ __launch_bounds__(kThreads) void k_poly_subtract(
-    double * __restrict__ signal, int64_t n_samp, const int32_t * __restrict__ sig_index, const PolyJob * __restrict__ jobs,
-    const PolyChunk * __restrict__ chunks, int order, int64_t n_interval, const double * __restrict__ coeff_in,
-    const int32_t * __restrict__ status_in) {
+    double * __restrict__ signal, int64_t n_samp, const int32_t * __restrict__ sig_index,
+    const uint8_t * __restrict__ det_flags, const int32_t * __restrict__ flag_index, uint8_t det_mask,
+    const uint8_t * __restrict__ shared_flags, uint8_t shared_mask, const PolyJob * __restrict__ jobs,
+    const PolyChunk * __restrict__ chunks, int64_t n_chunk, const double * __restrict__ partial, int order,
+    int64_t n_interval, double * __restrict__ coeff_io, const int32_t * __restrict__ status_in) {
+    constexpr int NV = PolyAcc<N>::NV;
+    __shared__ PolyRobustLds robust;
     const PolyChunk ch = chunks[blockIdx.x];
     const PolyJob job = jobs[ch.job];
     const int64_t d = blockIdx.y;
     const int32_t status = status_in[d * n_interval + job.view];
     if (status != kPolyFitted && status != kPolyReduced) return;
-    const double * __restrict__ crow = coeff_in + (d * n_interval + job.view) * (order + 1);
+    const double mark = partial[(d * n_chunk + job.chunk0) * (NV + 1) + NV];
+    if (mark < 0.0) {
+        // k_poly_solve left the fit to poly_forsythe: the whole interval by the workgroup of its first chunk, which
+        // alone writes the coefficients; the other workgroups of the interval have nothing to do
+        if (ch.chunk != 0) return;
+        const int n = (int)(-mark);
+        double * __restrict__ r = signal + (int64_t)sig_index[d] * n_samp + job.first;
+        const uint8_t * df = (det_flags != nullptr) ? det_flags + (int64_t)flag_index[d] * n_samp + job.first : nullptr;
+        const uint8_t * sf = (shared_flags != nullptr) ? shared_flags + job.first : nullptr;
+        poly_forsythe(r, df, det_mask, sf, shared_mask, job.last - job.first, n, order, robust,
+                      coeff_io + (d * n_interval + job.view) * (order + 1));
+        return;
+    }
+    const double * __restrict__ crow = coeff_io + (d * n_interval + job.view) * (order + 1);
     double coeff[N];
 #pragma unroll
     for (int k = 0; k < N; ++k) coeff[k] = (k <= order) ? crow[k] : 0.0;
@@ -537,7 +695,8 @@ void poly_launch(PolyArgs & a) {
                                partial, (int)a.order, a.n_interval, coeff, status);
             check_launch();
             hipLaunchKernelGGL(k_poly_subtract<N>, dim3((unsigned)n_chunk, (unsigned)nd), dim3(kThreads), 0, a.st, a.d_signal,
-                               a.n_samp, sidx + d0, jobs, chunks, (int)a.order, a.n_interval, coeff, status);
+                               a.n_samp, sidx + d0, a.d_det_flags, fidx + d0, a.det_mask, a.d_shared_flags, a.shared_mask,
+                               jobs, chunks, n_chunk, partial, (int)a.order, a.n_interval, coeff, status);
             check_launch();
         }
     }

@@ -115,9 +115,15 @@ class PolyFilter(Operator):
     """Operator which applies polynomial filtering to the TOD.
 
     ``coefficients[obs.name]`` ([n_det, n_interval, order + 1], zero beyond the fitted order), ``status[obs.name]``
-    (int32 [n_det, n_interval]: 0 fitted, 1 no good sample, 2 order reduced to the number of good samples, 3 not
-    positive definite -- interval left untouched) and ``filtered_detectors[obs.name]`` describe the last call.
-    ``det_data`` must be float64 (the reference converts other types; this operator raises)."""
+    (int32 [n_det, n_interval]: 0 fitted, 1 no good sample, 2 order reduced to the number of good samples, 3 a good
+    sample is NaN or infinite -- interval left untouched) and ``filtered_detectors[obs.name]`` describe the last call.
+    ``det_data`` must be float64 (the reference converts other types; this operator raises).
+
+    The solve: normal equations and Cholesky in fp64 while every pivot keeps at least 5 % of its diagonal entry
+    (scattered flags); otherwise -- good samples in a contiguous stretch, e.g. a detector cut for most of a throw --
+    the polynomials orthogonal on the good samples by their three-term recurrence, which stays as close to the exact
+    least-squares residual as the SVD solve of the reference.  Both give Legendre coefficients and the same status
+    values; status 3 does not occur for finite input."""
 
     API = Int(0, help="Internal interface version for this operator")
     det_data = Unicode(defaults.det_data, help="Observation detdata key apply filtering to")
