@@ -967,6 +967,48 @@ int toast_hip_periodic_project_signal_dev(
 int toast_hip_periodic_apply_precond_dev(int64_t n_amp, const int32_t * d_hits, const uint8_t * d_amp_flags,
                                          const double * d_amp_in, double * d_amp_out, void * stream);
 
+/* ------------------------------------------------------------------------------------
+ * Fourier2D template (toast_amd/csrc/fourier2d.hip; device-resident buffers, host index and interval arrays).
+ * The reference is NumPy and SciPy, one detector at a time (src/toast/templates/fourier2d.py).  The template holds
+ * nmode amplitudes per SAMPLE of every view, shared by all detectors: the amplitudes of sample i of view v are
+ * d_amplitudes[view_amp_offsets[v] + i * nmode + m]; d_templates[d][m] is the value of mode m at detector d
+ * (fourier2d.py:213-231, built on the host), in the order of data_index.  nmode = (2 order)^2 + 1, + 2 with
+ * subharmonics, for order 1 to 3: 5, 7, 17, 19, 37 or 39 (<= toast_hip_fourier2d_max_modes()).  Views are clipped to
+ * [0, n_samp).  n_group: 0 = by the rule (the detectors are split over the grid only when the sample tiles alone cannot
+ * fill the device), > 0 = that many detector groups.
+ *   add_to_signal   signal[d][s] += sum_m a[s][m] T[d][m], the sum in the order of NumPy's reduction
+ *                   [fourier2d.py:395-414]
+ *   project_signal  a[s][m] += signal[d][s] T[d][m], detector after detector: accumulated, NO flags
+ *                   [fourier2d.py:416-435].  One group: the reference's own sequence of roundings (bit-identical).
+ *                   Several groups: partial sums added in group order.  No atomics: order-deterministic either way.
+ *   norms           d_norms[s][m] = 1 / sum_d good[d][s] w2[d][m] in detector order, 0 where the sum is 0, with
+ *                   good = (flags & mask) == 0 (every sample when d_det_flags is NULL) and
+ *                   d_weighted_squares = w2[d][m] = (T[d][m] * T[d][m]) * weight_d [fourier2d.py:331-365; bit-identical]
+ *   apply_precond   d_amp_out[i] = d_amp_in[i] * d_norms[i] [fourier2d.py:457-459]
+ *   add_prior       one view: d_amp_out[i][m] += convolve(d_amp_in[:, m], invcorr * scale[m], "same")[i]
+ *                   [fourier2d.py:437-455] as a circular convolution of n_fft >= view_len + filter_len - 1 points (even):
+ *                   d_spectrum is the FFTW half-complex transform of invcorr zero-padded to n_fft, d_work holds
+ *                   2 * nmode * n_fft doubles; d_amp_in / d_amp_out point at the view's first amplitude.
+ * ---------------------------------------------------------------------------------- */
+int toast_hip_fourier2d_max_modes(void);
+int toast_hip_fourier2d_add_to_signal_dev(
+    int64_t nmode, const double * d_templates, const int64_t * view_amp_offsets /*host*/, const double * d_amplitudes,
+    const int32_t * data_index /*host*/, int64_t n_det, double * d_det_data, int64_t n_samp,
+    const toast_hip_interval * intervals /*host*/, int64_t n_view, int64_t n_group, void * stream);
+int toast_hip_fourier2d_project_signal_dev(
+    int64_t nmode, const double * d_templates, const int64_t * view_amp_offsets /*host*/, double * d_amplitudes,
+    const int32_t * data_index /*host*/, int64_t n_det, const double * d_det_data, int64_t n_samp,
+    const toast_hip_interval * intervals /*host*/, int64_t n_view, int64_t n_group, void * stream);
+int toast_hip_fourier2d_norms_dev(
+    int64_t nmode, const double * d_weighted_squares, const int64_t * view_amp_offsets /*host*/,
+    const int32_t * flag_index /*host*/, const uint8_t * d_det_flags, uint8_t det_flag_mask, int64_t n_det, int64_t n_samp,
+    const toast_hip_interval * intervals /*host*/, int64_t n_view, double * d_norms, void * stream);
+int toast_hip_fourier2d_apply_precond_dev(int64_t n_amp, const double * d_norms, const double * d_amp_in,
+                                          double * d_amp_out, void * stream);
+int toast_hip_fourier2d_add_prior_dev(
+    int64_t nmode, int64_t view_len, const double * d_amp_in, double * d_amp_out, int64_t filter_len, int64_t n_fft,
+    const double * d_spectrum, const double * scale /*host*/, double * d_work, void * stream);
+
 /* Host-pointer forms with the reference's arguments (src/toast/_libtoast/tod_filter.cpp:326-383, 9-97): buffers are
  * looked up in the memory manager (use_accel) or staged through the device.  `signals` are n_signal separate arrays of
  * n_samp doubles sharing one flag vector (non-zero = flagged). */

@@ -1514,6 +1514,67 @@ class _Dev:
         _check(lib().toast_hip_periodic_apply_precond_dev(_i64(n_amp), _p(d_hits), _p(d_amp_flags), _p(d_amp_in),
                                                           _p(d_amp_out), _p(stream)))
 
+    # ---- Fourier2D template kernels (csrc/fourier2d.hip)
+    def fourier2d_max_modes(self):
+        """Most modes per sample the Fourier2D kernels take."""
+        return int(real_lib().toast_hip_fourier2d_max_modes())
+
+    def fourier2d_add_to_signal(self, nmode, d_templates, view_amp_offsets, d_amplitudes, data_index, d_det_data, n_samp,
+                                intervals, n_group=0, stream=0):
+        """``d_templates`` float64 [n_det][nmode] in the order of ``data_index``; one amplitude offset per view."""
+        vo = self._small(view_amp_offsets, np.int64)
+        di = self._small(data_index, np.int32)
+        iv = self._small(intervals, interval_dtype)
+        if vo.size != iv.size:
+            raise RuntimeError("fourier2d_add_to_signal: one amplitude offset per view")
+        _check(lib().toast_hip_fourier2d_add_to_signal_dev(
+            _i64(nmode), _p(d_templates), _p(vo), _p(d_amplitudes), _p(di), _i64(di.size), _p(d_det_data), _i64(n_samp),
+            _p(iv), _i64(iv.size), _i64(n_group), _p(stream)))
+
+    def fourier2d_project_signal(self, nmode, d_templates, view_amp_offsets, d_amplitudes, data_index, d_det_data, n_samp,
+                                 intervals, n_group=0, stream=0):
+        vo = self._small(view_amp_offsets, np.int64)
+        di = self._small(data_index, np.int32)
+        iv = self._small(intervals, interval_dtype)
+        if vo.size != iv.size:
+            raise RuntimeError("fourier2d_project_signal: one amplitude offset per view")
+        _check(lib().toast_hip_fourier2d_project_signal_dev(
+            _i64(nmode), _p(d_templates), _p(vo), _p(d_amplitudes), _p(di), _i64(di.size), _p(d_det_data), _i64(n_samp),
+            _p(iv), _i64(iv.size), _i64(n_group), _p(stream)))
+
+    def fourier2d_norms(self, nmode, d_weighted_squares, view_amp_offsets, flag_index, d_det_flags, det_flag_mask, n_det,
+                        n_samp, intervals, d_norms, stream=0):
+        """``d_weighted_squares`` float64 [n_det][nmode] = (T * T) * weight; ``d_norms`` like the amplitudes."""
+        vo = self._small(view_amp_offsets, np.int64)
+        fi = None if flag_index is None else self._small(flag_index, np.int32)
+        iv = self._small(intervals, interval_dtype)
+        if vo.size != iv.size:
+            raise RuntimeError("fourier2d_norms: one amplitude offset per view")
+        if fi is not None and fi.size != int(n_det):
+            raise RuntimeError("fourier2d_norms: one flag row per detector")
+        _check(lib().toast_hip_fourier2d_norms_dev(
+            _i64(nmode), _p(d_weighted_squares), _p(vo), _p(fi), _p(d_det_flags), _u8(det_flag_mask), _i64(n_det),
+            _i64(n_samp), _p(iv), _i64(iv.size), _p(d_norms), _p(stream)))
+
+    def fourier2d_apply_precond(self, n_amp, d_norms, d_amp_in, d_amp_out, stream=0):
+        _check(lib().toast_hip_fourier2d_apply_precond_dev(_i64(n_amp), _p(d_norms), _p(d_amp_in), _p(d_amp_out),
+                                                           _p(stream)))
+
+    def fourier2d_add_prior(self, nmode, view_len, d_amp_in, d_amp_out, filter_len, n_fft, d_spectrum, scale, d_work,
+                            stream=0):
+        """One view; ``d_amp_in`` / ``d_amp_out`` point at its first amplitude, ``d_work`` holds 2 * nmode * n_fft doubles."""
+        sc = self._small(scale, np.float64)
+        if sc.size != int(nmode):
+            raise RuntimeError("fourier2d_add_prior: one scale per mode")
+        _check(lib().toast_hip_fourier2d_add_prior_dev(
+            _i64(nmode), _i64(view_len), _p(d_amp_in), _p(d_amp_out), _i64(filter_len), _i64(n_fft), _p(d_spectrum), _p(sc),
+            _p(d_work), _p(stream)))
+
+    def fft_r1d(self, forward, length, count, d_in, d_out, scale=1.0, stream=0):
+        """``count`` real transforms of ``length`` in FFTW half-complex layout (toast_hip_fft_r1d_dev)."""
+        _check(lib().toast_hip_fft_r1d_dev(C.c_int(1 if forward else 0), _i64(length), _i64(count), _p(d_in), _p(d_out),
+                                           C.c_double(float(scale)), _p(stream)))
+
     def combine_flags(self, d_out, out_index, d_det_flags, n_flag_samp, flag_index, det_flag_mask, d_shared_flags,
                       n_shared_flags, shared_flag_mask, n_samp, intervals, n_out_rows=0, outside_value=-1, stream=0):
         oi = self._small(out_index, np.int32)

@@ -814,11 +814,27 @@ class SharedDataManager(_KeyAccel, dict):
 
 
 # ----------------------------------------------------------------------------- instrument
+def detector_direction(quat):
+    """The boresight axis (0, 0, 1) rotated by a detector quaternion (x, y, z, w): qarray.rotate(quat, zaxis) with the
+    operation order of the reference's kernel (src/libtoast/src/toast_math_qarray.cpp:200-256: normalise, products,
+    2 * (...) + v)."""
+    q = np.asarray(quat, dtype=np.float64)
+    norm = 0.0
+    for v in q:
+        norm += v * v
+    q = q / np.sqrt(norm)
+    xw, yw = q[3] * q[0], q[3] * q[1]
+    x2, y2 = -q[0] * q[0], -q[1] * q[1]
+    xz, yz = q[0] * q[2], q[1] * q[2]
+    return np.array([2 * (yw + xz), 2 * (yz - xw), 2 * (x2 + y2) + 1.0])
+
+
 class Focalplane:
     """Detector table: ``detector_data[det]`` has ``quat``, ``gamma``, ``pol_leakage``
     (epsilon) and ``cal`` (reference: src/toast/instrument.py Focalplane)."""
 
-    def __init__(self, detectors, quats, gamma=None, epsilon=None, cal=None, sample_rate=1.0, columns=None):
+    def __init__(self, detectors, quats, gamma=None, epsilon=None, cal=None, sample_rate=1.0, columns=None,
+                 field_of_view=None):
         self.detectors = list(detectors)
         n = len(self.detectors)
         self.sample_rate = float(sample_rate)
@@ -835,6 +851,17 @@ class Focalplane:
         for name, values in (columns or {}).items():
             for d, v in zip(self.detectors, values):
                 self._table[d][name] = v
+        #: full opening angle of the focal plane in radians (instrument.py Focalplane.field_of_view)
+        self.field_of_view = self._compute_fov() if field_of_view is None else float(field_of_view)
+
+    def _compute_fov(self):
+        """instrument.py:800-815: 1.01 * twice the largest angle between a detector and the boresight; one degree when
+        every detector looks along the boresight."""
+        mincos = 1.0
+        if len(self.detectors) > 0:
+            mincos = min(float(detector_direction(self._table[d]["quat"])[2]) for d in self.detectors)
+        fov = 1.01 * 2.0 * np.arccos(mincos)
+        return float(np.radians(1.0)) if fov == 0 else float(fov)
 
     def __getitem__(self, det):
         return self._table[det]

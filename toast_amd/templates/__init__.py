@@ -1,5 +1,5 @@
-"""Template amplitudes and the destriping templates: Offset (baselines, below), SubHarmonic (templates/subharmonic.py)
-and Periodic (templates/periodic.py).
+"""Template amplitudes and the destriping templates: Offset (baselines, below), SubHarmonic (templates/subharmonic.py),
+Periodic (templates/periodic.py) and Fourier2D (templates/fourier2d.py).
 
 Reference: src/toast/templates/amplitudes.py (Amplitudes, AmplitudesMap),
 src/toast/templates/template.py (Template), src/toast/templates/offset/offset.py (Offset,
@@ -44,13 +44,25 @@ class Amplitudes(AcceleratorObject):
         self._comm = comm
         self._n_global = int(n_global)
         self._n_local = int(n_local)
-        if local_indices is not None or local_ranges is not None:
-            raise NotImplementedError("Amplitudes with local_ranges / local_indices (values shared between some "
-                                      "processes) are not supported: only full copies and disjoint pieces")
-        self._local_indices = None
-        self._local_ranges = None
         self._use_group = bool(use_group)
         world = None if comm is None else (comm.comm_group if use_group else comm.comm_world)
+        if local_indices is not None:
+            raise NotImplementedError("Amplitudes with local_indices (values shared between some processes) are not "
+                                      "supported: only full copies and disjoint pieces")
+        self._local_indices = None
+        self._local_ranges = None
+        if local_ranges is not None:
+            # ranges of (first global index, length) on a single process (the Fourier2D template's case: every view
+            # is one range): they cover the whole vector, so they are kept for the caller and change nothing else
+            if world is not None and (comm.group_size if use_group else comm.world_size) > 1:
+                raise NotImplementedError("Amplitudes with local_ranges on more than one process (values shared between "
+                                          "some processes) are not supported: only full copies and disjoint pieces")
+            ranges = [(int(first), int(n)) for first, n in local_ranges]
+            if any(n < 0 or first < 0 for first, n in ranges):
+                raise RuntimeError("local_ranges must be (first, n) pairs that are not negative")
+            if sum(n for _, n in ranges) != self._n_local or self._n_local != self._n_global:
+                raise RuntimeError("local_ranges on a single process must add up to n_local == n_global")
+            self._local_ranges = ranges
         self._full = False
         if _full is not None:
             self._full = bool(_full)      # copy of an existing distribution: no collective
@@ -152,6 +164,7 @@ class Amplitudes(AcceleratorObject):
     def duplicate(self):
         ret = Amplitudes(self._comm, self._n_global, self._n_local, dtype=self._local.dtype, use_group=self._use_group,
                          _full=self._full)
+        ret._local_ranges = None if self._local_ranges is None else list(self._local_ranges)
         if self.accel_in_use():
             ret.local_flags[:] = self.local_flags
             ret.accel_create(self._accel_name + "_dup")
@@ -894,7 +907,7 @@ class Offset(Template):
         self._flag_cache = {}
 
 
-# ---- shared by the templates with batched device sweeps (SubHarmonic, Periodic)
+# ---- shared by the templates with batched device sweeps (SubHarmonic, Periodic, Fourier2D)
 def amps_to_device(amplitudes, name):
     """Make the device copy of an amplitude vector the current one (created and uploaded when needed)."""
     if not amplitudes.accel_exists():
@@ -940,5 +953,6 @@ def block_amp_offsets(cache, det_start, obs_dets, per_obs, iob, dets):
     return cache[key]
 
 
+from .fourier2d import Fourier2D  # noqa: E402
 from .periodic import Periodic  # noqa: E402
 from .subharmonic import SubHarmonic  # noqa: E402

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Time the SubHarmonic / Periodic template sweeps on the GPU next to the stream ceiling of the same byte mix.
+"""Time the SubHarmonic / Periodic / Fourier2D template sweeps on the GPU next to the stream ceiling of the same byte mix.
 
 Shape: 256 detectors x 720 000 samples at 200 Hz (one GPU's share of BASELINE configs[4]), the `scanning` intervals of an
 ops.SimGround constant-elevation scan (113 sweeps of 6000 samples), 8 % of the samples flagged.  Timed with device events,
@@ -9,7 +9,10 @@ in one process:
   the two add_to_signal sweeps; the 8 B (read-only) sweeps are set against half of its bytes at the same rate;
 * toast_hip_subharmonic_add_to_signal_dev / _project_signal_dev / _precond_build_dev, order 1, 3 and 8;
 * toast_hip_periodic_add_to_signal_dev and _project_signal_dev (LDS path, and global atomics forced), 100 azimuth bins
-  on a shared key.
+  on a shared key;
+* toast_hip_fourier2d_add_to_signal_dev / _project_signal_dev at order 1 and 3 with subharmonics (7 and 39 amplitudes per
+  sample, shared by all detectors), and toast_hip_fourier2d_add_prior_dev over all views next to the time of the two
+  batched transforms per view that it contains (``prior_fft_share``).
 
 Prints one JSON line: ms, algorithmic bytes, TB/s and the ratio of each rate to the ceiling's.
 
@@ -120,6 +123,48 @@ def main(argv=None):
         ms = timed(lambda: D.periodic_project_signal(index.data_ptr(), None, idx, sig.data_ptr(), idx, dflags.data_ptr(), 1,
                                                      offs, amps.data_ptr(), n_samp, nbins, path=path))
         out[f"periodic_project_{name}"] = entry(ms, 9 * n_det * n_samp + 4 * n_samp)
+    # Fourier2D: nmode amplitudes per sample of the views, one basis row per detector
+    from toast_amd.templates.fourier2d import half_complex, prior_fft_length
+
+    voff_samples = np.concatenate([[0], np.cumsum(stops - starts)[:-1]])
+    for order in (1, 3):
+        nmode = (2 * order) ** 2 + 3
+        amps = 1.0e-3 * torch.randn(covered * nmode, dtype=torch.float64, device="cuda", generator=gen)
+        aout = torch.zeros(covered * nmode, dtype=torch.float64, device="cuda")
+        tmpl = torch.randn((n_det, nmode), dtype=torch.float64, device="cuda", generator=gen)
+        voff = voff_samples * nmode
+        ms = timed(lambda: D.fourier2d_add_to_signal(nmode, tmpl.data_ptr(), voff, amps.data_ptr(), idx, sig.data_ptr(), n_samp,
+                                                     ivl))
+        out[f"fourier2d_add_order{order}"] = entry(ms, 16 * n_det * covered + 8 * nmode * covered)
+        ms = timed(lambda: D.fourier2d_project_signal(nmode, tmpl.data_ptr(), voff, aout.data_ptr(), idx, sig.data_ptr(),
+                                                      n_samp, ivl))
+        out[f"fourier2d_project_order{order}"] = entry(ms, 8 * n_det * covered + 16 * nmode * covered)
+        lens = sorted(set(int(x) for x in (stops - starts)))
+        spectra = {}
+        for n in lens:
+            taps = n - n % 2
+            n_fft = prior_fft_length(n, taps)
+            filt = np.exp(-np.abs(np.arange(taps) - taps // 2) / 50.0)
+            spectra[n] = (taps, n_fft, torch.from_numpy(half_complex(np.fft.rfft(filt, n_fft), n_fft)).cuda())
+        most = max(v[1] for v in spectra.values())
+        work = torch.zeros(2 * nmode * most, dtype=torch.float64, device="cuda")
+        scale = np.full(nmode, 4.0)
+
+        def prior():
+            for first, last, off in zip(starts, stops, voff):
+                taps, n_fft, spec = spectra[int(last - first)]
+                D.fourier2d_add_prior(nmode, int(last - first), amps.data_ptr() + 8 * int(off), aout.data_ptr() + 8 * int(off),
+                                      taps, n_fft, spec.data_ptr(), scale, work.data_ptr())
+
+        def transforms():
+            for first, last in zip(starts, stops):
+                n_fft = spectra[int(last - first)][1]
+                D.fft_r1d(True, n_fft, nmode, work.data_ptr(), work.data_ptr() + 8 * nmode * n_fft)
+                D.fft_r1d(False, n_fft, nmode, work.data_ptr() + 8 * nmode * n_fft, work.data_ptr())
+
+        ms_prior, ms_fft = timed(prior), timed(transforms)
+        out[f"fourier2d_prior_order{order}"] = {"ms": round(ms_prior, 4), "fft_ms": round(ms_fft, 4),
+                                                "prior_fft_share": round(ms_fft / ms_prior, 3)}
     print(json.dumps(out))
 
 

@@ -8,7 +8,7 @@ configs[4] is upstream of this path and is not part of
     python workflows/ground_filter_mapmaker.py [--ndet 256] [--minutes 60] [--rate 200] [--nside 2048]
                                                [--iter 10] [--split] [--filter-order 5] [--trend-order 5]
                                                [--polyfilter ORDER] [--common-mode] [--save-map FILE]
-                                               [--subharmonic ORDER] [--periodic-az BINS]
+                                               [--subharmonic ORDER] [--periodic-az BINS] [--fourier2d ORDER]
 """
 import argparse
 import os
@@ -23,7 +23,7 @@ from toast_amd import ops  # noqa: E402
 from toast_amd.accel import native  # noqa: E402
 from toast_amd.data import defaults  # noqa: E402
 from toast_amd.sim import create_ground_data  # noqa: E402
-from toast_amd.templates import Offset, Periodic, SubHarmonic  # noqa: E402
+from toast_amd.templates import Fourier2D, Offset, Periodic, SubHarmonic  # noqa: E402
 
 
 def main(argv=None):
@@ -54,6 +54,9 @@ def main(argv=None):
     ap.add_argument("--periodic-az", type=int, default=None, metavar="BINS",
                     help="solve for a ground template of BINS azimuth bins per detector and observation next to the "
                          "baselines (templates.Periodic, key = azimuth; off by default)")
+    ap.add_argument("--fourier2d", type=int, default=None, metavar="ORDER",
+                    help="solve for 2-D Fourier modes up to ORDER across the focal plane, shared by all detectors, with a "
+                         "correlation prior in time, next to the baselines (templates.Fourier2D; off by default)")
     ap.add_argument("--sim-noise", action="store_true",
                     help="draw the detector noise on the device with ops.SimNoise from the observation's AnalyticNoise "
                          "instead of host white noise (off by default)")
@@ -128,6 +131,8 @@ def main(argv=None):
         templates.append(SubHarmonic(order=args.subharmonic, noise_model=defaults.noise_model, name="subharmonic"))
     if args.periodic_az is not None:
         templates.append(Periodic(key=defaults.azimuth, bins=args.periodic_az, name="ground"))
+    if args.fourier2d is not None:
+        templates.append(Fourier2D(order=args.fourier2d, noise_model=defaults.noise_model, name="fourier2d"))
     tmatrix = ops.TemplateMatrix(templates=templates, view=defaults.scanning_interval)
     mapper = ops.MapMaker(name="mapmaker", det_data=defaults.det_data, binning=binner, template_matrix=tmatrix,
                           iter_min=args.iter, iter_max=args.iter, convergence=1e-30, keep_solver_products=True)
