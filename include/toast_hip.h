@@ -897,6 +897,44 @@ int toast_hip_common_mode_subtract_dev(
     const uint8_t * d_det_flags, uint8_t det_flag_mask, const uint8_t * d_shared_flags, uint8_t shared_flag_mask,
     int64_t n_det, double * d_mean, int64_t * d_hits, void * stream);
 /* ------------------------------------------------------------------------------------
+ * Focal-plane polynomial filter for toast.ops.PolyFilter2D (device-resident buffers; host index, group, template
+ * and interval arrays)
+ *
+ * toast_hip_filter_poly2d_dev replaces `filter_poly2D` of src/libtoast/src/toast_tod_filter.cpp:357-470 (binding
+ * src/toast/_libtoast/tod_filter.cpp, `filter_poly2D`) TOGETHER WITH the host loops around it in
+ * src/toast/ops/polyfilter/polyfilter.py:270-381 (transposes, flag update, subtraction).  n_mode = (order + 1)^2;
+ * templates [n_det][n_mode] with templates[d][i * (order + 1) + j] = theta_d^i phi_d^j (checked: the kernels build the
+ * normal matrix from the moments theta^p phi^q); det_group[d] in 0 .. n_group - 1.  For every sample s of every view
+ * [starts[v], stops[v]) clipped to [0, n_samp) -- stop exclusive -- and every group g, over the detectors d of the group
+ * with good = !(shared_flags[s] & shared_flag_mask) && !(det_flags[flag_index[d]][s] & det_flag_mask):
+ *   A = sum_good T_d T_d^T, b = sum_good T_d signal[signal_index[d]][s]; c = pinv(A) b by a cyclic Jacobi
+ *   eigen-solve in fp64, every eigenvalue <= 1e-6 lambda_max dropped (DGELSS's rcond on a symmetric positive
+ *   semi-definite matrix); lambda_max = 0 gives c = 0.  A flagged detector is selected out, never multiplied in.
+ *   b not finite (a NaN or an infinity among the good signals) gives c = 0 and TOAST_HIP_POLY2D_NOT_FINITE.
+ *   When d_det_flags is given and all c_m == 0, poly_flag_mask is OR-ed into the flag of every detector of the group
+ *   at s; otherwise signal -= sum_m c_m T[d][m] for the good detectors.  Everything else keeps its bits.
+ * d_coeff [n_samp][n_group][n_mode] and d_status int32 [n_samp][n_group] (TOAST_HIP_POLY2D_*) are optional; only the
+ * samples inside the views are written.  d_det_flags / d_shared_flags may be NULL.  order 0 .. 3
+ * (toast_hip_filter_poly2d_max_order()); larger orders are the caller's (the operator takes its host path).
+ * path: 0 = by the rule, 1 = moments, solve and subtraction as three kernels through a scratch buffer (the only variant
+ * so far).  No atomics, fixed summation order: detectors in list order, modes ascending.
+ * ---------------------------------------------------------------------------------- */
+#define TOAST_HIP_POLY2D_SOLVED 0
+#define TOAST_HIP_POLY2D_NO_GOOD 1
+#define TOAST_HIP_POLY2D_TRUNCATED 2
+#define TOAST_HIP_POLY2D_NOT_FINITE 3
+int toast_hip_filter_poly2d_max_order(void);
+/* Measurement aid (tools/bench_filters.py): while on, every toast_hip_filter_poly2d_dev call brackets its three phases
+ * with device events, waits for them and adds the times up.  The call returns the sums so far -- ms_out[3]: moments,
+ * solve, subtraction; may be NULL --, clears them and switches the timing on or off.  Off by default. */
+int toast_hip_filter_poly2d_profile(int on, double * ms_out /*host*/);
+int toast_hip_filter_poly2d_dev(
+    int64_t order, int64_t n_samp, const int32_t * signal_index /*host*/, double * d_signal,
+    const int32_t * flag_index /*host*/, uint8_t * d_det_flags, uint8_t det_flag_mask, const uint8_t * d_shared_flags,
+    uint8_t shared_flag_mask, uint8_t poly_flag_mask, const int32_t * det_group /*host*/, int64_t n_group,
+    const double * templates /*host*/, int64_t n_det, const int64_t * starts /*host*/, const int64_t * stops /*host*/,
+    int64_t n_interval, double * d_coeff, int32_t * d_status, int path, void * stream);
+/* ------------------------------------------------------------------------------------
  * SubHarmonic and Periodic destriping templates (device-resident buffers; host index and interval arrays).
  * The reference has no compiled kernel for either: both are NumPy, one detector and one view at a time
  * (src/toast/templates/subharmonic.py, periodic.py).  Here all detectors of an observation go in one call.
@@ -1015,6 +1053,13 @@ int toast_hip_fourier2d_add_prior_dev(
 int toast_hip_filter_polynomial(int64_t order, const uint8_t * flags, int64_t n_samp, double * const * signals,
                                 int64_t n_signal, const int64_t * starts, const int64_t * stops, int64_t n_scan,
                                 int use_accel);
+/* `filter_poly2D` with the reference's own host layouts (kernels_numpy.py:86-97): det_groups [n_det], templates
+ * [n_det][n_mode], signals [n_samp][n_det], masks [n_samp][n_det] (non-zero = good), coeff [n_samp][n_group][n_mode]
+ * (written).  Signals and masks are read only; they are transposed to the device kernels' [n_det][n_samp] on the
+ * way in. */
+int toast_hip_filter_poly2d(const int32_t * det_groups, const double * templates, const double * signals,
+                            const uint8_t * masks, double * coeff, int64_t n_samp, int64_t n_det, int64_t n_group,
+                            int64_t n_mode, int use_accel);
 int toast_hip_sum_detectors(const int64_t * det_index, const int64_t * flag_index, int64_t n_det,
                             const uint8_t * shared_flags, uint8_t shared_flag_mask, const double * det_data,
                             int64_t n_data_rows, const uint8_t * det_flags, int64_t n_flag_rows, uint8_t det_flag_mask,

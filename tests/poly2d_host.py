@@ -1,0 +1,418 @@
+"""Inputs and host restatements for the PolyFilter2D tests (tests/golden/poly2d.npz, tests/golden/make_golden_poly2d.py,
+tests/test_poly2d_host.py, tests/test_gpu_poly2d.py).  NumPy and the host-side data model only.
+
+* ``build_case`` rebuilds the inputs of a fixture case from hashes (tests/poly_filter_host.hashed_uniform), so the fixture
+  holds no input array: signals, detector and shared flags, row indices, groups, views, the engineered samples.
+* ``case_templates``: positions of ``synth.hex_focalplane``, groups, offsets, scale and templates as the reference's
+  operator builds them (src/toast/ops/polyfilter/polyfilter.py:176-266).
+* ``emulate``: the device algorithm (csrc/poly2d_filter.hip) in float64 NumPy with the device's order of operations --
+  moments in detector order, cyclic Jacobi with the same rotations and stopping rule, the xor-butterfly projections,
+  the thresholded solve, the subtraction and the flag update.
+* ``apply_coefficients``: what the reference's operator does with the coefficients of its kernel (polyfilter.py:345-381):
+  flag update and subtraction.  The fixture holds the reference kernel's output -- the coefficients --; the filtered
+  signal and the updated flags follow from them through this function.
+"""
+import numpy as np
+
+import poly_filter_host as H
+
+N_SAMP = 1400
+STARTS = np.array([3, 741], dtype=np.int64)
+STOPS = np.array([700, 1317 + 13], dtype=np.int64)
+DET_MASK, DET_OTHER = 2, 8           # the detector-flag bit that counts, and one the mask must ignore
+SHARED_MASK, SHARED_OTHER = 4, 1
+POLY_MASK = 16
+BAD_FRACTIONS = np.array([0.0, 0.05, 0.1, 0.3, 0.3, 0.8])
+RCOND = 1.0e-6
+OFF_TOL = 2.0 ** -60
+MAX_SWEEPS = 24
+BORDER = (0.5e-6, 2.0e-6)            # a system with an eigenvalue ratio in here may be solved at either rank
+MAX_EXCLUDED = 0.10
+
+# name -> order, n_det, n_group, permuted rows
+CASES = {
+    "o0_d7": dict(order=0, n_det=7, n_group=1, permute=False),
+    "o1_d7": dict(order=1, n_det=7, n_group=1, permute=False),
+    "o1_d19_g2": dict(order=1, n_det=19, n_group=2, permute=False),
+    "o2_d19": dict(order=2, n_det=19, n_group=1, permute=False),
+    "o2_d37_g2": dict(order=2, n_det=37, n_group=2, permute=True),
+    "o3_d37": dict(order=3, n_det=37, n_group=1, permute=False),
+    "o3_d64_g2": dict(order=3, n_det=64, n_group=2, permute=False),
+}
+# engineered samples, all inside the first view
+S_GROUP_FLAGGED, S_SHARED, S_ONE_GOOD, S_FEW_GOOD, S_ZERO, S_NAN_FLAGGED = 100, 150, 200, 256, 300, 350
+NAN_CASE = dict(order=1, n_det=7, n_samp=40, sample=17, det=2)
+
+
+def detector_groups(n_det, n_group):
+    """Pixel ``d // 2`` of the hex focal plane belongs to group ``pixel % n_group``: 19 detectors in two groups are 10 + 9."""
+    return ((np.arange(n_det) // 2) % n_group).astype(np.int32)
+
+
+def case_templates(n_det, n_group, order, fov_deg=10.0):
+    """-> (templates [n_det][(order + 1)^2], det_group, quats)."""
+    from toast_amd.data import detector_direction
+    from toast_amd.synth import hex_focalplane
+
+    quats, _ = hex_focalplane(n_det, fov_deg=fov_deg)
+    xy = np.array([detector_direction(q)[:2] for q in quats])
+    theta, phi = np.arcsin(xy[:, 0]), np.arcsin(xy[:, 1])
+    det_group = detector_groups(n_det, n_group)
+    for g in range(n_group):
+        members = np.flatnonzero(det_group == g)
+        t_off, p_off = 0, 0
+        for d in members:                     # summed one by one, like the reference
+            t_off += theta[d]
+            p_off += phi[d]
+        theta[members] -= t_off / members.size
+        phi[members] -= p_off / members.size
+    scale = 0.999 / max(np.amax(np.abs(theta)), np.amax(np.abs(phi)))
+    theta, phi = theta * scale, phi * scale
+    orders = np.arange(order + 1)
+    xo, yo = np.meshgrid(orders, orders, indexing="ij")
+    xo, yo = xo.ravel(), yo.ravel()
+    templates = np.array([theta[d] ** xo * phi[d] ** yo for d in range(n_det)])
+    return templates, det_group, quats
+
+
+def build_case(name, seed):
+    """Inputs of case ``name`` with flag seed ``seed`` (the generator raises it until the exclusion share holds)."""
+    cfg = CASES[name]
+    order, n_det, n_group = cfg["order"], cfg["n_det"], cfg["n_group"]
+    n_mode = (order + 1) ** 2
+    templates, det_group, quats = case_templates(n_det, n_group, order)
+    base = 7000 + 10 * list(CASES).index(name)
+    if cfg["permute"]:
+        # rows permuted inside larger buffers; two detector rows of each buffer are not listed
+        n_sig_rows, n_flag_rows = n_det + 4, n_det + 3
+        sig_rows = np.argsort(H.hashed_uniform(base + 1, n_sig_rows))[:n_det].astype(np.int32)
+        flag_rows = np.argsort(H.hashed_uniform(base + 2, n_flag_rows))[:n_det].astype(np.int32)
+    else:
+        n_sig_rows = n_flag_rows = n_det
+        sig_rows = flag_rows = np.arange(n_det, dtype=np.int32)
+    s = np.arange(N_SAMP)
+    signal = 6.0 + 2.0 * np.sin(s / 50.0)[None, :] + (H.hashed_uniform(base + 3, n_sig_rows * N_SAMP).reshape(n_sig_rows, N_SAMP) - 0.5) * np.sqrt(12.0)
+    frac = BAD_FRACTIONS[(H.hashed_uniform(seed, N_SAMP) * BAD_FRACTIONS.size).astype(int)]
+    det_flags = (H.hashed_uniform(seed + 1, n_flag_rows * N_SAMP).reshape(n_flag_rows, N_SAMP) < frac[None, :]).astype(np.uint8) * DET_MASK
+    det_flags |= (H.hashed_uniform(seed + 2, n_flag_rows * N_SAMP).reshape(n_flag_rows, N_SAMP) < 0.2).astype(np.uint8) * DET_OTHER
+    shared = (H.hashed_uniform(seed + 3, N_SAMP) < 0.03).astype(np.uint8) * SHARED_MASK
+    shared |= (H.hashed_uniform(seed + 4, N_SAMP) < 0.2).astype(np.uint8) * SHARED_OTHER
+    g0 = np.flatnonzero(det_group == 0)
+    engineered = [S_GROUP_FLAGGED, S_SHARED, S_ONE_GOOD, S_FEW_GOOD, S_ZERO, S_NAN_FLAGGED]
+    shared[engineered] &= ~np.uint8(SHARED_MASK)
+    shared[S_SHARED] |= SHARED_MASK
+    det_flags[flag_rows[g0], S_GROUP_FLAGGED] |= DET_MASK                      # nobody good in group 0
+    det_flags[flag_rows[g0], S_ONE_GOOD] |= DET_MASK
+    det_flags[flag_rows[g0[g0.size // 2]], S_ONE_GOOD] &= ~np.uint8(DET_MASK)   # exactly one good detector
+    if n_mode > 1:
+        n_few = min(n_mode - 1, g0.size - 1)                                     # 0 < n_good < n_mode
+        det_flags[flag_rows[g0], S_FEW_GOOD] |= DET_MASK
+        det_flags[flag_rows[g0[:n_few]], S_FEW_GOOD] &= ~np.uint8(DET_MASK)
+    signal[:, S_ZERO] = 0.0                                                     # every good signal exactly 0
+    det_flags[:, S_ZERO] &= ~np.uint8(DET_MASK)
+    det_flags[flag_rows[g0[0]], S_ZERO] |= DET_MASK
+    signal[sig_rows[g0[1]], S_NAN_FLAGGED] = np.nan                             # a NaN under a flag
+    det_flags[flag_rows[g0[1]], S_NAN_FLAGGED] |= DET_MASK
+    return dict(order=order, n_det=n_det, n_group=n_group, n_mode=n_mode, templates=templates, det_group=det_group,
+                quats=quats, signal=signal, det_flags=det_flags, shared=shared, sig_rows=sig_rows, flag_rows=flag_rows,
+                starts=STARTS, stops=STOPS, n_samp=N_SAMP)
+
+
+def build_nan_case():
+    """One tiny case with a NaN in a GOOD sample: that system gets zero coefficients and is flagged.  Its one view runs
+    past both ends of the observation and is clipped."""
+    cfg = NAN_CASE
+    templates, det_group, quats = case_templates(cfg["n_det"], 1, cfg["order"])
+    n = cfg["n_samp"]
+    signal = 3.0 + (H.hashed_uniform(7900, cfg["n_det"] * n).reshape(cfg["n_det"], n) - 0.5) * np.sqrt(12.0)
+    det_flags = (H.hashed_uniform(7901, cfg["n_det"] * n).reshape(cfg["n_det"], n) < 0.1).astype(np.uint8) * DET_MASK
+    det_flags[cfg["det"], cfg["sample"]] = 0
+    signal[cfg["det"], cfg["sample"]] = np.nan
+    rows = np.arange(cfg["n_det"], dtype=np.int32)
+    return dict(order=cfg["order"], n_det=cfg["n_det"], n_group=1, n_mode=4, templates=templates, det_group=det_group,
+                quats=quats, signal=signal, det_flags=det_flags, shared=np.zeros(n, dtype=np.uint8), sig_rows=rows,
+                flag_rows=rows, starts=np.array([-3], dtype=np.int64), stops=np.array([n + 13], dtype=np.int64), n_samp=n)
+
+
+def view_samples(case):
+    n = case["n_samp"]
+    return np.concatenate([np.arange(max(int(a), 0), min(int(b), n)) for a, b in zip(case["starts"], case["stops"])])
+
+
+def good_mask(case, samples=None):
+    """[n_det][samples]: shared flag clear and detector flag clear."""
+    samples = view_samples(case) if samples is None else samples
+    good = (case["det_flags"][case["flag_rows"]][:, samples] & DET_MASK) == 0
+    return good & ((case["shared"][samples] & SHARED_MASK) == 0)[None, :]
+
+
+def gram_spectra(case):
+    """Singular values [n_view_samples][n_group][n_mode] of A = sum_good T T^T: the reference's own spectra."""
+    good = good_mask(case).astype(np.float64)
+    t = case["templates"]
+    out = np.zeros((good.shape[1], case["n_group"], case["n_mode"]))
+    for g in range(case["n_group"]):
+        m = np.flatnonzero(case["det_group"] == g)
+        a = np.einsum("ds,di,dj->sij", good[m], t[m], t[m])
+        out[:, g] = np.linalg.svd(a, compute_uv=False)
+    return out
+
+
+def excluded_systems(case):
+    """bool [n_view_samples][n_group]: an eigenvalue ratio inside BORDER."""
+    sv = gram_spectra(case)
+    lmax = sv[..., :1]
+    with np.errstate(invalid="ignore", divide="ignore"):
+        ratio = np.where(lmax > 0, sv / np.where(lmax > 0, lmax, 1.0), 0.0)
+    return np.any((ratio >= BORDER[0]) & (ratio <= BORDER[1]), axis=2)
+
+
+# ------------------------------------------------------------------ the device algorithm on the host
+def _moment_basis(templates, order):
+    no, nm = order + 1, 2 * order + 1
+    mom = np.zeros((templates.shape[0], nm * nm))
+    for p in range(nm):
+        for q in range(nm):
+            i1, j1 = min(p, order), min(q, order)
+            mom[:, p * nm + q] = templates[:, i1 * no + j1] * templates[:, (p - i1) * no + (q - j1)]
+    return mom
+
+
+def jacobi_solve(moments, proj, order):
+    """c [S][n_mode], status [S] from the packed systems, with the operations of k_p2d_solve in their order."""
+    no, nm = order + 1, 2 * order + 1
+    n = no * no
+    w_team = 1 if n == 1 else (4 if n == 4 else 16)
+    n_sys = moments.shape[0]
+    r = np.arange(n)
+    idx = ((r // no)[:, None] + (r // no)[None, :]) * nm + ((r % no)[:, None] + (r % no)[None, :])
+    a = moments[:, idx].copy()
+    v = np.broadcast_to(np.eye(n), (n_sys, n, n)).copy()
+    done = np.zeros(n_sys, dtype=bool)
+    eye = np.eye(n, dtype=bool)
+    sweeps = 0
+    if n > 1:
+        for _ in range(MAX_SWEEPS):
+            absa = np.abs(a)
+            diag = np.max(absa[:, eye], axis=1)
+            off = np.max(np.where(eye[None], 0.0, absa), axis=(1, 2))
+            done |= ~(off > OFF_TOL * diag)
+            if done.all():
+                break
+            sweeps += 1
+            for p in range(n - 1):
+                for q in range(p + 1, n):
+                    apq = a[:, p, q]
+                    k = np.flatnonzero(~done & (apq != 0.0))
+                    if k.size == 0:
+                        continue
+                    app, aqq, apq = a[k, p, p], a[k, q, q], apq[k]
+                    with np.errstate(over="ignore", invalid="ignore", divide="ignore"):
+                        theta = (aqq - app) / (2.0 * apq)
+                        t = np.where(theta >= 0.0, 1.0, -1.0) / (np.abs(theta) + np.sqrt(theta * theta + 1.0))
+                    cs = 1.0 / np.sqrt(t * t + 1.0)
+                    sn = t * cs
+                    cs, sn = cs[:, None], sn[:, None]
+                    for mat in (a, v):
+                        cp, cq = mat[k, :, p].copy(), mat[k, :, q].copy()
+                        mat[k, :, p] = cs * cp - sn * cq
+                        mat[k, :, q] = sn * cp + cs * cq
+                    rp, rq = a[k, p, :].copy(), a[k, q, :].copy()
+                    a[k, p, :] = cs * rp - sn * rq
+                    a[k, q, :] = sn * rp + cs * rq
+                    a[k, p, q] = 0.0
+                    a[k, q, p] = 0.0
+    lam = a[:, eye]
+    lmax = np.max(lam, axis=1) if n > 0 else np.zeros(n_sys)
+    lmax = np.maximum(lmax, 0.0)
+    finite = np.all(np.abs(proj) <= np.finfo(np.float64).max, axis=1)
+    b = np.where(finite[:, None], proj, 0.0)
+    part = np.zeros((n_sys, w_team, n))
+    part[:, :n, :] = v * b[:, :, None]                       # [system][lane r][eigenvector i]
+    lanes = np.arange(w_team)
+    o = w_team // 2
+    while o >= 1:
+        part = part + part[:, lanes ^ o, :]
+        o //= 2
+    y = part[:, 0, :]
+    keep = (lmax[:, None] > 0.0) & (lam > RCOND * lmax[:, None])
+    with np.errstate(invalid="ignore", divide="ignore"):
+        wgt = np.where(keep, y / np.where(keep, lam, 1.0), 0.0)
+    c = np.zeros((n_sys, n))
+    for i in range(n):
+        c += v[:, :, i] * wgt[:, i:i + 1]
+    c[~finite] = 0.0
+    rank = np.count_nonzero(keep, axis=1)
+    status = np.where(~finite, 3, np.where(rank == 0, 1, np.where(rank < n, 2, 0))).astype(np.int32)
+    return c, status, sweeps
+
+
+def emulate(case, with_flags=True):
+    """-> (signal, det_flags, coeff [n_samp][n_group][n_mode], status [n_samp][n_group], sweeps): the device algorithm on
+    copies of the case's buffers."""
+    order, n_group, n_mode = case["order"], case["n_group"], case["n_mode"]
+    nm2 = (2 * order + 1) ** 2
+    t = case["templates"]
+    mom = _moment_basis(t, order)
+    signal = case["signal"].copy()
+    det_flags = case["det_flags"].copy()
+    samples = view_samples(case)
+    good = good_mask(case, samples) if with_flags else \
+        np.broadcast_to(((case["shared"][samples] & SHARED_MASK) == 0)[None, :], (case["n_det"], samples.size)).copy()
+    coeff = np.zeros((case["n_samp"], n_group, n_mode))
+    status = np.full((case["n_samp"], n_group), -1, dtype=np.int32)
+    most = 0
+    for g in range(n_group):
+        members = np.flatnonzero(case["det_group"] == g)
+        m_acc = np.zeros((samples.size, nm2))
+        b_acc = np.zeros((samples.size, n_mode))
+        for d in members:
+            sel = good[d][:, None]
+            val = signal[case["sig_rows"][d], samples]
+            m_acc += np.where(sel, mom[d][None, :], 0.0)
+            with np.errstate(invalid="ignore"):
+                b_acc += np.where(sel, t[d][None, :] * val[:, None], 0.0)
+        c, st, sweeps = jacobi_solve(m_acc, b_acc, order)
+        most = max(most, sweeps)
+        coeff[samples, g] = c
+        status[samples, g] = st
+        zero = np.all(c == 0.0, axis=1)
+        for d in members:
+            fit = np.zeros(samples.size)
+            for m in range(n_mode):
+                fit += c[:, m] * t[d, m]
+            upd = good[d] & ~zero
+            row = case["sig_rows"][d]
+            signal[row, samples[upd]] = signal[row, samples[upd]] - fit[upd]
+            if with_flags:
+                det_flags[case["flag_rows"][d], samples[zero]] |= np.uint8(POLY_MASK)
+    return signal, det_flags, coeff, status, most
+
+
+# ------------------------------------------------------------------ the reference's operator around its kernel
+def reference_inputs(case, first, last):
+    """(signals [n][n_det], masks [n][n_det] uint8) of one view as polyfilter.py:306-327 builds them.  A NaN under a flag
+    would become NaN * 0 = NaN there and poison the whole system: the flagged entries are set to 0 here."""
+    samples = np.arange(first, last)
+    mask = good_mask(case, samples)
+    sig = case["signal"][case["sig_rows"]][:, samples]
+    return np.ascontiguousarray(np.where(mask, sig, 0.0).T), np.ascontiguousarray(mask.T.astype(np.uint8))
+
+
+def apply_coefficients(case, coeff, with_flags=True):
+    """polyfilter.py:345-381 for coefficients [n_samp][n_group][n_mode]: -> (signal, det_flags, fit [n_det][n_samp]).
+    ``fit`` is np.sum(coeff * templates, 1) for every detector of the group, flagged or not."""
+    signal = case["signal"].copy()
+    det_flags = case["det_flags"].copy()
+    samples = view_samples(case)
+    good = good_mask(case, samples) if with_flags else \
+        np.broadcast_to(((case["shared"][samples] & SHARED_MASK) == 0)[None, :], (case["n_det"], samples.size))
+    fit = np.zeros((case["n_det"], case["n_samp"]))
+    for d in range(case["n_det"]):
+        g = case["det_group"][d]
+        f = np.sum(coeff[samples, g] * case["templates"][d], 1)
+        fit[d, samples] = f
+        row = case["sig_rows"][d]
+        signal[row, samples[good[d]]] -= f[good[d]]
+        if with_flags:
+            zero = np.all(coeff[samples, g] == 0, axis=1)
+            det_flags[case["flag_rows"][d], samples[zero]] |= np.uint8(POLY_MASK)
+    return signal, det_flags, fit
+
+
+def compared(case, excluded):
+    """bool [n_det][n_samp]: detector-samples of the systems that take part in the value comparison."""
+    samples = view_samples(case)
+    out = np.zeros((case["n_det"], case["n_samp"]), dtype=bool)
+    for d in range(case["n_det"]):
+        out[d, samples] = ~excluded[:, case["det_group"][d]]
+    return out
+
+
+def listed_signal(case, buffer):
+    """The listed detector rows of a signal buffer, in detector order."""
+    return buffer[case["sig_rows"]]
+
+
+def load_fixture():
+    import os
+
+    z = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "poly2d.npz"), allow_pickle=False)
+    return {k: z[k] for k in z.files}
+
+
+def fixture_case(fix, name):
+    """-> (case, reference coefficients [n_samp][n_group][n_mode], excluded [n_view_samples][n_group], bounds dict)."""
+    case = build_case(name, int(fix[f"{name}_seed"]))
+    samples = view_samples(case)
+    coeff = np.zeros((case["n_samp"], case["n_group"], case["n_mode"]))
+    coeff[samples] = fix[f"{name}_coeff"]
+    excluded = np.unpackbits(fix[f"{name}_excluded"])[:samples.size * case["n_group"]].reshape(samples.size, case["n_group"]).astype(bool)
+    bounds = dict(zip(("filtered", "fit", "coeff"), fix[f"{name}_bounds"]))
+    return case, coeff, excluded, bounds
+
+
+# ------------------------------------------------------------------ the checks of every implementation
+def check_result(case, ref_coeff, excluded, bounds, got_signal, got_flags, got_coeff, with_flags=True, label=""):
+    """The checks every implementation has to pass against the reference's coefficients."""
+    ref_sig, ref_flags, ref_fit = apply_coefficients(case, ref_coeff, with_flags=with_flags)
+    samples = view_samples(case)
+    rows = case["sig_rows"]
+    good = np.zeros((case["n_det"], case["n_samp"]), dtype=bool)
+    good[:, samples] = good_mask(case) if with_flags else ((case["shared"][samples] & SHARED_MASK) == 0)[None, :]
+    cmp = compared(case, excluded)
+    # flags: equal on ALL systems, and nothing but POLY_MASK ever changes
+    if got_flags is not None:
+        assert np.array_equal(got_flags, ref_flags if with_flags else case["det_flags"]), label
+    # finiteness and untouched samples on all systems
+    assert np.array_equal(np.isnan(got_signal), np.isnan(case["signal"])), label
+    untouched = np.ones(case["signal"].shape, dtype=bool)
+    untouched[np.ix_(rows, samples)] = ~good[:, samples]
+    assert np.array_equal(got_signal[untouched].view(np.uint64), case["signal"][untouched].view(np.uint64)), label
+    assert np.all(np.isfinite(got_coeff)), label
+    outside = np.ones(case["n_samp"], dtype=bool)
+    outside[samples] = False
+    assert np.all(got_coeff[outside] == 0), label
+    # values on the compared systems
+    sel = cmp & good
+    d_sig = np.nanmax(np.abs(got_signal[rows][sel] - ref_sig[rows][sel]))
+    _, _, got_fit = apply_coefficients(case, got_coeff, with_flags=with_flags)
+    d_fit = np.max(np.abs(got_fit[cmp] - ref_fit[cmp]))
+    d_coeff = np.max(np.abs(got_coeff[samples] - ref_coeff[samples])[~excluded])
+    print(f"{label}: filtered {d_sig:.3e} / {bounds['filtered']:.3e}, fit {d_fit:.3e} / {bounds['fit']:.3e}, "
+          f"coeff {d_coeff:.3e} / {bounds['coeff']:.3e}")
+    assert d_sig <= bounds["filtered"], label
+    assert d_fit <= bounds["fit"], label
+    assert d_coeff <= bounds["coeff"], label
+
+
+# ------------------------------------------------------------------ the same inputs as an observation
+VIEW = "scan"
+GROUP_KEY = "wafer"
+OPERATOR_TRAITS = dict(det_flag_mask=DET_MASK, shared_flag_mask=SHARED_MASK, poly_flag_mask=POLY_MASK, det_mask=1,
+                       view=VIEW)
+
+
+def build_observation(case):
+    """-> toast_amd.data.Data with one observation holding the listed rows of ``case`` in detector order; the focal
+    plane carries the column GROUP_KEY ("w0", "w1", ...)."""
+    from toast_amd.data import Data, Focalplane, Observation, Telescope, defaults
+
+    dets = [f"D{k:03d}" for k in range(case["n_det"])]
+    fp = Focalplane(dets, case["quats"], sample_rate=10.0, columns={GROUP_KEY: [f"w{g}" for g in case["det_group"]]})
+    data = Data()
+    n = case["n_samp"]
+    ob = Observation(data.comm, Telescope("tele", fp), n, name="obs0", detectors=dets)
+    ob.set_times(np.arange(n) / 10.0)
+    ob.shared.create(defaults.shared_flags, case["shared"].copy())
+    ob.intervals.create(VIEW, [(max(int(a), 0), min(int(b), n)) for a, b in zip(case["starts"], case["stops"])])
+    ob.detdata.create(defaults.det_data, dtype=np.float64)
+    ob.detdata.create(defaults.det_flags, dtype=np.uint8)
+    ob.detdata[defaults.det_data].data[:] = case["signal"][case["sig_rows"]]
+    ob.detdata[defaults.det_flags].data[:] = case["det_flags"][case["flag_rows"]]
+    data.obs.append(ob)
+    return data
+
+
+def operator_traits(case):
+    return dict(OPERATOR_TRAITS, order=case["order"], focalplane_key=GROUP_KEY if case["n_group"] > 1 else None)

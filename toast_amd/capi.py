@@ -1418,6 +1418,44 @@ class _Dev:
             _i64(n_samp), _p(si), _p(d_signal), _p(fi), _p(d_det_flags), _u8(det_flag_mask), _p(d_shared_flags),
             _u8(shared_flag_mask), _i64(si.size), _p(d_mean), _p(d_hits), _p(stream)))
 
+    # ---- PolyFilter2D kernels (csrc/poly2d_filter.hip)
+    POLY2D_SOLVED, POLY2D_NO_GOOD, POLY2D_TRUNCATED, POLY2D_NOT_FINITE = 0, 1, 2, 3
+    POLY2D_PATH_RULE, POLY2D_PATH_THREE_KERNELS = 0, 1
+    POLY2D_PATHS = (POLY2D_PATH_RULE, POLY2D_PATH_THREE_KERNELS)    # every value ``path`` takes
+
+    def filter_poly2d_max_order(self):
+        """Largest ``order`` the PolyFilter2D kernels take; beyond it the operator runs its host path."""
+        return int(real_lib().toast_hip_filter_poly2d_max_order())
+
+    def filter_poly2d_profile(self, on):
+        """Switch the per-phase device-event timing of ``filter_poly2d`` on or off; returns the milliseconds summed since
+        the last call as ``[moments, solve, subtract]`` and clears them."""
+        ms = np.zeros(3)
+        _check(real_lib().toast_hip_filter_poly2d_profile(C.c_int(1 if on else 0), _p(ms)))
+        return ms
+
+    def filter_poly2d(self, order, n_samp, signal_index, d_signal, flag_index, d_det_flags, det_flag_mask,
+                      d_shared_flags, shared_flag_mask, poly_flag_mask, det_group, n_group, templates, starts, stops,
+                      d_coeff=0, d_status=0, path=0, stream=0):
+        """``templates`` host float64 [n_det][(order + 1)^2], ``det_group`` host int32 [n_det]; ``stops`` exclusive;
+        ``d_coeff`` float64 [n_samp][n_group][n_mode] and ``d_status`` int32 [n_samp][n_group] are optional."""
+        si = self._small(signal_index, np.int32)
+        fi = self._small(flag_index if flag_index is not None else np.zeros(si.size), np.int32)
+        dg = self._small(det_group, np.int32)
+        tm = np.ascontiguousarray(templates, dtype=np.float64)
+        st = self._small(starts, np.int64)
+        sp = self._small(stops, np.int64)
+        if st.size != sp.size:
+            raise RuntimeError("Starts / stops buffer sizes are not consistent.")
+        if fi.size != si.size or dg.size != si.size:
+            raise RuntimeError("filter_poly2d: one flag row and one group per signal row")
+        if tm.shape != (si.size, (int(order) + 1) ** 2):
+            raise RuntimeError("filter_poly2d: templates must be [n_det][(order + 1)^2]")
+        _check(lib().toast_hip_filter_poly2d_dev(
+            _i64(order), _i64(n_samp), _p(si), _p(d_signal), _p(fi), _p(d_det_flags), _u8(det_flag_mask),
+            _p(d_shared_flags), _u8(shared_flag_mask), _u8(poly_flag_mask), _p(dg), _i64(n_group), _p(tm), _i64(si.size),
+            _p(st), _p(sp), _i64(st.size), _p(d_coeff), _p(d_status), C.c_int(int(path)), _p(stream)))
+
     # ---- SubHarmonic / Periodic template kernels (csrc/template_basis.hip)
     PERIODIC_PATH_RULE, PERIODIC_PATH_LDS, PERIODIC_PATH_ATOMIC = 0, 1, 2
 

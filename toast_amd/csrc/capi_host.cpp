@@ -227,6 +227,40 @@ int toast_hip_filter_polynomial(int64_t order, const uint8_t * flags, int64_t n_
     });
 }
 
+int toast_hip_filter_poly2d(const int32_t * det_groups, const double * templates, const double * signals,
+                            const uint8_t * masks, double * coeff, int64_t n_samp, int64_t n_det, int64_t n_group,
+                            int64_t n_mode, int use_accel) {
+    return guarded([&] {
+        if (n_samp <= 0 || n_det <= 0 || n_group <= 0) return;
+        int64_t order = 0;
+        while ((order + 1) * (order + 1) < n_mode) ++order;
+        if ((order + 1) * (order + 1) != n_mode) fail_arg("filter_poly2D: the number of modes must be (order + 1)^2");
+        Call c(use_accel);
+        // the reference's [n_samp][n_det] layouts become the kernels' detector-major rows (a change of layout, no
+        // arithmetic); a mask of 0 becomes a detector flag
+        std::vector<double> sig((size_t)(n_det * n_samp));
+        std::vector<uint8_t> flags((size_t)(n_det * n_samp));
+        std::vector<int32_t> rows((size_t)n_det);
+        for (int64_t d = 0; d < n_det; ++d) {
+            rows[(size_t)d] = (int32_t)d;
+            for (int64_t s = 0; s < n_samp; ++s) {
+                sig[(size_t)(d * n_samp + s)] = signals[s * n_det + d];
+                flags[(size_t)(d * n_samp + s)] = masks[s * n_det + d] ? 0 : 1;
+            }
+        }
+        // temporaries that are not copied back: the reference's kernel leaves signals and masks alone
+        double * d_sig = const_cast<double *>(c.st.temp_in(sig.data(), sig.size()));
+        const uint8_t * d_flags = c.st.temp_in(flags.data(), flags.size());
+        double * d_coeff = c.st.temp_inout(coeff, (size_t)(n_samp * n_group * n_mode));
+        const int64_t start = 0, stop = n_samp;
+        // no flag update (the flag pointer of the update is the operator's business): poly_flag_mask = 0
+        c.check(toast_hip_filter_poly2d_dev(order, n_samp, rows.data(), d_sig, rows.data(), const_cast<uint8_t *>(d_flags), 1,
+                                            nullptr, 0, 0, det_groups, n_group, templates, n_det, &start, &stop, 1, d_coeff,
+                                            nullptr, 0, c.stream));
+        c.st.finish();
+    });
+}
+
 int toast_hip_sum_detectors(const int64_t * det_index, const int64_t * flag_index, int64_t n_det,
                             const uint8_t * shared_flags, uint8_t shared_flag_mask, const double * det_data,
                             int64_t n_data_rows, const uint8_t * det_flags, int64_t n_flag_rows, uint8_t det_flag_mask,

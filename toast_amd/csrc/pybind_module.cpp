@@ -449,6 +449,22 @@ PYBIND11_MODULE(_libtoast_hip, m) {
         check(toast_hip_filter_polynomial(order, fl, n_samp, sigs.data(), (int64_t)sigs.size(), st, sp, n_scan, use_accel));
     }, py::arg("order"), py::arg("flags"), py::arg("signals"), py::arg("starts"), py::arg("stops"),
        py::arg("use_accel") = false);
+    // ---- filter_poly2D (tod_filter.cpp, `filter_poly2D`; kernels_numpy.py:86-97)
+    m.def("filter_poly2D", [](py::buffer det_groups, py::buffer templates, py::buffer signals, py::buffer masks,
+                              py::buffer coeff, bool use_accel) {
+        Shape s(3);
+        int32_t * groups = extract<int32_t>(det_groups, "det_groups", 1, s, {-1});
+        const int64_t n_det = s[0];
+        double * tm = extract<double>(templates, "templates", 2, s, {n_det, -1});
+        const int64_t n_mode = s[1];
+        double * sig = extract<double>(signals, "signals", 2, s, {-1, n_det});
+        const int64_t n_samp = s[0];
+        uint8_t * mk = extract<uint8_t>(masks, "masks", 2, s, {n_samp, n_det});
+        double * cf = extract<double>(coeff, "coeff", 3, s, {n_samp, -1, n_mode});
+        const int64_t n_group = s[1];
+        check(toast_hip_filter_poly2d(groups, tm, sig, mk, cf, n_samp, n_det, n_group, n_mode, use_accel));
+    }, py::arg("det_groups"), py::arg("templates"), py::arg("signals"), py::arg("masks"), py::arg("coeff"),
+       py::arg("use_accel") = false);
     m.def("sum_detectors", [](py::array_t<int64_t, py::array::c_style | py::array::forcecast> det_indx,
                               py::array_t<int64_t, py::array::c_style | py::array::forcecast> flag_indx,
                               py::buffer shared_flags, uint8_t shared_flag_mask, py::buffer det_data, py::buffer det_flags,

@@ -22,7 +22,7 @@ from .noise_estimation import NoiseEstim
 from .noise_filter import NoiseFilter
 from .operator import Operator
 from .pipeline import Pipeline
-from .poly_filter import CommonModeFilter, PolyFilter
+from .poly_filter import CommonModeFilter, PolyFilter, PolyFilter2D
 from .pointing import BuildPixelDistribution, PixelsHealpix, PointingDetectorSimple, StokesWeights
 from .sim_ground import SimGround
 from .sim_tod_noise import SimNoise

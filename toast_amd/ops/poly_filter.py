@@ -1,11 +1,19 @@
-"""PolyFilter and CommonModeFilter: the two timestream filters every ground pipeline runs before
-GroundFilter and map-making (reference: src/toast/ops/polyfilter/polyfilter.py:433-646 and :648-1015).
+"""PolyFilter, PolyFilter2D and CommonModeFilter: the timestream filters every ground pipeline runs before GroundFilter
+and map-making (reference: src/toast/ops/polyfilter/polyfilter.py:30-431, :433-646 and :648-1015).
 
 * ``PolyFilter`` fits and subtracts a low-order Legendre polynomial per detector and per interval of a view.  The
   reference groups detectors with identical flags and hands each group to ``filter_polynomial`` on the host
   (polyfilter.py:556-602).  Here all detectors and all intervals of an observation go through one call of
   toast_hip_filter_polynomial_dev (csrc/poly_filter.hip); the shared and the detector flags stay separate arrays
   and are combined inside the kernel.
+* ``PolyFilter2D`` fits and subtracts, at every time stamp and per detector group (wafer), a low-order 2-D polynomial
+  across the focal plane.  The reference redistributes the observation by samples, transposes signal and masks to
+  [n_samp][n_det] on the host, calls ``filter_poly2D`` per view and copies everything back (polyfilter.py:132-404).
+  Every process holds whole observations with all their detectors in this data model, so nothing is redistributed, and
+  one call of toast_hip_filter_poly2d_dev (csrc/poly2d_filter.hip) per observation sweeps the detector-major arrays in
+  place over all intervals of the view: moments, a Jacobi eigen-solve truncated at 1e-6 like DGELSS, subtraction and
+  the flag update.  Orders above 3, ``use_accel=False`` and a process without a device take a NumPy host path
+  (``poly2d_host``: ``np.linalg.lstsq(A, b, rcond=1e-6)`` per system).
 * ``CommonModeFilter`` removes the focal-plane common mode at every time stamp: ``sum_detectors`` /
   ``subtract_mean`` of the reference (polyfilter.py:926-977) are toast_hip_sum_detectors_dev /
   toast_hip_subtract_mean_dev, fused into toast_hip_common_mode_subtract_dev.  Every process holds whole observations
@@ -13,9 +21,10 @@ GroundFilter and map-making (reference: src/toast/ops/polyfilter/polyfilter.py:4
   sits between the sum and the subtraction and the fused form is the one ``regress=False`` uses.  ``regress=True``
   takes the sum and the mean from the separate kernels and reuses the template-regression kernels of GroundFilter.
 
-Not reproduced: ``PolyFilter2D``; ``CommonModeFilter.redistribute`` and ``.plot``; a
-``det_data`` that is not float64 (the reference converts it to float64 and back, polyfilter.py:561-566; here it
-raises).
+Not reproduced: ``CommonModeFilter.redistribute`` and ``.plot``; a ``det_data`` that is not
+float64 (the reference converts it to float64 and back, polyfilter.py:561-566; here it raises).  ``PolyFilter2D``: the
+reference's summation order (results agree to a bound, not bit for bit), and a NaN or an infinity among the good signals
+of a system, which the reference hands to LAPACK: here that system gets zero coefficients and is flagged.
 """
 
 import re
@@ -31,7 +40,7 @@ from ..accel import (
     accel_enabled,
     native,
 )
-from ..data import defaults
+from ..data import defaults, detector_direction
 from ..traits import Bool, Int, TraitError, Unicode
 from .operator import Operator
 
@@ -205,6 +214,234 @@ class PolyFilter(Operator):
             req["shared"].append(self.shared_flags)
         if self.det_flags is not None:
             req["detdata"].append(self.det_flags)
+        return req
+
+    def _provides(self):
+        return {"meta": [], "shared": [], "detdata": []}
+
+
+def poly2d_templates(positions, groups, order):
+    """Templates [n_det][(order + 1)^2] of polyfilter.py:227-266.  ``positions`` [n_det][2]: theta, phi of every
+    detector; ``groups``: lists of detector indices, in the order the reference walks its ``groups`` dict.  The mean of
+    every group is removed (summed detector by detector, like the reference), one scale 0.999 / max(|theta|max, |phi|max)
+    over all groups, then theta^xorders * phi^yorders with meshgrid(..., indexing="ij")."""
+    pos = np.array(positions, dtype=np.float64)
+    for members in groups:
+        theta_offset, phi_offset = 0, 0
+        for d in members:
+            theta_offset += pos[d, 0]
+            phi_offset += pos[d, 1]
+        theta_offset /= len(members)
+        phi_offset /= len(members)
+        for d in members:
+            pos[d] = [pos[d, 0] - theta_offset, pos[d, 1] - phi_offset]
+    scale = 0.999 / max(np.amax(np.abs(pos[:, 0])), np.amax(np.abs(pos[:, 1])))
+    orders = np.arange(order + 1)
+    xorders, yorders = np.meshgrid(orders, orders, indexing="ij")
+    xorders, yorders = xorders.ravel(), yorders.ravel()
+    templates = np.zeros((pos.shape[0], (order + 1) ** 2))
+    for d in range(pos.shape[0]):
+        theta, phi = pos[d, 0] * scale, pos[d, 1] * scale
+        templates[d] = theta ** xorders * phi ** yorders
+    return templates
+
+
+def poly2d_host(templates, det_group, n_group, signal, sig_rows, det_flags, flag_rows, det_flag_mask, shared_flags,
+                shared_flag_mask, poly_flag_mask, starts, stops):
+    """The host path of PolyFilter2D, in place on ``signal`` [rows][n_samp] and ``det_flags`` (may be None).  Per sample
+    of every [start, stop) and per group: A = sum_good T T^T, b = sum_good T s, c = lstsq(A, b, rcond=1e-6) -- the
+    reference's kernel (kernels_numpy.py:86-97) --; all c == 0 flags the group's detectors with ``poly_flag_mask``;
+    otherwise the fit is subtracted from the good detectors.  A system whose b is not finite gets c = 0.
+    Returns the coefficients [n_samp][n_group][n_mode] (zero outside the intervals)."""
+    n_samp = signal.shape[1]
+    n_mode = templates.shape[1]
+    det_group = np.asarray(det_group)
+    coeff = np.zeros((n_samp, n_group, n_mode))
+    members = [np.flatnonzero(det_group == g) for g in range(n_group)]
+    for start, stop in zip(starts, stops):
+        start, stop = max(int(start), 0), min(int(stop), n_samp)
+        for s in range(start, stop):
+            shared_ok = shared_flags is None or (int(shared_flags[s]) & shared_flag_mask) == 0
+            for g, dets in enumerate(members):
+                if dets.size == 0:
+                    continue
+                if det_flags is not None:
+                    good = (det_flags[flag_rows[dets], s] & det_flag_mask) == 0
+                else:
+                    good = np.ones(dets.size, dtype=bool)
+                good &= shared_ok
+                used = dets[good]
+                if used.size > 0:
+                    t = templates[used]
+                    values = signal[sig_rows[used], s]
+                    proj = t.T @ values
+                    if np.all(np.isfinite(proj)):
+                        c = np.linalg.lstsq(t.T @ t, proj, rcond=1.0e-6)[0]
+                        coeff[s, g] = c
+                if np.all(coeff[s, g] == 0):
+                    if det_flags is not None:
+                        det_flags[flag_rows[dets], s] |= det_flags.dtype.type(poly_flag_mask)
+                elif used.size > 0:
+                    signal[sig_rows[used], s] -= templates[used] @ coeff[s, g]
+    return coeff
+
+
+class PolyFilter2D(Operator):
+    """Operator to regress out 2D polynomials across the focal plane.
+
+    ``coefficients[obs.name]`` ([n_samp, n_group, (order + 1)^2], zero outside the view), ``flagged_samples[obs.name]``
+    (per group, the number of samples of the view whose coefficients are all zero: they carry ``poly_flag_mask``) and
+    ``filtered_detectors[obs.name]`` / ``groups[obs.name]`` (group keys, sorted) describe the last call.  ``det_data`` must
+    be float64.  Orders 0 to 3 run on the device; larger orders, ``use_accel=False`` and a process without a device run
+    the NumPy host path.  A system with a NaN or an infinity among its good signals gets zero coefficients (and is
+    flagged); the reference passes it to LAPACK."""
+
+    API = Int(0, help="Internal interface version for this operator")
+    times = Unicode(defaults.times, help="Observation shared key for timestamps")
+    det_data = Unicode(defaults.det_data, help="Observation detdata key apply filtering to")
+    pattern = Unicode(".*", allow_none=True,
+                      help="Regex pattern to match against detector names. Only detectors that match the pattern are filtered.")
+    order = Int(1, allow_none=False, help="Polynomial order")
+    det_mask = Int(defaults.det_mask_invalid | defaults.det_mask_processing, help="Bit mask value for per-detector flagging")
+    det_flags = Unicode(defaults.det_flags, allow_none=True, help="Observation detdata key for flags to use")
+    det_flag_mask = Int(defaults.det_mask_invalid | defaults.det_mask_processing,
+                        help="Bit mask value for detector sample flagging")
+    poly_flag_mask = Int(defaults.det_mask_invalid, help="Bit mask value for samples that fail to filter")
+    shared_flags = Unicode(defaults.shared_flags, allow_none=True, help="Observation shared key for telescope flags to use")
+    shared_flag_mask = Int(defaults.shared_mask_invalid, help="Bit mask value for optional shared flagging")
+    view = Unicode(None, allow_none=True, help="Use this view of the data in all observations")
+    focalplane_key = Unicode(None, allow_none=True, help="Which focalplane key to match")
+
+    def _validate_det_mask(self, value):
+        return _positive("Det mask", value)
+
+    def _validate_shared_flag_mask(self, value):
+        return _positive("Shared flag mask", value)
+
+    def _validate_det_flag_mask(self, value):
+        return _positive("Det flag mask", value)
+
+    def __init__(self, **kwargs):
+        super().__init__(**kwargs)
+        self.coefficients = {}
+        self.flagged_samples = {}
+        self.filtered_detectors = {}
+        self.groups = {}
+
+    def _setup(self, obs, pat):
+        """-> (detectors, det_group, group keys, templates) of one observation: polyfilter.py:163-266."""
+        dets = [d for d in obs.select_local_detectors(None, flagmask=self.det_mask) if pat.match(d) is not None]
+        if len(dets) == 0:
+            return dets, None, [], None
+        focalplane = obs.telescope.focalplane
+        positions = []
+        for det in dets:
+            x, y, z = detector_direction(focalplane[det]["quat"])
+            positions.append(np.arcsin([x, y]))
+        if self.focalplane_key is None:
+            keys, by_key = [None], {None: list(range(len(dets)))}
+        else:
+            by_key = {}
+            for i, det in enumerate(dets):
+                if self.focalplane_key not in focalplane[det]:
+                    raise RuntimeError(f"Cannot divide detectors by {self.focalplane_key} because it is not defined in "
+                                       "the focalplane detector data.")
+                by_key.setdefault(focalplane[det][self.focalplane_key], []).append(i)
+            keys = sorted(by_key)
+        det_group = np.zeros(len(dets), dtype=np.int32)
+        for g, key in enumerate(keys):
+            det_group[by_key[key]] = g
+        # the offsets are taken in the order the groups were met, the group numbers in sorted order (polyfilter.py:211-243)
+        templates = poly2d_templates(positions, list(by_key.values()), self.order)
+        return dets, det_group, keys, templates
+
+    def _exec(self, data, detectors=None, use_accel=None, **kwargs):
+        from .. import capi
+
+        if detectors is not None:
+            raise RuntimeError("PolyFilter2D cannot be run on subsets of detectors")
+        if self.order < 0:
+            raise TraitError("PolyFilter2D: order should not be negative")
+        pat = re.compile(self.pattern if self.pattern is not None else ".*")
+        on_device = accel_enabled() and (use_accel is None or use_accel)
+        if on_device and self.order > capi.dev.filter_poly2d_max_order():
+            on_device = False
+        self.coefficients, self.flagged_samples, self.filtered_detectors, self.groups = {}, {}, {}, {}
+        n_mode = (self.order + 1) ** 2
+        for obs in data.obs:
+            # the reference gathers all detectors of a sample on one process first; observations of this data model
+            # hold them all already and carry no column communicator
+            if getattr(obs, "comm_col", None) is not None:
+                raise NotImplementedError("PolyFilter2D: detectors of one observation spread over several processes "
+                                          "(obs.comm_col) are not supported")
+            dets, det_group, keys, templates = self._setup(obs, pat)
+            self.filtered_detectors[obs.name] = dets
+            self.groups[obs.name] = keys
+            if len(dets) == 0:
+                continue
+            dd = obs.detdata[self.det_data]
+            if dd.dtype != np.dtype(np.float64):
+                raise RuntimeError(f"detdata '{self.det_data}' is {dd.dtype}: PolyFilter2D works in place on float64 "
+                                   "timestreams (the reference converts other types to float64 and back)")
+            starts, stops = view_spans(obs, self.view, "PolyFilter2D")
+            n, n_group = obs.n_local_samples, len(keys)
+            if starts.size == 0:
+                coeff = np.zeros((n, n_group, n_mode))
+            elif on_device:
+                coeff = self._device(obs, data, capi.dev, dets, det_group, n_group, templates, starts, stops)
+            else:
+                coeff = self._host(obs, dets, det_group, n_group, templates, starts, stops)
+            inside = np.zeros(n, dtype=bool)
+            for a, b in zip(starts, stops):
+                inside[max(a, 0):min(b, n)] = True
+            self.coefficients[obs.name] = coeff
+            self.flagged_samples[obs.name] = np.count_nonzero(np.all(coeff == 0, axis=2) & inside[:, None], axis=0)
+        data.comm.barrier()
+
+    def _device(self, obs, data, D, dets, det_group, n_group, templates, starts, stops):
+        res = _Resident(obs, self.det_data, self.det_flags, self.shared_flags)
+        n = obs.n_local_samples
+        coeff = np.zeros((n, n_group, templates.shape[1]))
+        accel_data_create(coeff, f"{self.name}_coeff", owner=self)
+        accel_data_update_device(coeff, f"{self.name}_coeff")
+        D.filter_poly2d(self.order, n, res.dd.indices(dets), res.sig_ptr, res.flag_index(dets), res.flag_ptr,
+                        self.det_flag_mask, res.shared_ptr, self.shared_flag_mask, self.poly_flag_mask, det_group, n_group,
+                        templates, starts, stops, d_coeff=accel_device_ptr(coeff))
+        native().accel_synchronize()
+        accel_data_update_host(coeff, f"{self.name}_coeff")
+        accel_data_delete(coeff, f"{self.name}_coeff")
+        # the flags changed on the device copy, which is the current one: the host follows lazily through ``.data``
+        res.release(data)
+        return coeff
+
+    def _host(self, obs, dets, det_group, n_group, templates, starts, stops):
+        dd = obs.detdata[self.det_data]
+        fd = obs.detdata[self.det_flags] if self.det_flags is not None else None
+        sf = obs.shared[self.shared_flags] if self.shared_flags is not None else None
+        # ``.data`` makes the host copy of the timestreams and flags the current one
+        shared = None
+        if sf is not None:
+            resident = sf.accel_exists() and sf.accel_in_use()
+            if resident:
+                sf.accel_update_host()
+            shared = np.array(sf.data)
+            if resident:
+                sf.accel_update_device()
+        return poly2d_host(templates, det_group, n_group, dd.data, np.asarray(dd.indices(dets)),
+                           fd.data if fd is not None else None, np.asarray(fd.indices(dets)) if fd is not None else None,
+                           self.det_flag_mask, shared, self.shared_flag_mask, self.poly_flag_mask, starts, stops)
+
+    def _finalize(self, data, **kwargs):
+        return
+
+    def _requires(self):
+        req = {"meta": [], "shared": [], "detdata": [self.det_data], "intervals": []}
+        if self.shared_flags is not None:
+            req["shared"].append(self.shared_flags)
+        if self.det_flags is not None:
+            req["detdata"].append(self.det_flags)
+        if self.view is not None:
+            req["intervals"].append(self.view)
         return req
 
     def _provides(self):

@@ -7,7 +7,8 @@ configs[4] is upstream of this path and is not part of
 
     python workflows/ground_filter_mapmaker.py [--ndet 256] [--minutes 60] [--rate 200] [--nside 2048]
                                                [--iter 10] [--split] [--filter-order 5] [--trend-order 5]
-                                               [--polyfilter ORDER] [--common-mode] [--save-map FILE]
+                                               [--polyfilter ORDER] [--polyfilter2d ORDER [--polyfilter2d-key COLUMN]]
+                                               [--common-mode] [--save-map FILE]
                                                [--subharmonic ORDER] [--periodic-az BINS] [--fourier2d ORDER]
 """
 import argparse
@@ -47,6 +48,11 @@ def main(argv=None):
                          "el-nod samples carry the `irregular` flag bit and stay out of the maps")
     ap.add_argument("--polyfilter", type=int, default=None, metavar="ORDER",
                     help="run ops.PolyFilter(order=ORDER, view='throw') before GroundFilter (off by default)")
+    ap.add_argument("--polyfilter2d", type=int, default=None, metavar="ORDER",
+                    help="run ops.PolyFilter2D(order=ORDER) -- a 2-D polynomial across the focal plane at every time stamp -- "
+                         "before CommonModeFilter and GroundFilter (off by default)")
+    ap.add_argument("--polyfilter2d-key", default=None, metavar="COLUMN",
+                    help="with --polyfilter2d: fit one polynomial per value of this focalplane column (focalplane_key)")
     ap.add_argument("--common-mode", action="store_true", help="run ops.CommonModeFilter() before GroundFilter (off by default)")
     ap.add_argument("--subharmonic", type=int, default=None, metavar="ORDER",
                     help="solve for Legendre polynomials up to ORDER per detector and sweep next to the baselines "
@@ -112,6 +118,9 @@ def main(argv=None):
                 o.intervals.create("throw", [(int(iv.first), int(iv.last)) for iv in o.intervals[defaults.scanning_interval]])
         ops.PolyFilter(order=args.polyfilter, view="throw", name="polyfilter").apply(data)
         lap("PolyFilter")
+    if args.polyfilter2d is not None:
+        ops.PolyFilter2D(order=args.polyfilter2d, focalplane_key=args.polyfilter2d_key, name="polyfilter2d").apply(data)
+        lap("PolyFilter2D")
     if args.common_mode:
         ops.CommonModeFilter(name="commonmode").apply(data)
         lap("CommonModeFilter")
