@@ -1156,6 +1156,28 @@ int toast_hip_fft_convolve_dev(
     const double * ang_coef /*host or NULL*/, int64_t n_kernel, int deconvolve,
     const double * apodize /*host*/, int64_t n_apodize, int64_t max_batch, void * stream);
 
+/* The same convolution with the analytic single-pole kernel of a detector time constant instead of tabulated kernels:
+ * K_d(f) = 1 + i 2 pi tau_d f, evaluated per bin as the reference's kernel function does (`2.0 * np.pi * tau * kfreqs`
+ * left to right) [ref: src/toast/ops/time_constant.py:155-168, called by toast.fft.convolve(kernel_func=...) at
+ * src/toast/fft.py:318-336].  tau: n_det time constants in seconds (host), indexed like per-detector kernels -- by
+ * position in data_index, not by buffer row.  invert = 0 multiplies by K (TimeConstant(deconvolve=True)), invert = 1 by
+ * 1 / K (the detector's low-pass response).  DC removal, the real Nyquist bin, padding, apodisation and crop as
+ * toast_hip_fft_convolve.  The fused kernels always run their default row passes for this kernel kind
+ * (toast_hip_fft_points / _rows_split / _rows_n2 do not apply to it); toast_hip_fft_select does.
+ * toast_hip_fft_impulse_extents_pole: toast_hip_fft_impulse_extents for these kernels [ref: src/toast/fft.py:836-872
+ * with the kernel function of src/toast/ops/time_constant.py:155-168 and the multiply of src/toast/fft.py:318-336]. */
+int toast_hip_fft_convolve_pole(
+    double * det_data, int64_t n_data_rows, const int32_t * data_index, int64_t n_det, int64_t n_samp,
+    double rate, const double * tau, int invert, const double * apodize, int64_t n_apodize, int use_accel);
+
+int toast_hip_fft_convolve_pole_dev(
+    double * d_det_data, const int32_t * data_index /*host*/, int64_t n_det, int64_t n_samp, double rate,
+    const double * tau /*host*/, int invert, const double * apodize /*host*/, int64_t n_apodize, int64_t max_batch,
+    void * stream);
+
+int toast_hip_fft_impulse_extents_pole(int64_t n_det, int64_t n_samp, double rate, const double * tau, int invert,
+                                       const double * apodize, int64_t n_apodize, int32_t * extents, void * stream);
+
 int toast_hip_fft_r1d(int forward, int64_t length, int64_t count, const double * in, double * out,
                       double scale, int use_accel);
 int toast_hip_fft_r1d_dev(int forward, int64_t length, int64_t count, const double * d_in, double * d_out,

@@ -297,6 +297,7 @@ struct Params {
                                   // timestream with non-temporal loads (so that the window table stays in L2), bit 2 / 3:
                                   // the same for pass 3's loads / stores, bit 4 / 5: the row pass' loads / stores
     double fstep, scale;
+    const double * tau;           // analytic single-pole kernel (PoleTab): time constant of detector b [s], or nullptr
 };
 
 // set_rfft_input evaluated for one element of the padded series (src/toast/fft.py:163-188)
@@ -525,6 +526,37 @@ struct KTabSel<true> {
         t.fstep = p.fstep;
         return t;
     }
+};
+
+// The analytic kernel kind: K(f) = 1 + i 2 pi tau f of a detector's single-pole time constant (reference
+// src/toast/ops/time_constant.py:155-168, `2.0 * np.pi * tau * kfreqs` evaluated left to right).  One double per
+// detector and no table: the row passes take this type where they take a KTab for tabulated kernels, selected at
+// compile time; 1 / K is the division branch of apply_kernel.
+struct PoleTab {
+    double w;                  // (2 pi) tau of this workgroup's detector
+    double fstep;
+};
+__device__ __forceinline__ int kernel_interval(const PoleTab &, int) { return 0; }
+__device__ __forceinline__ double2 kernel_eval(const PoleTab & t, int, int k) {
+    return make_double2(1.0, t.w * ((double)k * t.fstep));
+}
+__device__ __forceinline__ double2 kernel_at(const PoleTab & t, int64_t k) { return kernel_eval(t, 0, (int)k); }
+struct PoleSel {
+    static __device__ __forceinline__ PoleTab make(const Params & p, int64_t det, char *, int, int) {
+        PoleTab t;
+        t.w = 2.0 * 3.141592653589793238462643383279502884 * p.tau[det];
+        t.fstep = p.fstep;
+        return t;
+    }
+};
+// the table type of a row pass: PoleTab for the analytic kind, else the tabulated kernels in global memory or LDS
+template <bool TLDS, bool POLE>
+struct KSel {
+    using type = KTabSel<TLDS>;
+};
+template <bool TLDS>
+struct KSel<TLDS, true> {
+    using type = PoleSel;
 };
 
 __device__ __forceinline__ double2 apply_kernel(double2 v, double2 kk, int deconvolve) {

@@ -45,6 +45,9 @@ void convolve(double * d_tod, const int32_t * d_idx, int64_t n_det, int64_t n_sa
               int64_t n_buffer, int64_t n_reflect, double fstep, const double * d_knots, int64_t n_knot,
               const double * d_mag, const double * d_ang, int per_det, int deconvolve, const double * d_apod,
               int64_t max_batch, hipStream_t st);
+void convolve_pole(double * d_tod, const int32_t * d_idx, int64_t n_det, int64_t n_samp, int64_t n_fft,
+                   int64_t n_buffer, int64_t n_reflect, double fstep, const double * d_tau, int invert,
+                   const double * d_apod, int64_t max_batch, hipStream_t st);
 }  // namespace fused_fft
 }  // namespace toast_hip
 
@@ -224,6 +227,37 @@ __global__ __launch_bounds__(kThreads) void k_fft_kernel(double2 * __restrict__ 
             } else {
                 r.x = v.x * kr - v.y * ki;
                 r.y = v.x * ki + v.y * kr;
+            }
+            if (i == n_psd - 1) r.y = 0.0;  // Nyquist bin of a real transform is real
+            v = r;
+        }
+        f[i] = v;
+    }
+}
+
+// multiply by the analytic single-pole kernel K = 1 + i 2 pi tau f (invert: by 1 / K) of detector det0 + b:
+// src/toast/ops/time_constant.py:155-168 (`2.0 * np.pi * tau * kfreqs`, left to right), src/toast/fft.py:330-337
+__global__ __launch_bounds__(kThreads) void k_fft_kernel_pole(double2 * __restrict__ fdata, int det0, int64_t n_psd,
+                                                              double fstep, const double * __restrict__ tau,
+                                                              int invert) {
+    const int b = blockIdx.y;
+    const double w = 2.0 * 3.141592653589793238462643383279502884 * tau[det0 + b];
+    double2 * f = fdata + (int64_t)b * n_psd;
+    for (int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x; i < n_psd;
+         i += (int64_t)gridDim.x * kThreads) {
+        double2 v = f[i];
+        if (i == 0) {
+            v = make_double2(0.0, 0.0);  // remove DC level
+        } else {
+            const double ki = w * ((double)i * fstep);
+            double2 r;
+            if (invert) {
+                const double den = 1.0 + ki * ki;
+                r.x = (v.x + v.y * ki) / den;
+                r.y = (v.y - v.x * ki) / den;
+            } else {
+                r.x = v.x - v.y * ki;
+                r.y = v.x * ki + v.y;
             }
             if (i == n_psd - 1) r.y = 0.0;  // Nyquist bin of a real transform is real
             v = r;
@@ -535,6 +569,144 @@ inline dim3 grid2(int64_t n, int64_t batch) {
     return dim3((unsigned)gx, (unsigned)batch, 1);
 }
 
+// The kernel of one call: PCHIP cubics of |K| and arg K on common knots (tau == nullptr), or the analytic single-pole
+// kernel of n_det time constants (tau != nullptr; `deconvolve` then carries `invert`)
+struct KernelArg {
+    const double * knots;
+    int64_t n_knot;
+    const double * mag_coef;
+    const double * ang_coef;
+    int64_t n_kernel;
+    int deconvolve;
+    const double * tau;
+};
+
+void convolve_dev_any(double * d_tod, const int32_t * data_index, int64_t n_det, int64_t n_samp, double rate,
+                      const KernelArg & k, const double * apodize, int64_t n_apodize, int64_t max_batch, void * stream) {
+    const bool pole = k.tau != nullptr;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const int64_t n_fft = toast_hip_fft_length(n_samp);
+    const int64_t n_psd = n_fft / 2 + 1;
+    const int64_t n_buffer = (n_fft - n_samp) / 2;                          // fft.py:283
+    const int64_t n_reflect = (n_buffer < n_samp) ? n_buffer : n_samp;      // fft.py:284
+    if (n_apodize != n_reflect) fail_arg("fft_convolve: apodize window must have n_reflect entries");
+    // numpy.fft.rfftfreq(n, d): k * (1 / (n d)) with d = 1 / rate
+    const double fstep = 1.0 / ((double)n_fft * (1.0 / rate));
+
+    static const bool host_timing = std::getenv("TOAST_HIP_FFT_HOST_TIMING") != nullptr;
+    const auto ht0 = std::chrono::steady_clock::now();
+    auto ht = [&](const char * what) {
+        if (host_timing) {
+            std::fprintf(stderr, "[toast_hip] fft_convolve_dev %-22s +%8.3f ms\n", what,
+                         std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - ht0).count());
+        }
+    };
+    const int64_t n_coef = k.n_kernel * 4 * (k.n_knot - 1);
+    ParamBlock pb;
+    const size_t o_idx = pb.push(data_index, sizeof(int32_t) * n_det);
+    const size_t o_kn = pole ? 0 : pb.push(k.knots, sizeof(double) * k.n_knot);
+    const size_t o_mc = pole ? 0 : pb.push(k.mag_coef, sizeof(double) * n_coef);
+    const size_t o_ac = (!pole && k.ang_coef) ? pb.push(k.ang_coef, sizeof(double) * n_coef) : 0;
+    const size_t o_tau = pole ? pb.push(k.tau, sizeof(double) * n_det) : 0;
+    const size_t o_ap = pb.push(apodize, sizeof(double) * n_reflect);
+    ht("pushed");
+    const char * d = pb.commit(st);
+    ht("committed");
+    const int32_t * d_idx = (const int32_t *)(d + o_idx);
+    const double * d_ac = (!pole && k.ang_coef) ? (const double *)(d + o_ac) : nullptr;
+    const double * d_tau = pole ? (const double *)(d + o_tau) : nullptr;
+    const int per_det = (k.n_kernel == n_det && n_det > 1) ? 1 : 0;
+
+    if (use_fused(n_fft)) {
+        if (pole) {
+            fused_fft::convolve_pole(d_tod, d_idx, n_det, n_samp, n_fft, n_buffer, n_reflect, fstep, d_tau, k.deconvolve,
+                                     (const double *)(d + o_ap), max_batch, st);
+        } else {
+            fused_fft::convolve(d_tod, d_idx, n_det, n_samp, n_fft, n_buffer, n_reflect, fstep,
+                                (const double *)(d + o_kn), k.n_knot, (const double *)(d + o_mc), d_ac, per_det,
+                                k.deconvolve, (const double *)(d + o_ap), max_batch, st);
+        }
+        ht("launched");
+        return;
+    }
+    int64_t batch = (max_batch > 0) ? max_batch : 64;
+    // keep the two work buffers under ~8 GB
+    const int64_t cap = (int64_t)((size_t(8) << 30) / ((size_t)n_fft * 8 + (size_t)n_psd * 16));
+    if (batch > cap) batch = cap > 0 ? cap : 1;
+    if (batch > n_det) batch = n_det;
+    double * tbuf = (double *)g_tbuf.get((size_t)batch * n_fft * sizeof(double));
+    double2 * fbuf = (double2 *)g_fbuf.get((size_t)batch * n_psd * sizeof(double2));
+
+    for (int64_t det0 = 0; det0 < n_det; det0 += batch) {
+        const int64_t nb = (n_det - det0 < batch) ? (n_det - det0) : batch;
+        Plan & fwd = get_plan(n_fft, nb, true);
+        Plan & inv = get_plan(n_fft, nb, false);
+        hipLaunchKernelGGL(k_fft_fill, grid2(n_fft, nb), dim3(kThreads), 0, st, d_tod, d_idx,
+                           (int)det0, tbuf, (const double *)(d + o_ap), n_samp, n_fft, n_buffer,
+                           n_reflect);
+        exec_plan(fwd, tbuf, fbuf, st);
+        if (pole) {
+            hipLaunchKernelGGL(k_fft_kernel_pole, grid2(n_psd, nb), dim3(kThreads), 0, st, fbuf, (int)det0, n_psd,
+                               fstep, d_tau, k.deconvolve);
+        } else {
+            hipLaunchKernelGGL(k_fft_kernel, grid2(n_psd, nb), dim3(kThreads), 0, st, fbuf, (int)det0,
+                               n_psd, fstep, (const double *)(d + o_kn), (int)k.n_knot,
+                               (const double *)(d + o_mc), d_ac, per_det, k.deconvolve);
+        }
+        exec_plan(inv, fbuf, tbuf, st);
+        hipLaunchKernelGGL(k_fft_crop, grid2(n_samp, nb), dim3(kThreads), 0, st, tbuf, d_idx,
+                           (int)det0, d_tod, n_samp, n_fft, n_buffer, 1.0 / (double)n_fft);
+        TH_HIP(hipGetLastError());
+    }
+}
+
+// Width of every kernel's impulse response (reference src/toast/fft.py:836-872: an impulse of 100 in the middle of
+// an empty timestream goes through the same convolution; walk left and right from the peak of |response| while it
+// exceeds 2 % of the peak).  The reference does this on the host, one detector at a time; here the impulses are made,
+// convolved and measured on the device in batches of rows of a scratch buffer and only the widths come back.
+void impulse_extents_any(int64_t n_det, int64_t n_samp, double rate, const KernelArg & k, const double * apodize,
+                         int64_t n_apodize, int32_t * extents, void * stream) {
+    const bool pole = k.tau != nullptr;
+    Manager::get().require_device();
+    hipStream_t st = stream ? static_cast<hipStream_t>(stream) : Manager::get().stream();
+    // a common kernel has one impulse response
+    const int64_t n_resp = (!pole && k.n_kernel == 1) ? 1 : n_det;
+    int64_t batch = (int64_t)((size_t(1) << 30) / ((size_t)n_samp * sizeof(double)));   // <= 1 GB of rows
+    if (batch < 1) batch = 1;
+    if (batch > 256) batch = 256;
+    if (batch > n_resp) batch = n_resp;
+    const size_t row_bytes = (((size_t)n_samp * sizeof(double)) + 255) & ~size_t(255);
+    char * scratch = (char *)Manager::get().scratch(Manager::kScratchFftImpulse,
+                                                    (size_t)batch * row_bytes + 256 + sizeof(int32_t) * batch, st);
+    // rows must be contiguous [nb, n_samp] for the convolution: no padding between them
+    double * d_rows = (double *)scratch;
+    int32_t * d_ext = (int32_t *)(scratch + (((size_t)batch * n_samp * sizeof(double) + 255) & ~size_t(255)));
+    std::vector<int32_t> idx((size_t)batch);
+    for (int64_t i = 0; i < batch; ++i) idx[(size_t)i] = (int32_t)i;
+    const int64_t n_coef = 4 * (k.n_knot - 1);
+    for (int64_t r0 = 0; r0 < n_resp; r0 += batch) {
+        const int64_t nb = (n_resp - r0 < batch) ? (n_resp - r0) : batch;
+        TH_HIP(hipMemsetAsync(d_rows, 0, (size_t)nb * n_samp * sizeof(double), st));
+        hipLaunchKernelGGL(k_impulse_set, dim3((unsigned)((nb + 255) / 256)), dim3(256), 0, st, d_rows, nb, n_samp,
+                           n_samp / 2, 100.0);
+        KernelArg kb = k;
+        if (pole) {
+            kb.tau = k.tau + r0;
+        } else {
+            kb.n_kernel = (k.n_kernel == 1) ? 1 : nb;
+            kb.mag_coef = k.mag_coef + ((k.n_kernel == 1) ? 0 : r0 * n_coef);
+            kb.ang_coef = k.ang_coef ? k.ang_coef + ((k.n_kernel == 1) ? 0 : r0 * n_coef) : nullptr;
+        }
+        convolve_dev_any(d_rows, idx.data(), nb, n_samp, rate, kb, apodize, n_apodize, 0, st);
+        hipLaunchKernelGGL(k_impulse_extent, dim3((unsigned)nb), dim3(256), 0, st, d_rows, n_samp, d_ext);
+        TH_HIP(hipGetLastError());
+        copy_to_host(extents + r0, d_ext, sizeof(int32_t) * nb, st);
+    }
+    if (n_resp == 1) {
+        for (int64_t i = 1; i < n_det; ++i) extents[i] = extents[0];
+    }
+}
+
 }  // namespace
 
 namespace toast_hip {
@@ -589,68 +761,19 @@ int toast_hip_fft_convolve_dev(double * d_tod, const int32_t * data_index, int64
         if (n_det <= 0 || n_samp <= 0) return;
         if (n_knot < 2) fail_arg("fft_convolve: need at least two kernel frequencies");
         if (n_kernel != 1 && n_kernel != n_det) fail_arg("fft_convolve: n_kernel must be 1 or n_det");
-        hipStream_t st = static_cast<hipStream_t>(stream);
-        const int64_t n_fft = toast_hip_fft_length(n_samp);
-        const int64_t n_psd = n_fft / 2 + 1;
-        const int64_t n_buffer = (n_fft - n_samp) / 2;                          // fft.py:283
-        const int64_t n_reflect = (n_buffer < n_samp) ? n_buffer : n_samp;      // fft.py:284
-        if (n_apodize != n_reflect) fail_arg("fft_convolve: apodize window must have n_reflect entries");
-        // numpy.fft.rfftfreq(n, d): k * (1 / (n d)) with d = 1 / rate
-        const double fstep = 1.0 / ((double)n_fft * (1.0 / rate));
+        const KernelArg k{knots, n_knot, mag_coef, ang_coef, n_kernel, deconvolve, nullptr};
+        convolve_dev_any(d_tod, data_index, n_det, n_samp, rate, k, apodize, n_apodize, max_batch, stream);
+    });
+}
 
-        static const bool host_timing = std::getenv("TOAST_HIP_FFT_HOST_TIMING") != nullptr;
-        const auto ht0 = std::chrono::steady_clock::now();
-        auto ht = [&](const char * what) {
-            if (host_timing) {
-                std::fprintf(stderr, "[toast_hip] fft_convolve_dev %-22s +%8.3f ms\n", what,
-                             std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - ht0).count());
-            }
-        };
-        ParamBlock pb;
-        const size_t o_idx = pb.push(data_index, sizeof(int32_t) * n_det);
-        const size_t o_kn = pb.push(knots, sizeof(double) * n_knot);
-        const size_t o_mc = pb.push(mag_coef, sizeof(double) * n_kernel * 4 * (n_knot - 1));
-        const size_t o_ac = ang_coef ? pb.push(ang_coef, sizeof(double) * n_kernel * 4 * (n_knot - 1)) : 0;
-        const size_t o_ap = pb.push(apodize, sizeof(double) * n_reflect);
-        ht("pushed");
-        const char * d = pb.commit(st);
-        ht("committed");
-        const int32_t * d_idx = (const int32_t *)(d + o_idx);
-        const double * d_ac = ang_coef ? (const double *)(d + o_ac) : nullptr;
-
-        if (use_fused(n_fft)) {
-            fused_fft::convolve(d_tod, d_idx, n_det, n_samp, n_fft, n_buffer, n_reflect, fstep,
-                                (const double *)(d + o_kn), n_knot, (const double *)(d + o_mc), d_ac,
-                                (n_kernel == n_det && n_det > 1) ? 1 : 0, deconvolve,
-                                (const double *)(d + o_ap), max_batch, st);
-            ht("launched");
-            return;
-        }
-        int64_t batch = (max_batch > 0) ? max_batch : 64;
-        // keep the two work buffers under ~8 GB
-        const int64_t cap = (int64_t)((size_t(8) << 30) / ((size_t)n_fft * 8 + (size_t)n_psd * 16));
-        if (batch > cap) batch = cap > 0 ? cap : 1;
-        if (batch > n_det) batch = n_det;
-        double * tbuf = (double *)g_tbuf.get((size_t)batch * n_fft * sizeof(double));
-        double2 * fbuf = (double2 *)g_fbuf.get((size_t)batch * n_psd * sizeof(double2));
-
-        for (int64_t det0 = 0; det0 < n_det; det0 += batch) {
-            const int64_t nb = (n_det - det0 < batch) ? (n_det - det0) : batch;
-            Plan & fwd = get_plan(n_fft, nb, true);
-            Plan & inv = get_plan(n_fft, nb, false);
-            hipLaunchKernelGGL(k_fft_fill, grid2(n_fft, nb), dim3(kThreads), 0, st, d_tod, d_idx,
-                               (int)det0, tbuf, (const double *)(d + o_ap), n_samp, n_fft, n_buffer,
-                               n_reflect);
-            exec_plan(fwd, tbuf, fbuf, st);
-            hipLaunchKernelGGL(k_fft_kernel, grid2(n_psd, nb), dim3(kThreads), 0, st, fbuf, (int)det0,
-                               n_psd, fstep, (const double *)(d + o_kn), (int)n_knot,
-                               (const double *)(d + o_mc), d_ac, (n_kernel == n_det && n_det > 1) ? 1 : 0,
-                               deconvolve);
-            exec_plan(inv, fbuf, tbuf, st);
-            hipLaunchKernelGGL(k_fft_crop, grid2(n_samp, nb), dim3(kThreads), 0, st, tbuf, d_idx,
-                               (int)det0, d_tod, n_samp, n_fft, n_buffer, 1.0 / (double)n_fft);
-            TH_HIP(hipGetLastError());
-        }
+int toast_hip_fft_convolve_pole_dev(double * d_tod, const int32_t * data_index, int64_t n_det, int64_t n_samp,
+                                    double rate, const double * tau, int invert, const double * apodize,
+                                    int64_t n_apodize, int64_t max_batch, void * stream) {
+    return guarded([&] {
+        if (n_det <= 0 || n_samp <= 0) return;
+        if (tau == nullptr) fail_arg("fft_convolve_pole: tau must have n_det entries");
+        const KernelArg k{nullptr, 0, nullptr, nullptr, n_det, invert ? 1 : 0, tau};
+        convolve_dev_any(d_tod, data_index, n_det, n_samp, rate, k, apodize, n_apodize, max_batch, stream);
     });
 }
 
@@ -672,10 +795,21 @@ int toast_hip_fft_convolve(double * det_data, int64_t n_data_rows, const int32_t
     });
 }
 
-// Width of every kernel's impulse response (reference src/toast/fft.py:836-872: an impulse of 100 in the middle of
-// an empty timestream goes through the same convolution; walk left and right from the peak of |response| while it
-// exceeds 2 % of the peak).  The reference does this on the host, one detector at a time; here the impulses are made,
-// convolved and measured on the device in batches of rows of a scratch buffer and only the widths come back.
+int toast_hip_fft_convolve_pole(double * det_data, int64_t n_data_rows, const int32_t * data_index, int64_t n_det,
+                                int64_t n_samp, double rate, const double * tau, int invert, const double * apodize,
+                                int64_t n_apodize, int use_accel) {
+    return guarded([&] {
+        Manager::get().require_device();
+        hipStream_t st = Manager::get().stream();
+        Staging stg(use_accel != 0, st);
+        double * d_tod = stg.inout(det_data, (size_t)(n_data_rows * n_samp));
+        int rc = toast_hip_fft_convolve_pole_dev(d_tod, data_index, n_det, n_samp, rate, tau, invert, apodize,
+                                                 n_apodize, 0, st);
+        if (rc != TOAST_HIP_OK) throw Error(rc, toast_hip_last_error());
+        stg.finish();
+    });
+}
+
 int toast_hip_fft_impulse_extents(int64_t n_det, int64_t n_samp, double rate, const double * knots, int64_t n_knot,
                                   const double * mag_coef, const double * ang_coef, int64_t n_kernel,
                                   int deconvolve, const double * apodize, int64_t n_apodize, int32_t * extents,
@@ -683,41 +817,19 @@ int toast_hip_fft_impulse_extents(int64_t n_det, int64_t n_samp, double rate, co
     return guarded([&] {
         if (n_det <= 0 || n_samp <= 0) return;
         if (n_kernel != 1 && n_kernel != n_det) fail_arg("fft_impulse_extents: n_kernel must be 1 or n_det");
-        Manager::get().require_device();
-        hipStream_t st = stream ? static_cast<hipStream_t>(stream) : Manager::get().stream();
-        // a common kernel has one impulse response
-        const int64_t n_resp = (n_kernel == 1) ? 1 : n_det;
-        int64_t batch = (int64_t)((size_t(1) << 30) / ((size_t)n_samp * sizeof(double)));   // <= 1 GB of rows
-        if (batch < 1) batch = 1;
-        if (batch > 256) batch = 256;
-        if (batch > n_resp) batch = n_resp;
-        const size_t row_bytes = (((size_t)n_samp * sizeof(double)) + 255) & ~size_t(255);
-        char * scratch = (char *)Manager::get().scratch(Manager::kScratchFftImpulse,
-                                                        (size_t)batch * row_bytes + 256 + sizeof(int32_t) * batch, st);
-        // rows must be contiguous [nb, n_samp] for the convolution: no padding between them
-        double * d_rows = (double *)scratch;
-        int32_t * d_ext = (int32_t *)(scratch + (((size_t)batch * n_samp * sizeof(double) + 255) & ~size_t(255)));
-        std::vector<int32_t> idx((size_t)batch);
-        for (int64_t i = 0; i < batch; ++i) idx[(size_t)i] = (int32_t)i;
-        const int64_t n_coef = 4 * (n_knot - 1);
-        for (int64_t r0 = 0; r0 < n_resp; r0 += batch) {
-            const int64_t nb = (n_resp - r0 < batch) ? (n_resp - r0) : batch;
-            TH_HIP(hipMemsetAsync(d_rows, 0, (size_t)nb * n_samp * sizeof(double), st));
-            hipLaunchKernelGGL(k_impulse_set, dim3((unsigned)((nb + 255) / 256)), dim3(256), 0, st, d_rows, nb, n_samp,
-                               n_samp / 2, 100.0);
-            const int64_t nk = (n_kernel == 1) ? 1 : nb;
-            int rc = toast_hip_fft_convolve_dev(d_rows, idx.data(), nb, n_samp, rate, knots, n_knot,
-                                                mag_coef + ((n_kernel == 1) ? 0 : r0 * n_coef),
-                                                ang_coef ? ang_coef + ((n_kernel == 1) ? 0 : r0 * n_coef) : nullptr, nk,
-                                                deconvolve, apodize, n_apodize, 0, st);
-            if (rc != TOAST_HIP_OK) throw Error(rc, toast_hip_last_error());
-            hipLaunchKernelGGL(k_impulse_extent, dim3((unsigned)nb), dim3(256), 0, st, d_rows, n_samp, d_ext);
-            TH_HIP(hipGetLastError());
-            copy_to_host(extents + r0, d_ext, sizeof(int32_t) * nb, st);
-        }
-        if (n_kernel == 1) {
-            for (int64_t i = 1; i < n_det; ++i) extents[i] = extents[0];
-        }
+        if (n_knot < 2) fail_arg("fft_convolve: need at least two kernel frequencies");
+        const KernelArg k{knots, n_knot, mag_coef, ang_coef, n_kernel, deconvolve, nullptr};
+        impulse_extents_any(n_det, n_samp, rate, k, apodize, n_apodize, extents, stream);
+    });
+}
+
+int toast_hip_fft_impulse_extents_pole(int64_t n_det, int64_t n_samp, double rate, const double * tau, int invert,
+                                       const double * apodize, int64_t n_apodize, int32_t * extents, void * stream) {
+    return guarded([&] {
+        if (n_det <= 0 || n_samp <= 0) return;
+        if (tau == nullptr) fail_arg("fft_impulse_extents_pole: tau must have n_det entries");
+        const KernelArg k{nullptr, 0, nullptr, nullptr, n_det, invert ? 1 : 0, tau};
+        impulse_extents_any(n_det, n_samp, rate, k, apodize, n_apodize, extents, stream);
     });
 }
 

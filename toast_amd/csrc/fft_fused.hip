@@ -55,6 +55,7 @@ namespace fused_fft {
 bool rows_reg_supported(const Params & p);
 void launch_rows_reg(const Params & p, unsigned n_det, bool tab_lds, size_t tab_bytes, hipStream_t st);
 void launch_rows_reg16(const Params & p, unsigned n_det, bool tab_lds, size_t tab_bytes, hipStream_t st);
+void launch_rows_reg16_pole(const Params & p, unsigned n_det, hipStream_t st);
 void pack_tables(const Params & p, char * blob, int64_t n_kern, hipStream_t st);
 bool cols_reg_supported(const Params & p, int min_log_n1);
 int cols_reg_log_c(int log_n1);
@@ -175,7 +176,8 @@ __global__ __launch_bounds__((1 << LT) / P, (P == 16 ? 2 : 4)) void k_fft_cols(c
 
 // pass 2: rows (k1, N1 - k1) [block 0: rows 0 and N1 / 2]
 // LT = log2 of the tile = 2 N2: 12 (N2 = 2048, 64 KB, two workgroups per CU) or 11 (N2 = 1024, 32 KB, four per CU)
-template <int LT, int P, bool TLDS>
+// POLE: the analytic single-pole kernel (PoleTab, one double per detector) instead of the tabulated ones
+template <int LT, int P, bool TLDS, bool POLE = false>
 __global__ __launch_bounds__((1 << LT) / P, (P == 16 ? 2 : 4)) void k_fft_rows(const Params p) {
     constexpr int kRowTile = 1 << LT;
     constexpr int T = kRowTile / P;
@@ -198,8 +200,8 @@ __global__ __launch_bounds__((1 << LT) / P, (P == 16 ? 2 : 4)) void k_fft_rows(c
         const int64_t rr = (e & 1) ? r1 : r0;
         v[k] = (p.stream_hint & 16) ? load_nt(work + (rr << p.log_n2) + (e >> 1)) : work[(rr << p.log_n2) + (e >> 1)];
     }
-    const auto kt = KTabSel<TLDS>::make(p, p.per_det ? (int64_t)(p.det0 + b) : 0, reinterpret_cast<char *>(sm + kRowTile),
-                                        tid, T);
+    const auto kt = KSel<TLDS, POLE>::type::make(p, p.per_det ? (int64_t)(p.det0 + b) : 0,
+                                                 reinterpret_cast<char *>(sm + kRowTile), tid, T);
     PHASE_WAIT_LOADS;
     PHASE_SINCE_ENTRY(14);      // kernel entry -> tile and kernel tables landed
     PHASE_DECL;
@@ -456,6 +458,7 @@ static Plan & get_plan(int64_t n_fft, hipStream_t st) {
         set(reinterpret_cast<const void *>(&k_fft_rows<kLT, 8, true>), lds_tab);
         set(reinterpret_cast<const void *>(&k_fft_rows<kLT - 1, 8, false>), lds / 2);
         set(reinterpret_cast<const void *>(&k_fft_rows<kLT - 1, 8, true>), lds / 2 + kTabLdsHalf);
+        set(reinterpret_cast<const void *>(&k_fft_rows<kLT, 8, false, true>), lds);
         attr_set = true;
     }
     return g_plans.emplace(key, pl).first->second;
@@ -711,10 +714,15 @@ double pipeline_bytes_per_sample(int64_t n_samp, int64_t n_fft) {
     return 16.0 + 32.0 * (double)n_fft / (double)n_samp;
 }
 
-void convolve(double * d_tod, const int32_t * d_idx, int64_t n_det, int64_t n_samp, int64_t n_fft,
-              int64_t n_buffer, int64_t n_reflect, double fstep, const double * d_knots, int64_t n_knot,
-              const double * d_mag, const double * d_ang, int per_det, int deconvolve, const double * d_apod,
-              int64_t max_batch, hipStream_t st) {
+// d_tau != nullptr: the analytic single-pole kernel K = 1 + i 2 pi tau f of detector d (d_tau[d], seconds; `deconvolve`
+// then means "multiply by 1 / K") instead of the tabulated kernels -- no hints, no packed tables, and always the default
+// row passes (k_fft_rows for the self-paired rows, k_fft_rows_reg16 for the others, N2 = 2048) whatever the experiment
+// switches say: the other row passes have no analytic instantiation.
+static void convolve_any(double * d_tod, const int32_t * d_idx, int64_t n_det, int64_t n_samp, int64_t n_fft,
+                         int64_t n_buffer, int64_t n_reflect, double fstep, const double * d_knots, int64_t n_knot,
+                         const double * d_mag, const double * d_ang, int per_det, int deconvolve, const double * d_tau,
+                         const double * d_apod, int64_t max_batch, hipStream_t st) {
+    const bool pole = d_tau != nullptr;
     Plan & pl = get_plan(n_fft, st);
     const int64_t m = n_fft / 2;
     int log_m = 0;
@@ -730,7 +738,7 @@ void convolve(double * d_tod, const int32_t * d_idx, int64_t n_det, int64_t n_sa
     // Rows of N2 = 2048 (64 KB pair tiles) or, for M <= 2^20, of N2 = 1024 (32 KB pair tiles: four workgroups per CU in
     // the row pass; the column passes then move 64-byte instead of 128-byte pieces).  TOAST_HIP_FFT_N2=1024|2048.
     p.log_n2 = kLT - 1;
-    if (rows_n2() == 1024 && log_m >= 11 && log_m <= 20) p.log_n2 = kLT - 2;
+    if (!pole && rows_n2() == 1024 && log_m >= 11 && log_m <= 20) p.log_n2 = kLT - 2;
     p.log_n1 = log_m - p.log_n2;
     p.tb.wtile = pl.tables;
     p.tb.t0 = pl.tables + kTile;
@@ -744,6 +752,7 @@ void convolve(double * d_tod, const int32_t * d_idx, int64_t n_det, int64_t n_sa
     p.ang_coef = d_ang;
     p.per_det = per_det;
     p.deconvolve = deconvolve;
+    p.tau = d_tau;
     p.fstep = fstep;
     p.aligned = ((n_buffer % 2) == 0 && (n_samp % 2) == 0 && (n_reflect % 2) == 0 &&
                  (reinterpret_cast<uintptr_t>(d_tod) % 16) == 0 && (reinterpret_cast<uintptr_t>(d_apod) % 16) == 0)
@@ -782,28 +791,30 @@ void convolve(double * d_tod, const int32_t * d_idx, int64_t n_det, int64_t n_sa
     if (batch > n_det) batch = n_det;
     const int64_t n_hint = (int64_t(1) << p.log_n2) + 2;       // bins q N1, q = 0 .. N2 + 1
     const int64_t n_hint0 = int64_t(1) << p.log_n1;             // every bin of the first block
-    const size_t hint_bytes = ((size_t)n_hint * (sizeof(int32_t) + sizeof(uint16_t)) + (size_t)n_hint0 * sizeof(int32_t) +
-                               255 + 8) & ~size_t(255);
+    const size_t hint_bytes = pole ? 0 : ((size_t)n_hint * (sizeof(int32_t) + sizeof(uint16_t)) +
+                                          (size_t)n_hint0 * sizeof(int32_t) + 255 + 8) & ~size_t(255);
     // row pass: knots, this detector's cubics and 16-bit hints in LDS when they fit (layout: KTabSel<true>::make)
-    const size_t tab_bytes = (((size_t)n_knot + (size_t)4 * (n_knot - 1) * (d_ang ? 2 : 1)) * sizeof(double) +
-                              (size_t)n_hint * sizeof(uint16_t) + 15) & ~size_t(15);
+    const size_t tab_bytes = pole ? 0 : (((size_t)n_knot + (size_t)4 * (n_knot - 1) * (d_ang ? 2 : 1)) * sizeof(double) +
+                                         (size_t)n_hint * sizeof(uint16_t) + 15) & ~size_t(15);
     // ... which the register row pass copies from one packed block per kernel (k_pack_tables)
     const int64_t n_kern = per_det ? n_det : 1;
-    const size_t blob_bytes = (tab_bytes <= (size_t)kTabLdsMax) ? (((size_t)n_kern * tab_bytes + 255) & ~size_t(255)) : 0;
+    const size_t blob_bytes = (!pole && tab_bytes <= (size_t)kTabLdsMax) ? (((size_t)n_kern * tab_bytes + 255) & ~size_t(255)) : 0;
     char * scratch = (char *)Manager::get().scratch(Manager::kScratchFftWork,
                                                     hint_bytes + blob_bytes + (size_t)batch * m * sizeof(double2), st);
     int32_t * d_hint = (int32_t *)scratch;
     int32_t * d_hint0 = d_hint + n_hint;
     uint16_t * d_hint16 = (uint16_t *)(d_hint0 + n_hint0);
-    p.knot_hint = d_hint;
-    p.knot_hint16 = d_hint16;
-    p.knot_hint0 = d_hint0;
+    p.knot_hint = pole ? nullptr : d_hint;
+    p.knot_hint16 = pole ? nullptr : d_hint16;
+    p.knot_hint0 = pole ? nullptr : d_hint0;
     p.tab_blob = blob_bytes ? scratch + hint_bytes : nullptr;
     p.tab_bytes = blob_bytes ? (int)tab_bytes : 0;
     p.tab_copy_bytes = blob_bytes ? (int)((((size_t)n_knot + (size_t)4 * (n_knot - 1) * (d_ang ? 2 : 1)) * sizeof(double) + 15) & ~size_t(15)) : 0;
     p.work = (double2 *)(scratch + hint_bytes + blob_bytes);
-    hipLaunchKernelGGL(k_knot_hint, dim3((unsigned)((n_hint + n_hint0 + 255) / 256)), dim3(256), 0, st, d_knots,
-                       (int)n_knot, fstep, p.log_n1, n_hint, d_hint, d_hint16, d_hint0);
+    if (!pole) {
+        hipLaunchKernelGGL(k_knot_hint, dim3((unsigned)((n_hint + n_hint0 + 255) / 256)), dim3(256), 0, st, d_knots,
+                           (int)n_knot, fstep, p.log_n1, n_hint, d_hint, d_hint16, d_hint0);
+    }
     if (blob_bytes && rows_split() >= 2) pack_tables(p, scratch + hint_bytes, n_kern, st);
     static int tab_lds_env = -1;
     if (tab_lds_env < 0) {
@@ -865,38 +876,44 @@ void convolve(double * d_tod, const int32_t * d_idx, int64_t n_det, int64_t n_sa
         } else {
             hipLaunchKernelGGL((k_fft_cols<kLT, 16, false>), dim3(n_col_tiles, (unsigned)nb), dim3(kTile / 16), lds, st, p);
         }
-        const bool reg_rows = rows_split() >= 2 && !half_rows && rows_reg_supported(p);
-        const bool split = rows_split() == 1 && !half_rows;
-        // split / registers: rows 0 and N1 / 2 only (self-paired)
-        const dim3 g_pair((split || reg_rows) ? 1 : n_row_tiles, (unsigned)nb);
-        if (half_rows) {
-            const size_t lds_half = lds / 2 + (tab_lds ? tab_bytes : 0);
-            if (tab_lds) {
-                hipLaunchKernelGGL((k_fft_rows<kLT - 1, 8, true>), g_pair, dim3(kTile / 16), lds_half, st, p);
-            } else {
-                hipLaunchKernelGGL((k_fft_rows<kLT - 1, 8, false>), g_pair, dim3(kTile / 16), lds_half, st, p);
-            }
-        } else if (split || points_of(0) == 8) {
-            if (tab_lds) {
-                hipLaunchKernelGGL((k_fft_rows<kLT, 8, true>), g_pair, dim3(kTile / 8), lds_rows, st, p);
-            } else {
-                hipLaunchKernelGGL((k_fft_rows<kLT, 8, false>), g_pair, dim3(kTile / 8), lds_rows, st, p);
-            }
-        } else if (tab_lds) {
-            hipLaunchKernelGGL((k_fft_rows<kLT, 16, true>), g_pair, dim3(kTile / 16), lds_rows, st, p);
+        if (pole) {
+            // rows 0 and N1 / 2 (all there are at N1 = 2), then the pairs (g, N1 - g)
+            hipLaunchKernelGGL((k_fft_rows<kLT, 8, false, true>), dim3(1, (unsigned)nb), dim3(kTile / 8), lds, st, p);
+            if (rows_reg_supported(p)) launch_rows_reg16_pole(p, (unsigned)nb, st);
         } else {
-            hipLaunchKernelGGL((k_fft_rows<kLT, 16, false>), g_pair, dim3(kTile / 16), lds_rows, st, p);
-        }
-        if (reg_rows) {
-            if (rows_split() == 2) launch_rows_reg16(p, (unsigned)nb, tab_lds, tab_bytes, st);
-            else launch_rows_reg(p, (unsigned)nb, tab_lds, tab_bytes, st);
-        }
-        if (split && n_row_tiles > 1) {
-            const dim3 gr(n_row_tiles - 1, (unsigned)nb), bl(kTile / 16);
-            if (tab_lds) {
-                hipLaunchKernelGGL((k_fft_rows_split<8, 2, true>), gr, bl, lds_split, st, p);
+            const bool reg_rows = rows_split() >= 2 && !half_rows && rows_reg_supported(p);
+            const bool split = rows_split() == 1 && !half_rows;
+            // split / registers: rows 0 and N1 / 2 only (self-paired)
+            const dim3 g_pair((split || reg_rows) ? 1 : n_row_tiles, (unsigned)nb);
+            if (half_rows) {
+                const size_t lds_half = lds / 2 + (tab_lds ? tab_bytes : 0);
+                if (tab_lds) {
+                    hipLaunchKernelGGL((k_fft_rows<kLT - 1, 8, true>), g_pair, dim3(kTile / 16), lds_half, st, p);
+                } else {
+                    hipLaunchKernelGGL((k_fft_rows<kLT - 1, 8, false>), g_pair, dim3(kTile / 16), lds_half, st, p);
+                }
+            } else if (split || points_of(0) == 8) {
+                if (tab_lds) {
+                    hipLaunchKernelGGL((k_fft_rows<kLT, 8, true>), g_pair, dim3(kTile / 8), lds_rows, st, p);
+                } else {
+                    hipLaunchKernelGGL((k_fft_rows<kLT, 8, false>), g_pair, dim3(kTile / 8), lds_rows, st, p);
+                }
+            } else if (tab_lds) {
+                hipLaunchKernelGGL((k_fft_rows<kLT, 16, true>), g_pair, dim3(kTile / 16), lds_rows, st, p);
             } else {
-                hipLaunchKernelGGL((k_fft_rows_split<8, 2, false>), gr, bl, lds_split, st, p);
+                hipLaunchKernelGGL((k_fft_rows<kLT, 16, false>), g_pair, dim3(kTile / 16), lds_rows, st, p);
+            }
+            if (reg_rows) {
+                if (rows_split() == 2) launch_rows_reg16(p, (unsigned)nb, tab_lds, tab_bytes, st);
+                else launch_rows_reg(p, (unsigned)nb, tab_lds, tab_bytes, st);
+            }
+            if (split && n_row_tiles > 1) {
+                const dim3 gr(n_row_tiles - 1, (unsigned)nb), bl(kTile / 16);
+                if (tab_lds) {
+                    hipLaunchKernelGGL((k_fft_rows_split<8, 2, true>), gr, bl, lds_split, st, p);
+                } else {
+                    hipLaunchKernelGGL((k_fft_rows_split<8, 2, false>), gr, bl, lds_split, st, p);
+                }
             }
         }
         if (cols_reg || cols_inv_reg_for(p)) {
@@ -908,6 +925,21 @@ void convolve(double * d_tod, const int32_t * d_idx, int64_t n_det, int64_t n_sa
         }
         TH_HIP(hipGetLastError());
     }
+}
+
+void convolve(double * d_tod, const int32_t * d_idx, int64_t n_det, int64_t n_samp, int64_t n_fft,
+              int64_t n_buffer, int64_t n_reflect, double fstep, const double * d_knots, int64_t n_knot,
+              const double * d_mag, const double * d_ang, int per_det, int deconvolve, const double * d_apod,
+              int64_t max_batch, hipStream_t st) {
+    convolve_any(d_tod, d_idx, n_det, n_samp, n_fft, n_buffer, n_reflect, fstep, d_knots, n_knot, d_mag, d_ang, per_det,
+                 deconvolve, nullptr, d_apod, max_batch, st);
+}
+
+void convolve_pole(double * d_tod, const int32_t * d_idx, int64_t n_det, int64_t n_samp, int64_t n_fft,
+                   int64_t n_buffer, int64_t n_reflect, double fstep, const double * d_tau, int invert,
+                   const double * d_apod, int64_t max_batch, hipStream_t st) {
+    convolve_any(d_tod, d_idx, n_det, n_samp, n_fft, n_buffer, n_reflect, fstep, nullptr, 0, nullptr, nullptr, 1, invert,
+                 d_tau, d_apod, max_batch, st);
 }
 
 #if defined(TOAST_FFT_PHASE_CLOCK)

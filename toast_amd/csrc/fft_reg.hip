@@ -24,6 +24,8 @@
 #include "runtime.hpp"
 #include "fft_device.hpp"
 
+#include <type_traits>
+
 namespace toast_hip {
 namespace fused_fft {
 
@@ -262,6 +264,8 @@ __device__ __forceinline__ int kernel_interval_pre(const KTab<H> & t, int k, int
     }
     return (q == 0) ? ((k == g) ? lo_g : lo_ng) : lo;
 }
+// the analytic kernel has no intervals
+__device__ __forceinline__ int kernel_interval_pre(const PoleTab &, int, int, int, int) { return 0; }
 
 // pass 2 for the row pairs (g, N1 - g), 0 < g < N1 / 2, N2 = 2048: 256 threads = two pairs, one row per wave
 template <bool TLDS, bool CPLX>
@@ -397,7 +401,9 @@ __device__ __forceinline__ void row_fft_2048_p16(double2 (&v)[16], double * smd,
 // HG (the default; TOAST_HIP_FFT_HINTS=lds turns it off): the 16-bit interval hints (4 KB, two look-ups per bin, the same for
 // every workgroup: cache resident) stay in global memory -- 40 172 B of LDS instead of 44 272: FOUR workgroups per CU
 // instead of three (cfg-3 call 18.59-18.65 -> 18.33-18.43 ms, the 2^23 call 42.5-42.7 -> 41.5 ms; profiles/r06_c)
-template <bool TLDS, bool CPLX, bool HG = false>
+// POLE (with TLDS = CPLX = HG = false): the analytic single-pole kernel, PoleTab of fft_device.hpp -- no table copy, no
+// hints; 37 120 B of LDS
+template <bool TLDS, bool CPLX, bool HG = false, bool POLE = false>
 __global__ __launch_bounds__(256, 3) void k_fft_rows_reg16(const Params p) {
     extern __shared__ double2 sm[];           // 2 x 17 KB exchange buffers (one per row), stage twiddles, kernel tables
     const int tid = threadIdx.x;
@@ -419,8 +425,11 @@ __global__ __launch_bounds__(256, 3) void k_fft_rows_reg16(const Params p) {
         for (int j = 0; j < 3; ++j) tc[j] = (tid + 256 * j < n_chunk) ? g_tab[tid + 256 * j] : make_uint4(0, 0, 0, 0);
     }
     const double2 tws = (tid < 144) ? p.wrow[tid] : make_double2(0.0, 0.0);
-    int lo_g = __builtin_amdgcn_readfirstlane(p.knot_hint0[g]);
-    int lo_ng = __builtin_amdgcn_readfirstlane(p.knot_hint0[n1 - g]);
+    int lo_g = 0, lo_ng = 0;
+    if constexpr (!POLE) {
+        lo_g = __builtin_amdgcn_readfirstlane(p.knot_hint0[g]);
+        lo_ng = __builtin_amdgcn_readfirstlane(p.knot_hint0[n1 - g]);
+    }
     // w_N^k = w_N^g w_4096^q = (w_N^g w_4096^l) w_32^r for bin k = g + N1 q, q = l + 128 r
     double2 w0 = cmul(tw_big(p.tb, g), p.tb.wtile[l]);
     const double2 * __restrict__ rowp = p.work + (int64_t)b * m + (row << 11) + l;
@@ -436,8 +445,10 @@ __global__ __launch_bounds__(256, 3) void k_fft_rows_reg16(const Params p) {
     if (tid < 144) s_w[tid] = tws;
     asm volatile("" : "+v"(w0.x), "+v"(w0.y), "+s"(lo_g), "+s"(lo_ng));   // here, not where they are first used
     __syncthreads();
-    KTab<typename KTabSel<TLDS>::H> kt;
-    if constexpr (TLDS) {
+    typename std::conditional<POLE, PoleTab, KTab<typename KTabSel<TLDS>::H>>::type kt;
+    if constexpr (POLE) {
+        kt = PoleSel::make(p, kern, nullptr, tid, 256);
+    } else if constexpr (TLDS) {
         const int n_coef = 4 * (p.n_knot - 1);
         const double * s_knots = reinterpret_cast<const double *>(s_tab);
         kt.knots = s_knots;
@@ -926,6 +937,20 @@ void launch_rows_reg16(const Params & p, unsigned n_det, bool tab_lds, size_t ta
         if (cplx) hipLaunchKernelGGL((k_fft_rows_reg16<false, true>), grid, dim3(256), rows_reg16_lds(0), st, p);
         else hipLaunchKernelGGL((k_fft_rows_reg16<false, false>), grid, dim3(256), rows_reg16_lds(0), st, p);
     }
+}
+
+// the analytic single-pole kernel (Params::tau): no tables, so one instantiation and the smallest LDS footprint
+void launch_rows_reg16_pole(const Params & p, unsigned n_det, hipStream_t st) {
+    const void * fn = reinterpret_cast<const void *>(&k_fft_rows_reg16<false, false, false, true>);
+    static bool attr_set = false;
+    if (!attr_set) {
+        TH_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)rows_reg16_lds(0)));
+        attr_set = true;
+    }
+    const int n_pair = (1 << p.log_n1) / 2 - 1;                  // row pairs g = 1 .. N1 / 2 - 1
+    if (n_pair <= 0) return;
+    hipLaunchKernelGGL((k_fft_rows_reg16<false, false, false, true>), dim3((unsigned)n_pair, n_det), dim3(256),
+                       rows_reg16_lds(0), st, p);
 }
 
 // column passes in registers: N2 = 2048, N1 = 512 / 1024 / 2048, aligned timestreams

@@ -151,6 +151,89 @@ def convolve_dev(d_det_data, data_index, n_samp, rate, kernel_freq, kernels, dec
         C.c_void_p(int(stream))))
 
 
+class SinglePole:
+    """The analytic kernel of a single-pole detector time constant, K(f) = 1 + i 2 pi tau f (reference
+    src/toast/ops/time_constant.py:155-168): ``deconvolve=True`` describes K, ``deconvolve=False`` (the detector's
+    response) 1 / K.  ``tau`` is a scalar or one value per timestream, in seconds.
+
+    An instance is a valid ``kernel_func`` -- ``kernel(indx, freqs)`` returns the complex128 kernel of timestream
+    ``indx`` with the reference's three statements -- and the one kind of ``kernel_func`` that :func:`convolve` runs
+    on the device (``toast_hip_fft_convolve_pole``: one double per detector, evaluated per bin inside the multiply
+    stage of either FFT pipeline, no table)."""
+
+    def __init__(self, tau, deconvolve=False):
+        self.tau = np.array(tau, dtype=np.float64)
+        if self.tau.ndim > 1:
+            raise RuntimeError("tau should be a scalar or one value per timestream")
+        self.deconvolve = bool(deconvolve)
+
+    def taus(self, n_tod):
+        """The ``n_tod`` time constants (a scalar broadcasts)."""
+        if self.tau.ndim == 0:
+            return np.full(n_tod, float(self.tau), dtype=np.float64)
+        if self.tau.shape[0] != n_tod:
+            raise RuntimeError("tau should have one value per timestream")
+        return np.ascontiguousarray(self.tau)
+
+    def __call__(self, indx, freqs):
+        tau = float(self.tau) if self.tau.ndim == 0 else float(self.tau[indx])
+        kernel = np.zeros(len(freqs), dtype=np.complex128)
+        kernel.real[:] = 1
+        kernel.imag[:] = 2.0 * np.pi * tau * freqs
+        if not self.deconvolve:
+            kernel = 1.0 / kernel
+        return kernel
+
+
+def _apod_for(n_samp):
+    n_fft = fft_length(n_samp)
+    return apodization(min((n_fft - n_samp) // 2, n_samp))
+
+
+def convolve_buffer_pole(det_data, data_index, rate, tau, invert=True, use_accel=False):
+    """Rows ``data_index`` of the 2-D float64 buffer ``det_data`` in place through the single-pole kernels of
+    ``tau`` (seconds; scalar or one per entry of ``data_index`` -- by position in that list, not by buffer row):
+    multiplied by 1 / (1 + i 2 pi tau f) with ``invert`` (the detector's response), by 1 + i 2 pi tau f without."""
+    from .accel import ensure_assigned
+
+    ensure_assigned()
+    det_data = capi._buf(det_data, "det_data", np.float64, 2)
+    di = capi._buf(np.ascontiguousarray(data_index, dtype=np.int32), "data_index", np.int32, 1)
+    n_det, n_samp = di.size, det_data.shape[1]
+    taus = SinglePole(tau).taus(n_det)
+    apod = _apod_for(n_samp)
+    capi._check(capi.lib().toast_hip_fft_convolve_pole(
+        _p(det_data), C.c_int64(det_data.shape[0]), _p(di), C.c_int64(n_det), C.c_int64(n_samp), C.c_double(rate),
+        _p(taus), C.c_int(bool(invert)), _p(apod), C.c_int64(apod.size), C.c_int(bool(use_accel))))
+
+
+def convolve_pole_dev(d_det_data, data_index, n_samp, rate, tau, invert=True, max_batch=0, stream=0):
+    """Device-pointer variant of :func:`convolve_buffer_pole` (``d_det_data`` = device address of a [rows, n_samp]
+    f64 array)."""
+    di = np.ascontiguousarray(data_index, dtype=np.int32)
+    taus = SinglePole(tau).taus(di.size)
+    apod = _apod_for(n_samp)
+    capi._check(capi.lib().toast_hip_fft_convolve_pole_dev(
+        C.c_void_p(int(d_det_data)), _p(di), C.c_int64(di.size), C.c_int64(n_samp), C.c_double(rate), _p(taus),
+        C.c_int(bool(invert)), _p(apod), C.c_int64(apod.size), C.c_int64(max_batch), C.c_void_p(int(stream))))
+
+
+def impulse_extents_pole(n_tod, n_samp, rate, tau, invert=True):
+    """:func:`impulse_extents` for single-pole kernels (``toast_hip_fft_impulse_extents_pole``)."""
+    from .accel import ensure_assigned
+
+    ensure_assigned()
+    taus = SinglePole(tau).taus(n_tod)
+    # the width is a function of tau alone: detectors sharing a time constant share one measurement
+    uniq, inverse = np.unique(taus, return_inverse=True)
+    apod = _apod_for(n_samp)
+    out = np.zeros(uniq.size, dtype=np.int32)
+    capi._check(capi.lib().toast_hip_fft_impulse_extents_pole(
+        C.c_int64(uniq.size), C.c_int64(n_samp), C.c_double(rate), _p(uniq), C.c_int(bool(invert)), _p(apod),
+        C.c_int64(apod.size), _p(out), C.c_void_p(0)))
+    return out[np.ravel(inverse)]
+
+
 def extend_flags(flags, mask, buffer):
     """Grow every flagged region by ``buffer`` samples on both sides
     (reference: src/toast/utils.py:1055-1113).  The reference loops over the regions and ASSIGNS the mask to
@@ -257,15 +340,27 @@ def convolve(raw, rate, flags=None, flag_mask=None, kernel_freq=None, kernels=No
     """Drop-in for ``toast.fft.convolve`` (2-D ``raw`` = one row per timestream, in place).
 
     ``algorithm`` "numpy"/"internal"/None all map to the rocFFT pipeline (they are the same
-    mathematics in the reference: fft.py:296-350 vs :396-484); "nonuniform" and
-    ``kernel_func`` are not part of the hot path and raise.
+    mathematics in the reference: fft.py:296-350 vs :396-484); "nonuniform" is not part of the hot path and raises.
+
+    ``kernel_func`` may be a :class:`SinglePole`: the analytic time-constant kernel, evaluated on the device
+    (reference fft.py:318-336 with the kernel function of ops/time_constant.py:155-168).  ``deconvolve=True`` then
+    divides by whatever the object describes, as the reference would.  Such a call always runs the default row passes
+    of the fused kernels: ``set_rows_mode`` / ``set_rows_n2`` / the row entry of ``set_points`` do not apply to it
+    (``select`` does).  Any other callable raises: the reference evaluates those on the host.
     """
+    pole = None
     if kernel_func is not None:
-        raise NotImplementedError("kernel_func kernels are evaluated on the host in the reference; not supported")
+        # argument checks as the reference's (fft.py:774-781)
+        if kernel_freq is not None or kernels is not None:
+            raise RuntimeError("Cannot specify both the kernel function and explicit kernel values")
+        if not isinstance(kernel_func, SinglePole):
+            raise NotImplementedError("kernel_func kernels are evaluated on the host in the reference; only "
+                                      "SinglePole is supported")
+        pole = kernel_func
+    elif kernel_freq is None or kernels is None:
+        raise RuntimeError("Must specify either the kernel function or explicit kernel values")
     if algorithm not in (None, "numpy", "internal"):
         raise RuntimeError(f"Unknown or unsupported algorithm '{algorithm}'")
-    if kernel_freq is None or kernels is None:
-        raise RuntimeError("Must specify explicit kernel values")
     if (flags is None) != (flag_mask is None):
         raise RuntimeError("Both flags and flag_mask must be specified or set to None")
     raw = np.asarray(raw)
@@ -276,12 +371,22 @@ def convolve(raw, rate, flags=None, flag_mask=None, kernel_freq=None, kernels=No
     n_tod, n_samp = data.shape
     idx = np.arange(n_tod, dtype=np.int32)
     extend = np.zeros(n_tod, dtype=np.int32)
+    if pole is not None:
+        taus = pole.taus(n_tod)
+        # the object describes K (deconvolve) or 1 / K; dividing by it turns one into the other
+        invert = (not pole.deconvolve) != bool(deconvolve)
     if flags is not None:
         # impulse response spread (fft.py:836-872), through the same GPU pipeline, measured on the device
-        extend[:] = impulse_extents(n_tod, n_samp, rate, kernel_freq, kernels, deconvolve)
+        if pole is not None:
+            extend[:] = impulse_extents_pole(n_tod, n_samp, rate, taus, invert)
+        else:
+            extend[:] = impulse_extents(n_tod, n_samp, rate, kernel_freq, kernels, deconvolve)
         if np.any(extend == n_samp):
             raise RuntimeError("Impulse response spreads to all samples")
-    convolve_buffer(data, idx, rate, kernel_freq, kernels, deconvolve, use_accel=use_accel)
+    if pole is not None:
+        convolve_buffer_pole(data, idx, rate, taus, invert, use_accel=use_accel)
+    else:
+        convolve_buffer(data, idx, rate, kernel_freq, kernels, deconvolve, use_accel=use_accel)
     if flags is not None:
         if isinstance(flags, np.ndarray) and flags.ndim == 2 and flags.dtype == np.uint8 and flags.flags["C_CONTIGUOUS"]:
             extend_flags_buffer(flags, idx, flag_mask, extend)

@@ -10,6 +10,7 @@ configs[4] is upstream of this path and is not part of
                                                [--polyfilter ORDER] [--polyfilter2d ORDER [--polyfilter2d-key COLUMN]]
                                                [--common-mode] [--save-map FILE]
                                                [--subharmonic ORDER] [--periodic-az BINS] [--fourier2d ORDER]
+                                               [--time-constant MS [--time-constant-sigma S]]
 """
 import argparse
 import os
@@ -66,6 +67,12 @@ def main(argv=None):
     ap.add_argument("--sim-noise", action="store_true",
                     help="draw the detector noise on the device with ops.SimNoise from the observation's AnalyticNoise "
                          "instead of host white noise (off by default)")
+    ap.add_argument("--time-constant", type=float, default=None, metavar="MS",
+                    help="give every detector a single-pole time constant around MS milliseconds (focalplane column `tau`), "
+                         "convolve the simulated signal with it (ops.TimeConstant) and deconvolve it again with "
+                         "ops.TimeConstant(deconvolve=True) before the filters; prints the residual (off by default)")
+    ap.add_argument("--time-constant-sigma", type=float, default=0.0, metavar="S",
+                    help="with --time-constant: relative Gaussian spread of the time constants across the focal plane")
     ap.add_argument("--save-map", default=None, metavar="FILE", help="save the binned map as a .npy file")
     args = ap.parse_args(argv)
     n_samp = int(args.minutes * 60 * args.rate)
@@ -110,6 +117,33 @@ def main(argv=None):
         ops.SimNoise(noise_model=defaults.noise_model).apply(data, use_accel=True)
         lap("SimNoise")
         sig = ob.detdata[defaults.det_data].data
+    if args.time_constant is not None:
+        n_keep = min(8, sig.shape[0])
+        untouched = np.array(sig[:n_keep])
+        tau_rng = np.random.default_rng(2)
+        for o in data.obs:
+            fp = o.telescope.focalplane
+            for d in fp.detectors:
+                fp[d]["tau"] = 1.0e-3 * args.time_constant * (1.0 + args.time_constant_sigma * tau_rng.standard_normal())
+        # the detectors' response: no flags are involved in making the signal
+        ops.TimeConstant(tau_name="tau", det_flags=None, name="timeconstant_sim").apply(data)
+        lap("TimeConstant (convolve; first call: upload)")
+        ops.TimeConstant(tau_name="tau", deconvolve=True, name="timeconstant").apply(data)
+        lap("TimeConstant (deconvolve)")
+        sig = ob.detdata[defaults.det_data].data
+        dflags = ob.detdata[defaults.det_flags].data
+        diffs = []
+        for d in range(n_keep):
+            ok = (dflags[d] & defaults.det_mask_invalid) == 0
+            diffs.append((sig[d] - untouched[d])[ok])
+        # both calls remove the mean of the padded series: the difference is an offset per detector plus the residual
+        offsets = [float(np.mean(x)) for x in diffs]
+        resid = float(np.sqrt(np.mean(np.concatenate([x - m for x, m in zip(diffs, offsets)]) ** 2)))
+        taus = [ob.telescope.focalplane[d]["tau"] for d in ob.local_detectors]
+        print(f"time constants {1e3 * min(taus):.3f} .. {1e3 * max(taus):.3f} ms: convolved and deconvolved, rms residual "
+              f"against the untouched signal {resid:.3e} (first {n_keep} detectors, unflagged samples, mean offset "
+              f"{np.mean(offsets):.3f} removed; signal rms {float(np.std(untouched)):.2f})")
+        del untouched, diffs
     good = (ob.shared[defaults.shared_flags].data & 1) == 0
     rms_before = float(np.std(sig[0][good]))
     if args.polyfilter is not None:
