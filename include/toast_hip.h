@@ -924,6 +924,10 @@ int toast_hip_common_mode_subtract_dev(
 #define TOAST_HIP_POLY2D_TRUNCATED 2
 #define TOAST_HIP_POLY2D_NOT_FINITE 3
 int toast_hip_filter_poly2d_max_order(void);
+/* Sample tiles (of 256 samples) that one batch of toast_hip_filter_poly2d_dev holds for this order and number of groups,
+ * before it is clipped to the tiles of a call: the scratch of a batch stays below 96 MiB.  Host arithmetic, the launcher's
+ * own; 0 for an order or a group count the entry refuses. */
+int64_t toast_hip_filter_poly2d_batch_tiles(int64_t order, int64_t n_group);
 /* Measurement aid (tools/bench_filters.py): while on, every toast_hip_filter_poly2d_dev call brackets its three phases
  * with device events, waits for them and adds the times up.  The call returns the sums so far -- ms_out[3]: moments,
  * solve, subtraction; may be NULL --, clears them and switches the timing on or off.  Off by default. */
@@ -1029,6 +1033,10 @@ int toast_hip_periodic_apply_precond_dev(int64_t n_amp, const int32_t * d_hits, 
  *                   2 * nmode * n_fft doubles; d_amp_in / d_amp_out point at the view's first amplitude.
  * ---------------------------------------------------------------------------------- */
 int toast_hip_fourier2d_max_modes(void);
+/* Detector groups (grid.y) that add_to_signal and project_signal launch for n_det detectors over n_tile sample tiles
+ * (a view of len samples has ceil(len / 256)) when asked for n_group (0 = by the rule).  Host arithmetic, the launchers'
+ * own; 0 without detectors or tiles. */
+int64_t toast_hip_fourier2d_groups(int64_t n_det, int64_t n_tile, int64_t n_group);
 int toast_hip_fourier2d_add_to_signal_dev(
     int64_t nmode, const double * d_templates, const int64_t * view_amp_offsets /*host*/, const double * d_amplitudes,
     const int32_t * data_index /*host*/, int64_t n_det, double * d_det_data, int64_t n_samp,

@@ -49,17 +49,20 @@ def detector_groups(n_det, n_group):
     return ((np.arange(n_det) // 2) % n_group).astype(np.int32)
 
 
-def case_templates(n_det, n_group, order, fov_deg=10.0):
-    """-> (templates [n_det][(order + 1)^2], det_group, quats)."""
+def case_templates(n_det, n_group, order, fov_deg=10.0, det_group=None):
+    """-> (templates [n_det][(order + 1)^2], det_group, quats).  ``det_group``: any assignment of the detectors to
+    0 .. n_group - 1 instead of ``detector_groups``; a group may be empty."""
     from toast_amd.data import detector_direction
     from toast_amd.synth import hex_focalplane
 
     quats, _ = hex_focalplane(n_det, fov_deg=fov_deg)
     xy = np.array([detector_direction(q)[:2] for q in quats])
     theta, phi = np.arcsin(xy[:, 0]), np.arcsin(xy[:, 1])
-    det_group = detector_groups(n_det, n_group)
+    det_group = detector_groups(n_det, n_group) if det_group is None else np.asarray(det_group, dtype=np.int32)
     for g in range(n_group):
         members = np.flatnonzero(det_group == g)
+        if members.size == 0:
+            continue
         t_off, p_off = 0, 0
         for d in members:                     # summed one by one, like the reference
             t_off += theta[d]
@@ -200,28 +203,31 @@ def jacobi_solve(moments, proj, order):
             if done.all():
                 break
             sweeps += 1
+            # the systems still sweeping, system index last: every pair is a handful of contiguous vector operations,
+            # with the arithmetic of the lanes that rotate and a select for those that do not
+            act = np.flatnonzero(~done)
+            aa, va = a[act].transpose(1, 2, 0).copy(), v[act].transpose(1, 2, 0).copy()
             for p in range(n - 1):
                 for q in range(p + 1, n):
-                    apq = a[:, p, q]
-                    k = np.flatnonzero(~done & (apq != 0.0))
-                    if k.size == 0:
+                    apq = aa[p, q]
+                    rot = apq != 0.0
+                    if not rot.any():
                         continue
-                    app, aqq, apq = a[k, p, p], a[k, q, q], apq[k]
                     with np.errstate(over="ignore", invalid="ignore", divide="ignore"):
-                        theta = (aqq - app) / (2.0 * apq)
+                        theta = (aa[q, q] - aa[p, p]) / (2.0 * apq)
                         t = np.where(theta >= 0.0, 1.0, -1.0) / (np.abs(theta) + np.sqrt(theta * theta + 1.0))
-                    cs = 1.0 / np.sqrt(t * t + 1.0)
-                    sn = t * cs
-                    cs, sn = cs[:, None], sn[:, None]
-                    for mat in (a, v):
-                        cp, cq = mat[k, :, p].copy(), mat[k, :, q].copy()
-                        mat[k, :, p] = cs * cp - sn * cq
-                        mat[k, :, q] = sn * cp + cs * cq
-                    rp, rq = a[k, p, :].copy(), a[k, q, :].copy()
-                    a[k, p, :] = cs * rp - sn * rq
-                    a[k, q, :] = sn * rp + cs * rq
-                    a[k, p, q] = 0.0
-                    a[k, q, p] = 0.0
+                        cs = 1.0 / np.sqrt(t * t + 1.0)
+                        sn = t * cs
+                        for mat in (aa, va):
+                            cp, cq = mat[:, p].copy(), mat[:, q].copy()
+                            mat[:, p] = np.where(rot, cs * cp - sn * cq, cp)
+                            mat[:, q] = np.where(rot, sn * cp + cs * cq, cq)
+                        rp, rq = aa[p].copy(), aa[q].copy()
+                        aa[p] = np.where(rot, cs * rp - sn * rq, rp)
+                        aa[q] = np.where(rot, sn * rp + cs * rq, rq)
+                    aa[p, q] = np.where(rot, 0.0, aa[p, q])
+                    aa[q, p] = np.where(rot, 0.0, aa[q, p])
+            a[act], v[act] = aa.transpose(2, 0, 1), va.transpose(2, 0, 1)
     lam = a[:, eye]
     lmax = np.max(lam, axis=1) if n > 0 else np.zeros(n_sys)
     lmax = np.maximum(lmax, 0.0)
@@ -261,19 +267,21 @@ def emulate(case, with_flags=True):
         np.broadcast_to(((case["shared"][samples] & SHARED_MASK) == 0)[None, :], (case["n_det"], samples.size)).copy()
     coeff = np.zeros((case["n_samp"], n_group, n_mode))
     status = np.full((case["n_samp"], n_group), -1, dtype=np.int32)
-    most = 0
+    # the systems of all groups go through one solve: a system's result does not depend on the others of the call
+    m_acc = np.zeros((n_group, samples.size, nm2))
+    b_acc = np.zeros((n_group, samples.size, n_mode))
     for g in range(n_group):
-        members = np.flatnonzero(case["det_group"] == g)
-        m_acc = np.zeros((samples.size, nm2))
-        b_acc = np.zeros((samples.size, n_mode))
-        for d in members:
+        for d in np.flatnonzero(case["det_group"] == g):
             sel = good[d][:, None]
             val = signal[case["sig_rows"][d], samples]
-            m_acc += np.where(sel, mom[d][None, :], 0.0)
+            m_acc[g] += np.where(sel, mom[d][None, :], 0.0)
             with np.errstate(invalid="ignore"):
-                b_acc += np.where(sel, t[d][None, :] * val[:, None], 0.0)
-        c, st, sweeps = jacobi_solve(m_acc, b_acc, order)
-        most = max(most, sweeps)
+                b_acc[g] += np.where(sel, t[d][None, :] * val[:, None], 0.0)
+    c_all, st_all, most = jacobi_solve(m_acc.reshape(-1, nm2), b_acc.reshape(-1, n_mode), order)
+    c_all, st_all = c_all.reshape(n_group, samples.size, n_mode), st_all.reshape(n_group, samples.size)
+    for g in range(n_group):
+        members = np.flatnonzero(case["det_group"] == g)
+        c, st = c_all[g], st_all[g]
         coeff[samples, g] = c
         status[samples, g] = st
         zero = np.all(c == 0.0, axis=1)
@@ -334,16 +342,17 @@ def listed_signal(case, buffer):
     return buffer[case["sig_rows"]]
 
 
-def load_fixture():
+def load_fixture(file="poly2d.npz"):
     import os
 
-    z = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "poly2d.npz"), allow_pickle=False)
+    z = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", file), allow_pickle=False)
     return {k: z[k] for k in z.files}
 
 
-def fixture_case(fix, name):
-    """-> (case, reference coefficients [n_samp][n_group][n_mode], excluded [n_view_samples][n_group], bounds dict)."""
-    case = build_case(name, int(fix[f"{name}_seed"]))
+def fixture_case(fix, name, build=None):
+    """-> (case, reference coefficients [n_samp][n_group][n_mode], excluded [n_view_samples][n_group], bounds dict).
+    ``build(name, seed)``: the builder of the fixture's cases, ``build_case`` by default."""
+    case = (build_case if build is None else build)(name, int(fix[f"{name}_seed"]))
     samples = view_samples(case)
     coeff = np.zeros((case["n_samp"], case["n_group"], case["n_mode"]))
     coeff[samples] = fix[f"{name}_coeff"]

@@ -121,6 +121,8 @@ def lib():
         _lib.toast_hip_last_error.restype = C.c_char_p
         _lib.toast_hip_version.restype = C.c_char_p
         _lib.toast_hip_sim_noise_fft_length.restype = C.c_int64
+        _lib.toast_hip_filter_poly2d_batch_tiles.restype = C.c_int64
+        _lib.toast_hip_fourier2d_groups.restype = C.c_int64
     return _lib
 
 
@@ -1427,6 +1429,11 @@ class _Dev:
         """Largest ``order`` the PolyFilter2D kernels take; beyond it the operator runs its host path."""
         return int(real_lib().toast_hip_filter_poly2d_max_order())
 
+    def filter_poly2d_batch_tiles(self, order, n_group):
+        """Sample tiles of 256 samples per batch of ``filter_poly2d``, before clipping to the tiles of a call: the
+        launcher's own figure (host arithmetic)."""
+        return int(real_lib().toast_hip_filter_poly2d_batch_tiles(_i64(order), _i64(n_group)))
+
     def filter_poly2d_profile(self, on):
         """Switch the per-phase device-event timing of ``filter_poly2d`` on or off; returns the milliseconds summed since
         the last call as ``[moments, solve, subtract]`` and clears them."""
@@ -1556,6 +1563,11 @@ class _Dev:
     def fourier2d_max_modes(self):
         """Most modes per sample the Fourier2D kernels take."""
         return int(real_lib().toast_hip_fourier2d_max_modes())
+
+    def fourier2d_groups(self, n_det, n_tile, n_group=0):
+        """Detector groups ``fourier2d_add_to_signal`` / ``fourier2d_project_signal`` launch for ``n_det`` detectors over
+        ``n_tile`` sample tiles of 256 samples when asked for ``n_group`` (0: the rule).  Host arithmetic."""
+        return int(real_lib().toast_hip_fourier2d_groups(_i64(n_det), _i64(n_tile), _i64(n_group)))
 
     def fourier2d_add_to_signal(self, nmode, d_templates, view_amp_offsets, d_amplitudes, data_index, d_det_data, n_samp,
                                 intervals, n_group=0, stream=0):

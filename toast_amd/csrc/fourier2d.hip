@@ -321,6 +321,12 @@ extern "C" {
 
 int toast_hip_fourier2d_max_modes(void) { return kF2dMaxModes; }
 
+int64_t toast_hip_fourier2d_groups(int64_t n_det, int64_t n_tile, int64_t n_group) {
+    if (n_det < 1 || n_tile < 1) return 0;
+    const int64_t dpg = f2d_det_per_group(n_det, n_tile, n_group);
+    return (n_det + dpg - 1) / dpg;
+}
+
 int toast_hip_fourier2d_add_to_signal_dev(int64_t nmode, const double * d_templates, const int64_t * view_amp_offsets,
                                           const double * d_amplitudes, const int32_t * data_index, int64_t n_det,
                                           double * d_det_data, int64_t n_samp, const toast_hip_interval * intervals,

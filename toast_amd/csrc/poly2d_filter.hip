@@ -327,13 +327,26 @@ struct P2dArgs {
     hipStream_t st;
 };
 
+// bytes of scratch per sample tile: for every slot and group the packed system, the coefficients, and the status (half a
+// double)
+template <int ORDER>
+size_t p2d_tile_bytes(int64_t n_group) {
+    using P = P2d<ORDER>;
+    return (size_t)kThreads * (size_t)n_group * (sizeof(double) * (P::NV + P::N) + sizeof(int32_t));
+}
+
+// sample tiles per batch, before clipping to the tiles of the call: what keeps the scratch below kP2dScratchBytes
+template <int ORDER>
+int64_t p2d_batch_tiles(int64_t n_group) {
+    const int64_t batch = (int64_t)(kP2dScratchBytes / p2d_tile_bytes<ORDER>(n_group));
+    return (batch < 1) ? 1 : batch;
+}
+
 template <int ORDER>
 void p2d_launch(const P2dArgs & a) {
     using P = P2d<ORDER>;
-    // doubles per slot and group: the packed system, the coefficients, and the status (half a double)
-    const size_t per_tile = (size_t)kThreads * (size_t)a.n_group * (sizeof(double) * (P::NV + P::N) + sizeof(int32_t));
-    int64_t batch = (int64_t)(kP2dScratchBytes / per_tile);
-    if (batch < 1) batch = 1;
+    const size_t per_tile = p2d_tile_bytes<ORDER>(a.n_group);
+    int64_t batch = p2d_batch_tiles<ORDER>(a.n_group);
     if (batch > a.n_tile) batch = a.n_tile;
     const int64_t n_slot_max = batch * kThreads;
     char * scratch = static_cast<char *>(Manager::get().scratch(Manager::kScratchPoly, per_tile * (size_t)batch, a.st));
@@ -383,6 +396,16 @@ void p2d_launch(const P2dArgs & a) {
 extern "C" {
 
 int toast_hip_filter_poly2d_max_order(void) { return kP2dMaxOrder; }
+
+int64_t toast_hip_filter_poly2d_batch_tiles(int64_t order, int64_t n_group) {
+    if (order < 0 || order > kP2dMaxOrder || n_group < 1 || n_group > 65535) return 0;
+    switch (order) {
+        case 0: return p2d_batch_tiles<0>(n_group);
+        case 1: return p2d_batch_tiles<1>(n_group);
+        case 2: return p2d_batch_tiles<2>(n_group);
+        default: return p2d_batch_tiles<3>(n_group);
+    }
+}
 
 int toast_hip_filter_poly2d_profile(int on, double * ms_out) {
     return guarded([&] {
