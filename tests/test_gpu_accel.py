@@ -333,9 +333,9 @@ def test_mapmaker_leaves_solution_and_offset_variances_on_the_device():
     data, tmpl = run(True)
     amps = data["mm_solve_amplitudes"]["baselines"]
     assert amps.accel_in_use()                                 # not copied back by the solver
-    assert getattr(tmpl, "_offsetvar_stale", False)            # computed on the device, host copy pending
+    assert tmpl._mirrors["offsetvar"].stale                    # computed on the device, host copy pending
     var_dev = np.array(tmpl._offsetvar)                        # fetched now
-    assert not tmpl._offsetvar_stale
+    assert not tmpl._mirrors["offsetvar"].stale
     # the host-side form of the same initialisation on the same data (keep_solver_products: the solver flags are still there)
     host = Offset(step_time=20.0, noise_model=defaults.noise_model, name="host_side", good_fraction=0.2)
     for trait in ("view", "det_data", "det_flags", "det_flag_mask", "det_mask"):

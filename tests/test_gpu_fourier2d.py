@@ -266,7 +266,7 @@ def test_class_on_resident_buffers(name):
     dets = tmpl.detectors()
     assert tmpl._n_local == int(GOLD[f"{name}_n_local"])
     # the norms were computed on the device at set-up and stay there
-    assert tmpl._norms_on_dev and tmpl._norms_stale
+    assert tmpl._mirrors["norms"].on_device and tmpl._mirrors["norms"].stale
     # so were the prior's spectra and work rows: the PCG loop allocates nothing
     assert tmpl._work[0] != 0 and len(tmpl._prior_views) == sum(len(v) for v in fc.view_samples(layout))
     assert np.array_equal(tmpl._norms.reshape(-1, nmode)[rows], GOLD[f"{name}_norms"])

@@ -279,16 +279,17 @@ def test_periodic_device_matches_reference(name):
     data, tmpl = _periodic(name)
     dets = tmpl.detectors()
     assert tmpl._n_local == int(GOLD[f"{name}_n_local"])
-    assert np.array_equal([tmpl._det_offset[d] for d in dets], GOLD[f"{name}_det_offset"])
+    assert np.array_equal([tmpl._det_start[d] for d in dets], GOLD[f"{name}_det_offset"])
     assert np.array_equal([tmpl._obs_nbins[i] for i in range(len(data.obs))], GOLD[f"{name}_obs_nbins"])
     # hits and flags were counted on the device; the index rows were computed there
-    assert tmpl._hits_on_dev
+    assert tmpl._mirrors["hits"].on_device
     assert np.array_equal(tmpl._amp_hits, GOLD[f"{name}_hits"])
     assert np.array_equal(tmpl._amp_flags.astype(np.uint8), GOLD[f"{name}_flags"])
     assert np.any(tmpl._amp_flags & (tmpl._amp_hits >= tmpl.minimum_bin_hits))
     for iob, ob in enumerate(data.obs):
-        assert tmpl._index_on_dev[iob] == "device"
+        assert tmpl._index[iob].on_device and tmpl._index[iob].stale
         assert np.array_equal(tmpl._host_index(iob, ob)[0], GOLD[f"{name}_index_obs{iob}"])
+        assert not tmpl._index[iob].stale
     _to_device(data)
     exact, scale = _periodic_terms(name)
     results = {}
@@ -315,6 +316,75 @@ def test_periodic_device_matches_reference(name):
     tmpl.clear()
     for z in (again, amps, out):
         z.clear()
+
+
+@pytest.mark.parametrize("sequence", ["written_on_device", "uploaded_then_dropped", "never_registered"])
+def test_device_mirror(sequence):
+    """The coherence states of ``DeviceMirror`` on eight float64 values."""
+    from toast_amd import capi
+    from toast_amd.accel import accel_data_present
+    from toast_amd.templates import DeviceMirror
+
+    values = np.arange(8, dtype=np.float64) + 1.0
+    if sequence == "written_on_device":
+        mirror, x = DeviceMirror(np.full(8, 9.0), "test_mirror").create(zero_out=True), Dev(values)
+        assert mirror.on_device and not mirror.stale
+        capi.dev.vec_axpby(8, 2.0, x.ptr, 1.0, mirror.ptr)       # 2 x onto the zeros (toast_hip_vec_axpby_dev)
+        mirror.written()
+        assert mirror.stale and np.array_equal(mirror.buffer, np.full(8, 9.0))
+        assert np.array_equal(mirror.host, 2.0 * values) and not mirror.stale
+        mirror.buffer[0] = -1.0
+        assert mirror.host[0] == -1.0                            # (a second fetch would bring the 2 back)
+        x.free()
+        mirror.drop()
+    elif sequence == "uploaded_then_dropped":
+        mirror, y = DeviceMirror(values.copy(), "test_mirror"), Dev(np.zeros(8))
+        assert mirror.upload() is mirror and mirror.on_device and not mirror.stale
+        assert accel_data_present(mirror.buffer, mirror.name)
+        capi.dev.vec_axpby(8, 1.0, mirror.upload().ptr, 0.0, y.ptr)
+        assert np.array_equal(y.get(), values)
+        y.free()
+        mirror.drop()
+        assert np.array_equal(mirror.host, values)
+    else:
+        mirror = DeviceMirror(values.copy(), "test_mirror")
+        mirror.drop()
+        assert np.array_equal(mirror.host, values)
+    assert not mirror.on_device and not mirror.stale and not accel_data_present(mirror.buffer, mirror.name)
+
+
+@pytest.mark.parametrize("kind", ["offset", "subharmonic", "periodic"])
+def test_clear_releases_what_the_template_registered(kind):
+    """``clear()`` leaves nothing of the template on the device, and a second ``_initialize`` gives the same
+    preconditioner bit for bit (Fourier2D: test_gpu_fourier2d.py, through ``device_tables()``)."""
+    from toast_amd.accel import accel_data_present
+    from toast_amd.templates import Offset, Periodic, SubHarmonic
+
+    data = tc.build("tiny")
+    tmpl = {"offset": lambda: Offset(name="off", step_time=5.0, noise_model=tc.NOISE),
+            "subharmonic": lambda: SubHarmonic(name="sub", **tc.SUBHARMONIC_CASES["sub0"][1]),
+            "periodic": lambda: Periodic(name="per", **tc.PERIODIC_CASES["per_bins"][1])}[kind]()
+    tc.configure(tmpl).data = data
+
+    def precond():
+        amps, out = _resident(tmpl, tc.amplitudes(tmpl._n_local, 3)), _resident(tmpl, -3.0)
+        tmpl.apply_precond(amps, out)
+        assert out.accel_in_use()
+        result = out.local.copy()
+        amps.clear()
+        out.clear()
+        return result
+
+    first = precond()
+    assert np.any(first != -3.0)
+    mirrors = list(tmpl._mirrors.values()) + list(getattr(tmpl, "_index", {}).values())
+    assert len(mirrors) == (3 if kind == "periodic" else 1)
+    assert all(m.on_device and accel_data_present(m.buffer, m.name) for m in mirrors)
+    tmpl.clear()
+    assert not any(m.on_device or m.stale or accel_data_present(m.buffer, m.name) for m in mirrors)
+    tmpl._initialize(data)
+    assert np.array_equal(precond(), first)
+    tmpl.clear()
 
 
 def test_periodic_per_detector_key_device_equals_host_path():

@@ -92,7 +92,7 @@ def test_subharmonic_host_matches_reference(name):
 def test_periodic_host_matches_reference(name):
     data, tmpl = _periodic(name)
     assert tmpl._n_local == int(GOLD[f"{name}_n_local"])
-    assert np.array_equal([tmpl._det_offset[d] for d in tmpl.detectors()], GOLD[f"{name}_det_offset"])
+    assert np.array_equal([tmpl._det_start[d] for d in tmpl.detectors()], GOLD[f"{name}_det_offset"])
     n_obs = len(data.obs)
     assert np.array_equal([tmpl._obs_min[i] for i in range(n_obs)], GOLD[f"{name}_obs_min"])
     assert np.array_equal([tmpl._obs_max[i] for i in range(n_obs)], GOLD[f"{name}_obs_max"])
@@ -133,7 +133,42 @@ def test_layout_detector_missing_from_an_observation():
     assert sub._det_start == {"d0": 0, "d1": per_view * sum(n_view), "d2": per_view * (sum(n_view) + n_view[0])}
     assert sub._n_local == per_view * (2 * sum(n_view) + n_view[0])
     data, per = _periodic("per_bins")
-    assert per._det_offset == {"d0": 0, "d1": 14, "d2": 21} and per._n_local == 35
+    assert per._det_start == {"d0": 0, "d1": 14, "d2": 21} and per._n_local == 35
+
+
+def test_obs_detectors_field_and_pattern():
+    """``Template._obs_detectors`` on the layout where d1 is missing from the second observation, with a detdata field
+    that lacks d0 and a pattern that excludes d2.  The expected lists were recorded from ``_initialize`` of the four
+    templates when each still had its own selection loop: Offset with the field as its solver flags and Periodic with
+    it as its per-detector key selected the ``also_in`` rows, SubHarmonic and Fourier2D (and the other two without the
+    field) the rows without; ``_all_dets`` gave the order, which is the observation's."""
+    from toast_amd.templates import Fourier2D, Offset, Periodic, SubHarmonic
+
+    data = tc.build("long")
+    for ob in data.obs:
+        ob.detdata.create("partial", dtype=np.float64, detectors=[d for d in ob.local_detectors if d != "d0"])
+        ob.detdata["partial"].data[:] = np.arange(ob.n_local_samples)[None, :]
+    expect = {      # (pattern, also_in) -> the detectors of obs0 and of obs1
+        (None, ()): (["d0", "d1", "d2"], ["d0", "d2"]),
+        (None, ("partial",)): (["d1", "d2"], ["d2"]),
+        ("d[01]", ()): (["d0", "d1"], ["d0"]),
+        ("d[01]", ("partial",)): (["d1"], []),
+        ("d[01]", ("partial", "no_such_field", None)): (["d1"], []),
+    }
+    for cls in (Offset, SubHarmonic, Periodic, Fourier2D):
+        tmpl = tc.configure(cls(name="t"))
+        for (pattern, also_in), lists in expect.items():
+            tmpl.pattern = pattern
+            assert tuple(tmpl._obs_detectors(ob, also_in) for ob in data.obs) == lists, (cls.__name__, pattern, also_in)
+    # and the callers hand over their own field: Offset its solver flags, Periodic its per-detector key
+    per = tc.configure(Periodic(name="p", key="partial", is_detdata_key=True, bins=4))
+    per.data = data
+    assert per._all_dets == ["d1", "d2"] and per._obs_dets == {0: {"d1", "d2"}, 1: {"d2"}}
+    for ob in data.obs:
+        ob.detdata.create("partial_flags", dtype=np.uint8, detectors=ob.detdata["partial"].detectors)
+    off = tc.configure(Offset(name="o", step_time=10.0, pattern="d[01]"), det_flags="partial_flags")
+    off.data = data
+    assert off._all_dets == ["d1"] and off._obs_dets == {0: {"d1"}, 1: set()}
 
 
 def test_template_matrix_runs_both_templates_in_both_directions():
@@ -250,7 +285,7 @@ def test_periodic_per_detector_key():
     assert np.array_equal(tmpl._host_index(0, ob), np.where(good, expect, -1))
     hit_good = good & ((ob.detdata[tc.DET_FLAGS].data & tc.DET_FLAG_MASK) == 0)
     for k, det in enumerate(ob.local_detectors):
-        off = tmpl._det_offset[det]
+        off = tmpl._det_start[det]
         assert np.array_equal(tmpl._amp_hits[off:off + 6], np.bincount(expect[k][hit_good[k]], minlength=6))
     amps = tmpl.zeros()
     amps.local[:] = np.arange(tmpl._n_local) + 1.0

@@ -381,8 +381,57 @@ class AmplitudesMap(dict):
                 v.accel_delete()
 
 
+class DeviceMirror:
+    """A host array that a template derives at set-up, its device copy under one registration name, and which side is
+    current: host only, both, or device newer (then the first ``host`` access fetches the values, once)."""
+
+    def __init__(self, buffer, name):
+        self.buffer = buffer        # the host array WITHOUT synchronisation: the accelerator key
+        self.name = name
+        self.on_device = False      # registered on the device?
+        self.stale = False          # device newer than host?
+
+    def create(self, zero_out=False):
+        """Register without an upload, as the side that kernels write; ``written()`` once they were launched."""
+        accel_data_create(self.buffer, self.name, zero_out=zero_out, owner=self)
+        self.on_device = True
+        return self
+
+    def upload(self):
+        """Make sure the host values are on the device (copied once; the host array does not change afterwards)."""
+        if not self.on_device:
+            self.create()
+            accel_data_update_device(self.buffer, self.name)
+        return self
+
+    @property
+    def ptr(self):
+        return accel_device_ptr(self.buffer)
+
+    def written(self):
+        self.stale = True
+
+    @property
+    def host(self):
+        """The host array, brought up to date first."""
+        if self.stale:
+            self.stale = False
+            accel_data_update_host(self.buffer, self.name)
+        return self.buffer
+
+    def drop(self, fetch=True):
+        """Release the device copy; ``fetch``: somebody may still read the values on the host."""
+        if self.on_device:
+            if fetch:
+                _ = self.host
+            accel_data_delete(self.buffer, self.name)
+        self.on_device = self.stale = False
+
+
 class Template(TraitConfig):
-    """Base class of timestream templates (templates/template.py)."""
+    """Base class of timestream templates (templates/template.py), and what the templates of this package share: the
+    selection of detectors, the detector-major amplitude layout, residency of what a sweep reads, and the device mirrors
+    of the arrays a template derives at set-up (``_mirrors``: key -> DeviceMirror, dropped by ``clear()``)."""
 
     data = Any(None, help="This must be an instance of a Data class (or None)")
     view = Unicode(None, allow_none=True, help="Use this view of the data in all observations")
@@ -394,9 +443,96 @@ class Template(TraitConfig):
     pattern = Unicode(None, allow_none=True, help="Regex pattern to match against detector names. "
                                                   "Only these are projected.")
 
+    def __init__(self, **kwargs):
+        self._mirrors = {}
+        super().__init__(**kwargs)
+
     def _observe_data(self, change):
         if change["new"] is not None:
             self._initialize(change["new"])
+
+    # ---- set-up shared by the templates
+    def _obs_detectors(self, ob, also_in=()):
+        """The local detectors of one observation that this template works on, in the observation's order: not cut by
+        ``det_mask``, present in ``det_data`` and in the detdata fields ``also_in`` (where those exist), matching
+        ``pattern`` (offset.py:226-236)."""
+        det_pat = re.compile(self.pattern) if self.pattern is not None else None
+        # (sets: `d in list` over 1024 detectors twice per detector was 5 ms of Offset._initialize)
+        have = [set(ob.detdata[field].detectors) for field in (self.det_data, *also_in)
+                if field is not None and field in ob.detdata]
+        return [d for d in ob.select_local_detectors(flagmask=self.det_mask)
+                if all(d in h for h in have) and (det_pat is None or det_pat.match(d) is not None)]
+
+    def _layout_detector_major(self, comm, per_obs):
+        """Detector-major amplitude layout: the detectors in the order of ``_all_dets``; within a detector, observation
+        ``iob`` contributes ``per_obs[iob]`` amplitudes when it holds the detector (``_obs_dets``)."""
+        self._per_obs = per_obs
+        self._det_start = {}
+        offset = 0
+        for det in self._all_dets:
+            self._det_start[det] = offset
+            for iob, n_amp in per_obs.items():
+                if det in self._obs_dets[iob]:
+                    offset += n_amp
+        self._n_local = offset
+        self._n_global = self._n_local
+        if comm.comm_world is not None:
+            self._n_global = int(comm.allreduce_scalar(self._n_local, op="sum"))
+        self._amp_offset_cache = {}
+
+    def det_amp_offsets(self, iob, dets):
+        """First amplitude of each detector's block for observation ``iob`` (the running ``amp_offset`` of
+        offset.py:727-760), cached."""
+        return block_amp_offsets(self._amp_offset_cache, self._det_start, self._obs_dets, self._per_obs, iob, dets)
+
+    def _det_weights(self, ob, dets):
+        if self.noise_model is not None and self.noise_model in ob:
+            return np.array([float(ob[self.noise_model].detector_weight(d)) for d in dets], dtype=np.float64)
+        return np.ones(len(dets), dtype=np.float64)
+
+    def _supports_accel(self):
+        return True
+
+    def supports_accel(self):
+        return self._supports_accel()
+
+    def _implementations(self):
+        return [ImplementationType.DEFAULT, ImplementationType.COMPILED]
+
+    # ---- residency shared by the templates
+    def _det_flag_args(self, ob, dets, borrowed=None):
+        """(rows of ``dets`` in the solver flags, device pointer of the flags), made resident and current first;
+        (None, 0) without solver flags.  ``borrowed``: see ``make_resident``."""
+        if self.det_flags is None:
+            return None, 0
+        fd = make_resident(ob.detdata[self.det_flags], self.det_flags, borrowed)
+        return fd.indices(dets), accel_device_ptr(fd.buffer)
+
+    def _device_sweep(self, detectors, amplitudes):
+        """The loop of a batched (``*_multi``) sweep on device-resident buffers: makes the amplitudes current on the
+        device and yields (iob, ob, detectors of ``detectors`` in that observation, its ``det_data``) for every
+        observation that holds some of them.  Nothing for a disabled template or one without amplitudes."""
+        if not self._check_enabled() or self._n_local == 0:
+            return
+        amplitudes.accel_resident(f"{self.name}_amps")
+        for iob, ob in enumerate(self.data.obs):
+            dets = [d for d in detectors if d in self._obs_dets[iob]]
+            if len(dets) > 0:
+                yield iob, ob, dets, ob.detdata[self.det_data]
+
+    def _on_device(self, amplitudes_in, amplitudes_out, fn):
+        """Run ``fn`` with both vectors resident; hand the result back to the host when the
+        caller's vectors were host-current (the PCG keeps them resident and skips this)."""
+        stay = amplitudes_in.accel_in_use() or amplitudes_out.accel_in_use()
+        in_was = amplitudes_in.accel_in_use()
+        amplitudes_in.accel_resident(f"{self.name}_amps_in")
+        amplitudes_out.accel_resident(f"{self.name}_amps_out")
+        fn()
+        if not stay:
+            native().accel_synchronize()
+            amplitudes_out.accel_update_host()
+        if not in_was:
+            amplitudes_in.accel_used(False)  # never modified on the device
 
     def initialize(self, new_data):
         self.data = new_data
@@ -428,6 +564,28 @@ class Template(TraitConfig):
         if self._check_enabled():
             self._apply_precond(amplitudes_in, amplitudes_out, **kwargs)
 
+    # One detector at a time: the batched device sweep of the template with that detector alone, or its host method.
+    def _add_to_signal(self, detector, amplitudes, use_accel=None, **kwargs):
+        if detector not in self._all_dets:
+            return
+        if use_accel:
+            self.add_to_signal_multi([detector], amplitudes)
+        else:
+            self._add_to_signal_host(detector, amplitudes)
+
+    def _project_signal(self, detector, amplitudes, use_accel=None, **kwargs):
+        if detector not in self._all_dets:
+            return
+        if use_accel:
+            self.project_signal_multi([detector], amplitudes)
+        else:
+            self._project_signal_host(detector, amplitudes)
+
+    def clear(self):
+        """Release the device copies of this template's mirrors; their host arrays stay readable."""
+        for mirror in self._mirrors.values():
+            mirror.drop()
+
 
 class Offset(Template):
     """One amplitude per detector per ``step_time`` of every view (baseline offsets)."""
@@ -441,28 +599,14 @@ class Offset(Template):
 
     def __init__(self, **kwargs):
         self._flag_cache = {}
+        self._prior = None
         super().__init__(**kwargs)
 
     # The offset variances are computed on the device (``_init_variances_device``) and read there by the preconditioner:
     # the host copy is fetched when somebody asks for it.
     @property
     def _offsetvar(self):
-        if getattr(self, "_offsetvar_stale", False):
-            self._offsetvar_stale = False
-            accel_data_update_host(self._offsetvar_buf, f"{self.name}_offsetvar")
-        return self._offsetvar_buf
-
-    @_offsetvar.setter
-    def _offsetvar(self, value):
-        self._drop_offsetvar_device()
-        self._offsetvar_buf = value
-        self._offsetvar_stale = False
-
-    def _drop_offsetvar_device(self):
-        if getattr(self, "_offsetvar_on_dev", False):
-            accel_data_delete(self._offsetvar_buf, f"{self.name}_offsetvar")
-        self._offsetvar_on_dev = False
-        self._offsetvar_stale = False
+        return self._mirrors["offsetvar"].host
 
     def _step_length(self, stime, rate):
         return int(np.rint(stime * rate))   # offset.py:723-724 (round half to even)
@@ -473,7 +617,7 @@ class Offset(Template):
         # with a noise prior the baselines run through the whole observation and the view only
         # flags samples (offset.py:135-140)
         self._bounds_view = None if self.use_noise_prior else self.view
-        if getattr(self, "_prior", None) is not None:
+        if self._prior is not None:
             self._prior.clear()
         self._prior = None
         self._obs_views, self._obs_view_flags, self._obs_rate, self._obs_dets = {}, {}, {}, {}
@@ -503,38 +647,16 @@ class Offset(Template):
             for vw in ob.intervals[self.view]:
                 vf[vw.first:vw.last] = 0
             self._obs_view_flags[iob] = vf
-            self._obs_dets[iob] = set()
-            det_pat = re.compile(self.pattern) if self.pattern is not None else None
-            # (sets: `d in list` over 1024 detectors twice per detector was 5 ms of this function)
-            have_data = set(ob.detdata[self.det_data].detectors) if self.det_data in ob.detdata else None
-            have_flags = set(ob.detdata[self.det_flags].detectors) \
-                if (self.det_flags is not None and self.det_flags in ob.detdata) else None
-            for d in ob.select_local_detectors(flagmask=self.det_mask):
-                if have_data is not None and d not in have_data:
-                    continue
-                if det_pat is not None and det_pat.match(d) is None:
-                    continue  # offset.py:226-236
-                if have_flags is not None and d not in have_flags:
-                    continue  # no solver flags for it: not part of this (split) run
-                self._obs_dets[iob].add(d)
-                all_dets.setdefault(d, None)
+            # (a detector without solver flags is not part of this (split) run)
+            dets = self._obs_detectors(ob, also_in=(self.det_flags,))
+            self._obs_dets[iob] = set(dets)
+            all_dets.update(dict.fromkeys(dets))
         self._all_dets = list(all_dets.keys())
-        self._det_start = {}
-        view_totals = {iob: int(np.sum(v)) for iob, v in self._obs_views.items()}
-        offset = 0
-        for det in self._all_dets:
-            self._det_start[det] = offset
-            for iob, ob in enumerate(new_data.obs):
-                if det in self._obs_dets[iob]:
-                    offset += view_totals[iob]
-        self._n_local = offset
-        comm = new_data.comm
-        self._n_global = self._n_local
-        if comm.comm_world is not None:
-            self._n_global = int(comm.allreduce_scalar(self._n_local, op="sum"))
+        self._layout_detector_major(new_data.comm, {iob: int(np.sum(v)) for iob, v in self._obs_views.items()})
         self._amp_flags = np.zeros(self._n_local, dtype=np.uint8)
-        self._offsetvar = np.zeros(self._n_local, dtype=np.float64)
-        self._amp_offset_cache = {}
+        for mirror in self._mirrors.values():
+            mirror.drop(fetch=False)      # (initialised before: the old variances go)
+        self._mirrors["offsetvar"] = DeviceMirror(np.zeros(self._n_local, dtype=np.float64), f"{self.name}_offsetvar")
         # offset variance / flags: offset.py:262-343
         from ..accel import accel_enabled
 
@@ -547,8 +669,7 @@ class Offset(Template):
         self._flag_cache = {}
         if self.use_noise_prior and self._n_local > 0:
             # the prior builds its filters from the variances on the host and registers the array under its own name
-            _ = self._offsetvar
-            self._drop_offsetvar_device()
+            self._mirrors["offsetvar"].drop()
             self._init_noise_prior(new_data)
 
     def _init_noise_prior(self, new_data):
@@ -586,7 +707,6 @@ class Offset(Template):
         (toast_hip_offset_count_flagged_dev), flags and variances of all amplitudes from a second one
         (toast_hip_offset_variance_dev); only the two finished vectors come back to the host."""
         from .. import capi
-        from ..accel import accel_data_create, accel_data_delete, accel_data_update_device, accel_data_update_host
 
         # per-amplitude counts of flagged samples: device scratch, never on the host
         bad_bytes = 8 * self._n_local
@@ -594,12 +714,11 @@ class Offset(Template):
         capi.dev.memset(bad_ptr, 0, bad_bytes)
         # an amplitude that no (detector, observation) block claims stays cut, like a baseline without samples
         self._amp_flags[:] = 1
-        flag_name, var_name = f"{self.name}_init_flags", f"{self.name}_offsetvar"
+        flag_name = f"{self.name}_init_flags"
         accel_data_create(self._amp_flags, flag_name)
         accel_data_update_device(self._amp_flags, flag_name)
         # (the variances stay on the device under the name the preconditioner looks for; host copy on demand)
-        accel_data_create(self._offsetvar_buf, var_name, zero_out=True, owner=self)
-        self._offsetvar_on_dev = True
+        var = self._mirrors["offsetvar"].create(zero_out=True)
         try:
             for iob, ob in enumerate(new_data.obs):
                 dets = [d for d in self._all_dets if d in self._obs_dets[iob]]
@@ -621,20 +740,16 @@ class Offset(Template):
                 if self.noise_model is not None:
                     w = np.array([ob[self.noise_model].detector_weight(d) for d in dets], dtype=np.float64)
                 if self.det_flags is not None:
-                    fd = ob.detdata[self.det_flags]
-                    if not fd.accel_in_use():
-                        if not fd.accel_exists():
-                            fd.accel_create(self.det_flags)
-                        fd.accel_update_device()
-                    capi.dev.offset_count_flagged(step_length, offs, self._obs_views[iob], bad_ptr,
-                                                  fd.indices(dets), accel_device_ptr(fd.buffer), self.det_flag_mask,
-                                                  ob.n_local_samples, ob.intervals[self._bounds_view].data)
+                    f_idx, f_ptr = self._det_flag_args(ob, dets)
+                    capi.dev.offset_count_flagged(step_length, offs, self._obs_views[iob], bad_ptr, f_idx, f_ptr,
+                                                  self.det_flag_mask, ob.n_local_samples,
+                                                  ob.intervals[self._bounds_view].data)
                 capi.dev.offset_variance(offs, w, lens, bad_ptr, self.good_fraction,
-                                         accel_device_ptr(self._amp_flags), accel_device_ptr(self._offsetvar_buf))
+                                         accel_device_ptr(self._amp_flags), var.ptr)
             accel_data_update_host(self._amp_flags, flag_name)
-            self._offsetvar_stale = True
+            var.written()
         except BaseException:
-            self._drop_offsetvar_device()
+            var.drop(fetch=False)
             raise
         finally:
             accel_data_delete(self._amp_flags, flag_name)
@@ -680,54 +795,11 @@ class Offset(Template):
         z.local_flags[:] = self._amp_flags
         return z
 
-    def _supports_accel(self):
-        return True
-
-    def supports_accel(self):
-        return self._supports_accel()
-
-    def _implementations(self):
-        return [ImplementationType.DEFAULT, ImplementationType.COMPILED]
-
-    def _amps_to(self, amplitudes, use_accel):
-        if use_accel:
-            if not amplitudes.accel_exists():
-                amplitudes.accel_create(f"{self.name}_amps")
-                amplitudes.accel_update_device()
-            elif not amplitudes.accel_in_use():
-                amplitudes.accel_update_device()
-        elif amplitudes.accel_in_use():
-            amplitudes.accel_update_host()
-
-    def det_amp_offsets(self, iob, dets):
-        """First amplitude of each detector's block for observation ``iob`` (the running
-        ``amp_offset`` of offset.py:727-760), cached."""
-        key = (iob, tuple(dets))
-        cache = self.__dict__.setdefault("_amp_offset_cache", {})
-        if key not in cache:
-            out = []
-            for d in dets:
-                off = self._det_start[d]
-                for job in range(iob):
-                    if d in self._obs_dets[job]:
-                        off += int(np.sum(self._obs_views[job]))
-                out.append(off)
-            cache[key] = np.array(out, dtype=np.int64)
-        return cache[key]
-
     def add_to_signal_multi(self, detectors, amplitudes, **kwargs):
         """All detectors in one launch per observation (device-resident buffers only)."""
         from .. import capi
-        from ..accel import accel_device_ptr
 
-        if not self._check_enabled():
-            return
-        self._amps_to(amplitudes, True)
-        for iob, ob in enumerate(self.data.obs):
-            dets = [d for d in detectors if d in self._obs_dets[iob]]
-            if len(dets) == 0:
-                continue
-            dd = ob.detdata[self.det_data]
+        for iob, ob, dets, dd in self._device_sweep(detectors, amplitudes):
             capi.dev.offset_add_to_signal_multi(
                 self._step_length(self.step_time, self._obs_rate[iob]), self.det_amp_offsets(iob, dets),
                 self._obs_views[iob], accel_device_ptr(amplitudes.buffer), accel_device_ptr(amplitudes.local_flags),
@@ -735,16 +807,8 @@ class Offset(Template):
 
     def project_signal_multi(self, detectors, amplitudes, **kwargs):
         from .. import capi
-        from ..accel import accel_device_ptr
 
-        if not self._check_enabled():
-            return
-        self._amps_to(amplitudes, True)
-        for iob, ob in enumerate(self.data.obs):
-            dets = [d for d in detectors if d in self._obs_dets[iob]]
-            if len(dets) == 0:
-                continue
-            dd = ob.detdata[self.det_data]
+        for iob, ob, dets, dd in self._device_sweep(detectors, amplitudes):
             if self.det_flags is not None:
                 f_idx = ob.detdata[self.det_flags].indices(dets)
                 f_ptr = accel_device_ptr(self._solver_flags(iob, ob, True))
@@ -760,7 +824,8 @@ class Offset(Template):
         if detector not in self._all_dets:
             return
         use_accel = bool(use_accel)
-        self._amps_to(amplitudes, use_accel)
+        if use_accel:
+            amplitudes.accel_resident(f"{self.name}_amps")      # (host-staged: ``arg`` fetches the host values)
         amp_offset = self._det_start[detector]
         for iob, ob in enumerate(self.data.obs):
             if detector not in self._obs_dets[iob]:
@@ -782,11 +847,7 @@ class Offset(Template):
         if use_accel and not self._obs_view_flags[iob].any():
             # no sample lies outside the view: the solver flags ARE the detector flags, and they
             # are used where they live (no 1 B/det-sample round trip through the host)
-            if not fd.accel_in_use():
-                if not fd.accel_exists():
-                    fd.accel_create(self.det_flags)
-                fd.accel_update_device()
-            return fd.buffer
+            return make_resident(fd, self.det_flags).buffer
         if key not in self._flag_cache and use_accel and (self.det_flag_mask & 1) and fd.accel_in_use():
             # device-current flags and a view: (flags & mask) != 0 inside the view, 1 outside, built
             # on the device (toast_hip_combine_flags_dev); equivalent under `& det_flag_mask` to
@@ -817,7 +878,8 @@ class Offset(Template):
         if detector not in self._all_dets:
             return
         use_accel = bool(use_accel)
-        self._amps_to(amplitudes, use_accel)
+        if use_accel:
+            amplitudes.accel_resident(f"{self.name}_amps")      # (host-staged: ``arg`` fetches the host values)
         amp_offset = self._det_start[detector]
         for iob, ob in enumerate(self.data.obs):
             if detector not in self._obs_dets[iob]:
@@ -836,20 +898,6 @@ class Offset(Template):
                                                     n_amp_views, amplitudes.arg(use_accel), amplitudes.local_flags,
                                                     ob.intervals[self._bounds_view].data, use_accel)
             amp_offset += int(np.sum(n_amp_views))
-
-    def _on_device(self, amplitudes_in, amplitudes_out, fn):
-        """Run ``fn`` with both vectors resident; hand the result back to the host when the
-        caller's vectors were host-current (the PCG keeps them resident and skips this)."""
-        stay = amplitudes_in.accel_in_use() or amplitudes_out.accel_in_use()
-        in_was = amplitudes_in.accel_in_use()
-        amplitudes_in.accel_resident(f"{self.name}_amps_in")
-        amplitudes_out.accel_resident(f"{self.name}_amps_out")
-        fn()
-        if not stay:
-            native().accel_synchronize()
-            amplitudes_out.accel_update_host()
-        if not in_was:
-            amplitudes_in.accel_used(False)  # never modified on the device
 
     def _add_prior(self, amplitudes_in, amplitudes_out, use_accel=None, **kwargs):
         if not self.use_noise_prior or self._n_local == 0:
@@ -871,9 +919,9 @@ class Offset(Template):
             # device-resident PCG vectors: the variances are uploaded once per template
             amplitudes_in.accel_resident()
             amplitudes_out.accel_resident()
-            self._offsetvar_to_device()
-            native().template_offset_apply_diag_precond(self._offsetvar_buf, amplitudes_in.buffer,
-                                                        amplitudes_in.local_flags, amplitudes_out.buffer, True)
+            var = self._mirrors["offsetvar"].upload()
+            native().template_offset_apply_diag_precond(var.buffer, amplitudes_in.buffer, amplitudes_in.local_flags,
+                                                        amplitudes_out.buffer, True)
             return
         native().template_offset_apply_diag_precond(self._offsetvar, amplitudes_in.local, amplitudes_in.local_flags,
                                                     amplitudes_out.local, False)
@@ -884,39 +932,19 @@ class Offset(Template):
         product that reads its output (toast_hip_pcg_precond_diag_dot_dev)."""
         if self.use_noise_prior or not self._check_enabled() or self._n_local == 0:
             return None
-        self._offsetvar_to_device()
-        from ..accel import accel_device_ptr
-
-        return accel_device_ptr(self._offsetvar_buf)
-
-    def _offsetvar_to_device(self):
-        if not getattr(self, "_offsetvar_on_dev", False):
-            accel_data_create(self._offsetvar_buf, f"{self.name}_offsetvar", owner=self)
-            accel_data_update_device(self._offsetvar_buf, f"{self.name}_offsetvar")
-            self._offsetvar_on_dev = True
+        return self._mirrors["offsetvar"].upload().ptr
 
     def clear(self):
-        if getattr(self, "_prior", None) is not None:
+        if self._prior is not None:
             self._prior.clear()
-        if getattr(self, "_offsetvar_buf", None) is not None:
-            _ = self._offsetvar          # (somebody may still read the variances on the host)
-            self._drop_offsetvar_device()
+        super().clear()          # (fetches first: somebody may still read the variances on the host)
         for (iob, on_dev), buf in self._flag_cache.items():
             if on_dev:
                 accel_data_delete(buf, f"{self.name}_solver_flags")
         self._flag_cache = {}
 
 
-# ---- shared by the templates with batched device sweeps (SubHarmonic, Periodic, Fourier2D)
-def amps_to_device(amplitudes, name):
-    """Make the device copy of an amplitude vector the current one (created and uploaded when needed)."""
-    if not amplitudes.accel_exists():
-        amplitudes.accel_create(name)
-        amplitudes.accel_update_device()
-    elif not amplitudes.accel_in_use():
-        amplitudes.accel_update_device()
-
-
+# ---- used by the shared methods of Template and by the set-up code of the templates
 def make_resident(obj, name, borrowed=None):
     """Make the device copy of ``obj`` current.  ``borrowed``: a list that collects the objects this call had to upload,
     for ``release_borrowed`` -- set-up code that only READS them hands the host side back as the current one."""

@@ -22,22 +22,13 @@ observation and the view.  Amplitudes shared between the processes of a detector
 ``_initialize`` raises ``NotImplementedError`` when the data communicator has more than one process.
 """
 
-import re
-
 import numpy as np
 import scipy.signal
 
-from ..accel import (
-    accel_data_create,
-    accel_data_delete,
-    accel_data_update_device,
-    accel_data_update_host,
-    accel_device_ptr,
-    native,
-)
+from ..accel import accel_data_create, accel_data_delete, accel_data_update_device, accel_device_ptr, native
 from ..data import defaults, detector_direction
-from ..traits import Bool, Float, ImplementationType, Int, Unicode
-from . import Amplitudes, Template, amps_to_device, make_resident, release_borrowed
+from ..traits import Bool, Float, Int, Unicode
+from . import Amplitudes, DeviceMirror, Template, release_borrowed
 
 
 def evaluate_template(theta, phi, radius, order, fit_subharmonics):
@@ -109,8 +100,7 @@ class Fourier2D(Template):
     def __init__(self, **kwargs):
         self._dev_tables = {}
         self._work = (0, 0)
-        self._norms_on_dev = False
-        self._norms_stale = False
+        self._prior_views = None
         super().__init__(**kwargs)
 
     # ------------------------------------------------------------------ set-up
@@ -137,22 +127,15 @@ class Fourier2D(Template):
             raise NotImplementedError("Fourier2D: the amplitudes would be shared between the processes that hold the "
                                       "detectors of an observation; that reduction is not built: run on one process")
         nmode = self.nmode
-        det_pat = re.compile(self.pattern) if self.pattern is not None else None
         all_dets = {}
         self._obs_dets = {}
         self._obs_view_offset = {}      # first local amplitude of every view
         self._local_ranges = []
         offset = 0
         for iob, ob in enumerate(new_data.obs):
-            self._obs_dets[iob] = set()
-            have_data = set(ob.detdata[self.det_data].detectors) if self.det_data in ob.detdata else None
-            for d in ob.select_local_detectors(flagmask=self.det_mask):
-                if have_data is not None and d not in have_data:
-                    continue
-                if det_pat is not None and det_pat.match(d) is None:
-                    continue
-                self._obs_dets[iob].add(d)
-                all_dets.setdefault(d, None)
+            dets = self._obs_detectors(ob)
+            self._obs_dets[iob] = set(dets)
+            all_dets.update(dict.fromkeys(dets))
             offs = []
             obs_first = offset      # the observation's amplitudes start here in the global vector too
             for ivw, vw in enumerate(ob.intervals[self.view]):
@@ -168,7 +151,7 @@ class Fourier2D(Template):
         self._all_dets = list(all_dets.keys())
         self._n_local = offset
         self._n_global = offset
-        self._norms_buf = np.zeros(self._n_local, dtype=np.float64)
+        self._mirrors["norms"] = DeviceMirror(np.zeros(self._n_local, dtype=np.float64), f"{self.name}_norms")
         # basis and filters: host NumPy on both paths
         self._templates, self._filters, self._filter_floored = {}, {}, {}
         corr_len, amp = float(self.correlation_length), float(self.correlation_amplitude)
@@ -209,21 +192,17 @@ class Fourier2D(Template):
         """The detectors of one observation in the order the reference's set-up takes them."""
         return [d for d in ob.local_detectors if d in self._obs_dets[iob]]
 
-    def _det_weights(self, ob, dets):
-        if self.noise_model is not None and self.noise_model in ob:
-            return np.array([float(ob[self.noise_model].detector_weight(d)) for d in dets], dtype=np.float64)
-        return np.ones(len(dets), dtype=np.float64)
-
     def _norms_host(self, new_data):
         """fourier2d.py:320-365"""
         nmode = self.nmode
+        norms = self._norms
         for iob, ob in enumerate(new_data.obs):
             dets = self._obs_det_list(iob, ob)
             weights = self._det_weights(ob, dets)
             for ivw, vw in enumerate(ob.intervals[self.view]):
                 view_len = int(vw.last - vw.first)
                 first = int(self._obs_view_offset[iob][ivw])
-                norms_view = self._norms_buf[first:first + view_len * nmode].reshape((-1, nmode))
+                norms_view = norms[first:first + view_len * nmode].reshape((-1, nmode))
                 good = np.empty(view_len, dtype=np.float64)
                 for det, detweight in zip(dets, weights):
                     good[:] = 1.0
@@ -231,54 +210,39 @@ class Fourier2D(Template):
                         flags = ob.detdata[self.det_flags][det, vw.first:vw.last]
                         good[(flags & self.det_flag_mask) != 0] = 0
                     norms_view += np.outer(good, self._templates[iob][det] ** 2 * detweight)
-        nonzero = self._norms_buf != 0
-        self._norms_buf[nonzero] = 1.0 / self._norms_buf[nonzero]
+        nonzero = norms != 0
+        norms[nonzero] = 1.0 / norms[nonzero]
 
     def _norms_device(self, new_data):
         """The same sums by toast_hip_fourier2d_norms_dev over the resident flags; the norms stay on the device."""
         from .. import capi
 
         nmode = self.nmode
-        name = f"{self.name}_norms"
-        accel_data_create(self._norms_buf, name, zero_out=True, owner=self)
-        self._norms_on_dev = True
+        norms = self._mirrors["norms"].create(zero_out=True)
         for iob, ob in enumerate(new_data.obs):
             dets = self._obs_det_list(iob, ob)
             if len(dets) == 0 or len(ob.intervals[self.view]) == 0:
                 continue
             weights = self._det_weights(ob, dets)
             w2 = np.ascontiguousarray([self._templates[iob][d] ** 2 * w for d, w in zip(dets, weights)], dtype=np.float64)
-            f_idx, f_ptr, borrowed = None, 0, []
+            borrowed = []
             w2_name = f"{self.name}_w2"
             accel_data_create(w2, w2_name)
             try:
                 accel_data_update_device(w2, w2_name)
-                if self.det_flags is not None:
-                    fd = make_resident(ob.detdata[self.det_flags], self.det_flags, borrowed)
-                    f_idx, f_ptr = fd.indices(dets), accel_device_ptr(fd.buffer)
+                f_idx, f_ptr = self._det_flag_args(ob, dets, borrowed)
                 capi.dev.fourier2d_norms(nmode, accel_device_ptr(w2), self._obs_view_offset[iob], f_idx, f_ptr,
                                          self.det_flag_mask, len(dets), ob.n_local_samples, ob.intervals[self.view].data,
-                                         accel_device_ptr(self._norms_buf))
+                                         norms.ptr)
                 native().accel_synchronize()      # (w2 is released below)
             finally:
                 accel_data_delete(w2, w2_name)
                 release_borrowed(borrowed)
-        self._norms_stale = True
+        norms.written()
 
     # The norms are computed on the device when the accelerator is on and read there by the preconditioner: the host
     # copy is fetched when somebody asks for it.
-    @property
-    def _norms(self):
-        if self._norms_stale:
-            self._norms_stale = False
-            accel_data_update_host(self._norms_buf, f"{self.name}_norms")
-        return self._norms_buf
-
-    def _norms_to_device(self):
-        if not self._norms_on_dev:
-            accel_data_create(self._norms_buf, f"{self.name}_norms", owner=self)
-            accel_data_update_device(self._norms_buf, f"{self.name}_norms")
-            self._norms_on_dev = True
+    _norms = property(lambda self: self._mirrors["norms"].host)
 
     # ------------------------------------------------------------------ Template interface
     def _detectors(self):
@@ -290,12 +254,6 @@ class Fourier2D(Template):
 
     def _supports_accel(self):
         return self.nmode <= self._max_modes()
-
-    def supports_accel(self):
-        return self._supports_accel()
-
-    def _implementations(self):
-        return [ImplementationType.DEFAULT, ImplementationType.COMPILED]
 
     def _device_table(self, key, build):
         """A small table registered on the device once per template, released by ``clear()``."""
@@ -314,14 +272,9 @@ class Fourier2D(Template):
         """All detectors and all views of an observation in one launch (device-resident buffers only)."""
         from .. import capi
 
-        if not self._check_enabled() or self._n_local == 0:
-            return
-        amps_to_device(amplitudes, f"{self.name}_amps")
-        for iob, ob in enumerate(self.data.obs):
-            dets = [d for d in detectors if d in self._obs_dets[iob]]
-            if len(dets) == 0 or len(ob.intervals[self.view]) == 0:
+        for iob, ob, dets, dd in self._device_sweep(detectors, amplitudes):
+            if len(ob.intervals[self.view]) == 0:
                 continue
-            dd = ob.detdata[self.det_data]
             capi.dev.fourier2d_add_to_signal(self.nmode, self._template_table(iob, dets), self._obs_view_offset[iob],
                                              accel_device_ptr(amplitudes.buffer), dd.indices(dets),
                                              accel_device_ptr(dd.buffer), ob.n_local_samples, ob.intervals[self.view].data,
@@ -331,19 +284,13 @@ class Fourier2D(Template):
         """No flags, and the amplitudes are accumulated: see the module docstring."""
         from .. import capi
 
-        if not self._check_enabled() or self._n_local == 0:
-            return
-        amps_to_device(amplitudes, f"{self.name}_amps")
-        for iob, ob in enumerate(self.data.obs):
-            dets = [d for d in detectors if d in self._obs_dets[iob]]
-            if len(dets) == 0 or len(ob.intervals[self.view]) == 0:
+        for iob, ob, dets, dd in self._device_sweep(detectors, amplitudes):
+            if len(ob.intervals[self.view]) == 0:
                 continue
-            dd = ob.detdata[self.det_data]
             capi.dev.fourier2d_project_signal(self.nmode, self._template_table(iob, dets), self._obs_view_offset[iob],
                                               accel_device_ptr(amplitudes.buffer), dd.indices(dets),
                                               accel_device_ptr(dd.buffer), ob.n_local_samples, ob.intervals[self.view].data,
                                               n_group=n_group)
-        amplitudes.accel_used(True)
 
     def _view_slices(self, iob, ob):
         nmode = self.nmode
@@ -351,12 +298,7 @@ class Fourier2D(Template):
             first = int(self._obs_view_offset[iob][ivw])
             yield ivw, vw, slice(first, first + int(vw.last - vw.first) * nmode, 1)
 
-    def _add_to_signal(self, detector, amplitudes, use_accel=None, **kwargs):
-        if detector not in self._all_dets:
-            return
-        if use_accel:
-            self.add_to_signal_multi([detector], amplitudes)
-            return
+    def _add_to_signal_host(self, detector, amplitudes):
         nmode = self.nmode
         local = amplitudes.local
         for iob, ob in enumerate(self.data.obs):
@@ -366,12 +308,7 @@ class Fourier2D(Template):
             for ivw, vw, amp_slice in self._view_slices(iob, ob):
                 row[vw.first:vw.last] += np.sum(local[amp_slice].reshape((-1, nmode)) * self._templates[iob][detector], 1)
 
-    def _project_signal(self, detector, amplitudes, use_accel=None, **kwargs):
-        if detector not in self._all_dets:
-            return
-        if use_accel:
-            self.project_signal_multi([detector], amplitudes)
-            return
+    def _project_signal_host(self, detector, amplitudes):
         nmode = self.nmode
         local = amplitudes.local
         for iob, ob in enumerate(self.data.obs):
@@ -387,7 +324,7 @@ class Fourier2D(Template):
         Built by ``_initialize`` when the accelerator is on; otherwise when the first resident vector arrives."""
         from .. import capi
 
-        if getattr(self, "_prior_views", None) is None:
+        if self._prior_views is None:
             nmode = self.nmode
             views, most = [], 0
             for iob, ob in enumerate((self.data if data is None else data).obs):
@@ -406,20 +343,6 @@ class Fourier2D(Template):
             if nbytes > 0:
                 self._work = (capi.device_malloc(nbytes), nbytes)
         return self._prior_views
-
-    def _on_device(self, amplitudes_in, amplitudes_out, fn):
-        """Run ``fn`` with both vectors resident; hand the result back to the host when the caller's vectors were
-        host-current (the PCG keeps them resident and skips this)."""
-        stay = amplitudes_in.accel_in_use() or amplitudes_out.accel_in_use()
-        in_was = amplitudes_in.accel_in_use()
-        amplitudes_in.accel_resident(f"{self.name}_amps_in")
-        amplitudes_out.accel_resident(f"{self.name}_amps_out")
-        fn()
-        if not stay:
-            native().accel_synchronize()
-            amplitudes_out.accel_update_host()
-        if not in_was:
-            amplitudes_in.accel_used(False)  # never modified on the device
 
     def _prior_device(self, amplitudes_in, amplitudes_out):
         from .. import capi
@@ -459,8 +382,7 @@ class Fourier2D(Template):
 
             amplitudes_in.accel_resident()
             amplitudes_out.accel_resident()
-            self._norms_to_device()
-            capi.dev.fourier2d_apply_precond(self._n_local, accel_device_ptr(self._norms_buf),
+            capi.dev.fourier2d_apply_precond(self._n_local, self._mirrors["norms"].upload().ptr,
                                              accel_device_ptr(amplitudes_in.buffer), accel_device_ptr(amplitudes_out.buffer))
             return
         # fourier2d.py:457-459
@@ -470,23 +392,17 @@ class Fourier2D(Template):
     def device_tables(self):
         """The host keys of everything this template has registered on the device (tests / inspection)."""
         keys = [arr for arr, _ in self._dev_tables.values()]
-        if self._norms_on_dev:
-            keys.append(self._norms_buf)
-        return keys
+        return keys + [m.buffer for m in self._mirrors.values() if m.on_device]
 
     def clear(self):
         """Release everything this template registered: basis tables, spectra, the norms and the prior's work buffer."""
         from .. import capi
 
-        if getattr(self, "_norms_on_dev", False):
-            _ = self._norms          # (somebody may still read the norms on the host)
-            accel_data_delete(self._norms_buf, f"{self.name}_norms")
-        self._norms_on_dev = False
-        self._norms_stale = False
-        for arr, name in getattr(self, "_dev_tables", {}).values():
+        super().clear()          # (fetches first: somebody may still read the norms on the host)
+        for arr, name in self._dev_tables.values():
             accel_data_delete(arr, name)
         self._dev_tables = {}
-        ptr, nbytes = getattr(self, "_work", (0, 0))
+        ptr, nbytes = self._work
         if ptr:
             capi.device_release(ptr, nbytes)
         self._work = (0, 0)

@@ -24,13 +24,11 @@ observation without the key has no amplitudes; the reference indexes its per-obs
 misplaces the later observations in that case.
 """
 
-import re
-
 import numpy as np
 
-from ..accel import accel_data_create, accel_data_delete, accel_data_update_device, accel_data_update_host, accel_device_ptr
-from ..traits import Bool, Float, ImplementationType, Int, Unicode
-from . import Amplitudes, Template, amps_to_device, block_amp_offsets, make_resident, release_borrowed
+from ..accel import accel_device_ptr
+from ..traits import Bool, Float, Int, Unicode
+from . import Amplitudes, DeviceMirror, Template, make_resident, release_borrowed
 
 
 class Periodic(Template):
@@ -45,10 +43,10 @@ class Periodic(Template):
     minimum_bin_hits = Int(3, help="Minimum number of samples per amplitude bin")
 
     def __init__(self, **kwargs):
-        self._index = {}
-        self._index_on_dev = {}
-        self._hits_on_dev = False
+        self._index = {}        # per observation: the mirror of its int32 rows of bin indices
         super().__init__(**kwargs)
+
+    _amp_hits = property(lambda self: self._mirrors["hits"].host)
 
     # ------------------------------------------------------------------ set-up
     def _key_field(self, ob):
@@ -81,7 +79,6 @@ class Periodic(Template):
         self._obs_dets = {}
         self._obs_min, self._obs_max, self._obs_incr, self._obs_nbins = {}, {}, {}, {}
         total_bins = 0
-        det_pat = re.compile(self.pattern) if self.pattern is not None else None
         for iob, ob in enumerate(new_data.obs):
             self._obs_dets[iob] = set()
             if not self._has_key(ob):
@@ -108,34 +105,14 @@ class Periodic(Template):
             self._obs_min[iob], self._obs_max[iob] = float(omin), float(omax)
             self._obs_nbins[iob], self._obs_incr[iob] = obins, float(oincr)
             total_bins += obins
-            have_data = set(ob.detdata[self.det_data].detectors) if self.det_data in ob.detdata else None
-            have_key = set(ob.detdata[self.key].detectors) if self.is_detdata_key else None
-            for d in ob.select_local_detectors(flagmask=self.det_mask):
-                if have_data is not None and d not in have_data:
-                    continue
-                if have_key is not None and d not in have_key:
-                    continue
-                if det_pat is not None and det_pat.match(d) is None:
-                    continue
-                self._obs_dets[iob].add(d)
-                all_dets.setdefault(d, None)
+            dets = self._obs_detectors(ob, also_in=(self.key,) if self.is_detdata_key else ())
+            self._obs_dets[iob] = set(dets)
+            all_dets.update(dict.fromkeys(dets))
         self._all_dets = list(all_dets.keys())
         if total_bins == 0:
             raise RuntimeError(f"Template {self.name} has zero amplitude bins- change the binning size.")
-        self._det_offset = {}
-        offset = 0
-        for det in self._all_dets:
-            self._det_offset[det] = offset
-            for iob in range(len(new_data.obs)):
-                if det in self._obs_dets[iob]:
-                    offset += self._obs_nbins[iob]
-        self._n_local = offset
-        self._n_global = self._n_local
-        comm = new_data.comm
-        if comm.comm_world is not None:
-            self._n_global = int(comm.allreduce_scalar(self._n_local, op="sum"))
-        self._amp_offset_cache = {}
-        self._amp_hits = np.zeros(self._n_local, dtype=np.int32)
+        self._layout_detector_major(new_data.comm, self._obs_nbins)
+        self._mirrors["hits"] = DeviceMirror(np.zeros(self._n_local, dtype=np.int32), f"{self.name}_hits")
         self._amp_flags = np.zeros(self._n_local, dtype=bool)
         if self._n_local == 0:
             return
@@ -162,11 +139,8 @@ class Periodic(Template):
                     amp_indx = np.array((vals[row, sl][good] - self._obs_min[iob]) / self._obs_incr[iob], dtype=np.int32)
                     amp_indx[amp_indx >= nbins] = nbins - 1
                     index[row, sl][good] = amp_indx
-            self._index[iob] = index
-        elif self._index_on_dev.get(iob) == "device":
-            accel_data_update_host(self._index[iob], f"{self.name}_index")
-            self._index_on_dev[iob] = "both"
-        return self._index[iob]
+            self._index[iob] = DeviceMirror(index, f"{self.name}_index")
+        return self._index[iob].host
 
     def _index_row(self, ob, det):
         return int(ob.detdata[self.key].indices([det])[0]) if self.is_detdata_key else 0
@@ -174,7 +148,7 @@ class Periodic(Template):
     def _init_hits_host(self, new_data):
         """periodic.py:232-272, view after view."""
         for det in self._all_dets:
-            amp_offset = self._det_offset[det]
+            amp_offset = self._det_start[det]
             for iob, ob in enumerate(new_data.obs):
                 if det not in self._obs_dets[iob]:
                     continue
@@ -195,8 +169,8 @@ class Periodic(Template):
         """Device pointer of the cached index of one observation (toast_hip_periodic_index_dev on first use)."""
         from .. import capi
 
-        state = self._index_on_dev.get(iob)
-        if state is None:
+        index = self._index.get(iob)
+        if index is None or not index.on_device:
             field = self._key_field(ob)
             key = make_resident(field[self.key], self.key, borrowed)
             kbuf = key.buffer if self.is_detdata_key else key.data
@@ -211,26 +185,19 @@ class Periodic(Template):
                                        f"shape of the key")
                 f_ptr = accel_device_ptr(fbuf)
             n_row = kbuf.shape[0] if self.is_detdata_key else 1
-            if iob not in self._index:
-                self._index[iob] = np.empty((n_row, ob.n_local_samples), dtype=np.int32)
-                host_valid = False
-            else:
-                host_valid = True
-            accel_data_create(self._index[iob], f"{self.name}_index", owner=self)
+            host_valid = index is not None
+            if not host_valid:
+                index = self._index[iob] = DeviceMirror(np.empty((n_row, ob.n_local_samples), dtype=np.int32),
+                                                        f"{self.name}_index")
             capi.dev.periodic_index(accel_device_ptr(kbuf), f_ptr, self.flag_mask, n_row, ob.n_local_samples,
                                     self._obs_min[iob], self._obs_incr[iob], self._obs_nbins[iob],
-                                    ob.intervals[self.view].data, accel_device_ptr(self._index[iob]))
-            self._index_on_dev[iob] = "both" if host_valid else "device"
-        return accel_device_ptr(self._index[iob])
+                                    ob.intervals[self.view].data, index.create().ptr)
+            if not host_valid:
+                index.written()      # (rows that _host_index computed are the same ones: both sides current)
+        return index.ptr
 
     def _index_rows(self, ob, dets):
         return ob.detdata[self.key].indices(dets) if self.is_detdata_key else None
-
-    def _det_flag_args(self, ob, dets, borrowed=None):
-        if self.det_flags is None:
-            return None, 0
-        fd = make_resident(ob.detdata[self.det_flags], self.det_flags, borrowed)
-        return fd.indices(dets), accel_device_ptr(fd.buffer)
 
     def _init_hits_device(self, new_data):
         """Hits of the first view, then of all views (toast_hip_periodic_hits_dev).  The hit counts only grow, so an
@@ -239,9 +206,7 @@ class Periodic(Template):
         its end, which needs the views sorted and disjoint: checked."""
         from .. import capi
 
-        name = f"{self.name}_hits"
-        accel_data_create(self._amp_hits, name, zero_out=True, owner=self)
-        self._hits_on_dev = True
+        hits = self._mirrors["hits"].create(zero_out=True)
         for iob, ob in enumerate(new_data.obs):
             dets = [d for d in self._all_dets if d in self._obs_dets[iob]]
             views = ob.intervals[self.view]
@@ -258,13 +223,14 @@ class Periodic(Template):
                 raise RuntimeError(f"Periodic template {self.name}: the intervals of view {self.view} of observation "
                                    f"{ob.name} are not sorted and disjoint")
             split = int(views[0].last)
-            capi.dev.periodic_hits(*args, 0, split, accel_device_ptr(self._amp_hits))
-            accel_data_update_host(self._amp_hits, name)
+            capi.dev.periodic_hits(*args, 0, split, hits.ptr)
+            hits.written()
             for off in self.det_amp_offsets(iob, dets):
                 sl = slice(int(off), int(off) + self._obs_nbins[iob])
                 self._amp_flags[sl] = self._amp_hits[sl] < self.minimum_bin_hits
-            capi.dev.periodic_hits(*args, split, ob.n_local_samples, accel_device_ptr(self._amp_hits))
-            accel_data_update_host(self._amp_hits, name)      # (also: the kernels are done with what was borrowed)
+            capi.dev.periodic_hits(*args, split, ob.n_local_samples, hits.ptr)
+            hits.written()
+            _ = hits.host      # (fetched now: the kernels are done with what was borrowed)
             release_borrowed(borrowed)
 
     # ------------------------------------------------------------------ Template interface
@@ -276,31 +242,13 @@ class Periodic(Template):
         z.local_flags[:] = np.where(self._amp_flags, 1, 0)
         return z
 
-    def _supports_accel(self):
-        return True
-
-    def supports_accel(self):
-        return self._supports_accel()
-
-    def _implementations(self):
-        return [ImplementationType.DEFAULT, ImplementationType.COMPILED]
-
-    def det_amp_offsets(self, iob, dets):
-        """First amplitude of each detector's bins for observation ``iob``, cached."""
-        return block_amp_offsets(self._amp_offset_cache, self._det_offset, self._obs_dets, self._obs_nbins, iob, dets)
-
     def add_to_signal_multi(self, detectors, amplitudes, **kwargs):
         """All detectors of an observation in one launch (device-resident buffers only)."""
         from .. import capi
 
-        if not self._check_enabled() or self._n_local == 0:
-            return
-        amps_to_device(amplitudes, f"{self.name}_amps")
-        for iob, ob in enumerate(self.data.obs):
-            dets = [d for d in detectors if d in self._obs_dets[iob]]
-            if len(dets) == 0 or self._obs_nbins[iob] == 0:
+        for iob, ob, dets, dd in self._device_sweep(detectors, amplitudes):
+            if self._obs_nbins[iob] == 0:
                 continue
-            dd = ob.detdata[self.det_data]
             capi.dev.periodic_add_to_signal(self._device_index(iob, ob), self._index_rows(ob, dets),
                                             self.det_amp_offsets(iob, dets), accel_device_ptr(amplitudes.buffer),
                                             dd.indices(dets), accel_device_ptr(dd.buffer), ob.n_local_samples,
@@ -309,28 +257,17 @@ class Periodic(Template):
     def project_signal_multi(self, detectors, amplitudes, path=0, **kwargs):
         from .. import capi
 
-        if not self._check_enabled() or self._n_local == 0:
-            return
-        amps_to_device(amplitudes, f"{self.name}_amps")
-        for iob, ob in enumerate(self.data.obs):
-            dets = [d for d in detectors if d in self._obs_dets[iob]]
-            if len(dets) == 0 or self._obs_nbins[iob] == 0:
+        for iob, ob, dets, dd in self._device_sweep(detectors, amplitudes):
+            if self._obs_nbins[iob] == 0:
                 continue
-            dd = ob.detdata[self.det_data]
             f_idx, f_ptr = self._det_flag_args(ob, dets)
             capi.dev.periodic_project_signal(self._device_index(iob, ob), self._index_rows(ob, dets), dd.indices(dets),
                                              accel_device_ptr(dd.buffer), f_idx, f_ptr, self.det_flag_mask,
                                              self.det_amp_offsets(iob, dets), accel_device_ptr(amplitudes.buffer),
                                              ob.n_local_samples, self._obs_nbins[iob], path=path)
-        amplitudes.accel_used(True)
 
-    def _add_to_signal(self, detector, amplitudes, use_accel=None, **kwargs):
-        if detector not in self._all_dets:
-            return
-        if use_accel:
-            self.add_to_signal_multi([detector], amplitudes)
-            return
-        amp_offset = self._det_offset[detector]
+    def _add_to_signal_host(self, detector, amplitudes):
+        amp_offset = self._det_start[detector]
         local = amplitudes.local
         for iob, ob in enumerate(self.data.obs):
             if detector not in self._obs_dets[iob]:
@@ -345,13 +282,8 @@ class Periodic(Template):
                 row[sl][good] += amps[irow[sl][good]]
             amp_offset += nbins
 
-    def _project_signal(self, detector, amplitudes, use_accel=None, **kwargs):
-        if detector not in self._all_dets:
-            return
-        if use_accel:
-            self.project_signal_multi([detector], amplitudes)
-            return
-        amp_offset = self._det_offset[detector]
+    def _project_signal_host(self, detector, amplitudes):
+        amp_offset = self._det_start[detector]
         local = amplitudes.local
         for iob, ob in enumerate(self.data.obs):
             if detector not in self._obs_dets[iob]:
@@ -379,11 +311,7 @@ class Periodic(Template):
 
             amplitudes_in.accel_resident()
             amplitudes_out.accel_resident()
-            if not self._hits_on_dev:
-                accel_data_create(self._amp_hits, f"{self.name}_hits", owner=self)
-                accel_data_update_device(self._amp_hits, f"{self.name}_hits")
-                self._hits_on_dev = True
-            capi.dev.periodic_apply_precond(self._n_local, accel_device_ptr(self._amp_hits),
+            capi.dev.periodic_apply_precond(self._n_local, self._mirrors["hits"].upload().ptr,
                                             accel_device_ptr(amplitudes_in.local_flags),
                                             accel_device_ptr(amplitudes_in.buffer), accel_device_ptr(amplitudes_out.buffer))
             return
@@ -399,11 +327,7 @@ class Periodic(Template):
 
     def clear(self):
         """Release the device copies of the index rows and of the hit counts; forget the cached indices."""
-        for iob, state in getattr(self, "_index_on_dev", {}).items():
-            if state is not None:
-                accel_data_delete(self._index[iob], f"{self.name}_index")
-        self._index_on_dev = {}
+        for index in self._index.values():
+            index.drop(fetch=False)
         self._index = {}
-        if getattr(self, "_hits_on_dev", False):
-            accel_data_delete(self._amp_hits, f"{self.name}_hits")
-        self._hits_on_dev = False
+        super().clear()

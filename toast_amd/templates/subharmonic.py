@@ -16,14 +16,12 @@ A (detector, view) without a single good sample makes the reference fail inside 
 ``numpy.linalg.LinAlgError`` with the detector, observation and view in the message.
 """
 
-import re
-
 import numpy as np
 
-from ..accel import accel_data_create, accel_data_delete, accel_data_update_device, accel_data_update_host, accel_device_ptr
+from ..accel import accel_data_create, accel_data_delete, accel_data_update_host, accel_device_ptr
 from ..data import defaults
-from ..traits import ImplementationType, Int, Unicode
-from . import Amplitudes, Template, amps_to_device, block_amp_offsets, make_resident, release_borrowed
+from ..traits import Int, Unicode
+from . import Amplitudes, DeviceMirror, Template, release_borrowed
 
 
 def legendre_basis(norder, view_len):
@@ -47,9 +45,8 @@ class SubHarmonic(Template):
     order = Int(1, help="The filter order")
     noise_model = Unicode(None, allow_none=True, help="Observation key containing the optional noise model")
 
-    def __init__(self, **kwargs):
-        self._precond_on_dev = False
-        super().__init__(**kwargs)
+    # inverse of the weighted Gram matrix of every (detector, observation, view) block, in amplitude order
+    _precond = property(lambda self: self._mirrors["precond"].host)
 
     # ------------------------------------------------------------------ set-up
     def _initialize(self, new_data):
@@ -61,35 +58,16 @@ class SubHarmonic(Template):
         norder = self.order + 1
         all_dets = {}
         self._obs_dets = {}
-        det_pat = re.compile(self.pattern) if self.pattern is not None else None
         for iob, ob in enumerate(new_data.obs):
-            self._obs_dets[iob] = set()
-            have_data = set(ob.detdata[self.det_data].detectors) if self.det_data in ob.detdata else None
-            for d in ob.select_local_detectors(flagmask=self.det_mask):
-                if have_data is not None and d not in have_data:
-                    continue
-                if det_pat is not None and det_pat.match(d) is None:
-                    continue
-                self._obs_dets[iob].add(d)
-                all_dets.setdefault(d, None)
+            dets = self._obs_detectors(ob)
+            self._obs_dets[iob] = set(dets)
+            all_dets.update(dict.fromkeys(dets))
         self._all_dets = list(all_dets.keys())
         self._obs_nview = {iob: len(ob.intervals[self.view]) for iob, ob in enumerate(new_data.obs)}
-        self._det_start = {}
-        offset = 0
-        for det in self._all_dets:
-            self._det_start[det] = offset
-            for iob in range(len(new_data.obs)):
-                if det in self._obs_dets[iob]:
-                    offset += self._obs_nview[iob] * norder
-        self._n_local = offset
-        self._n_global = self._n_local
-        comm = new_data.comm
-        if comm.comm_world is not None:
-            self._n_global = int(comm.allreduce_scalar(self._n_local, op="sum"))
-        self._amp_offset_cache = {}
+        self._layout_detector_major(new_data.comm, {iob: n * norder for iob, n in self._obs_nview.items()})
         self._templates = {}
-        # inverse of the weighted Gram matrix of every (detector, observation, view) block, in amplitude order
-        self._precond = np.zeros((self._n_local // norder, norder, norder), dtype=np.float64)
+        self._mirrors["precond"] = DeviceMirror(np.zeros((self._n_local // norder, norder, norder), dtype=np.float64),
+                                                f"{self.name}_precond")
         if self._n_local == 0:
             return
         # (set-up runs on the device for a template that will be swept there; the flags it reads are handed back)
@@ -110,11 +88,6 @@ class SubHarmonic(Template):
         if iob not in self._templates:
             self._templates[iob] = [legendre_basis(self.order + 1, int(vw.last - vw.first)) for vw in ob.intervals[self.view]]
         return self._templates[iob]
-
-    def _det_weights(self, ob, dets):
-        if self.noise_model is not None and self.noise_model in ob:
-            return np.array([float(ob[self.noise_model].detector_weight(d)) for d in dets], dtype=np.float64)
-        return np.ones(len(dets), dtype=np.float64)
 
     def _blocks(self, iob, dets):
         """First block (amplitude index / norder) of each detector for observation ``iob``."""
@@ -162,10 +135,8 @@ class SubHarmonic(Template):
             n_view = self._obs_nview[iob]
             if len(dets) == 0 or n_view == 0:
                 continue
-            f_idx, f_ptr, borrowed = None, 0, []
-            if self.det_flags is not None:
-                fd = make_resident(ob.detdata[self.det_flags], self.det_flags, borrowed)
-                f_idx, f_ptr = fd.indices(dets), accel_device_ptr(fd.buffer)
+            borrowed = []
+            f_idx, f_ptr = self._det_flag_args(ob, dets, borrowed)
             g = np.zeros((len(dets), n_view, norder, norder), dtype=np.float64)
             n = np.zeros((len(dets), n_view), dtype=np.int64)
             g_name, n_name = f"{self.name}_gram", f"{self.name}_ngood"
@@ -231,29 +202,11 @@ class SubHarmonic(Template):
     def _supports_accel(self):
         return self.order + 1 <= self._max_terms()
 
-    def supports_accel(self):
-        return self._supports_accel()
-
-    def _implementations(self):
-        return [ImplementationType.DEFAULT, ImplementationType.COMPILED]
-
-    def det_amp_offsets(self, iob, dets):
-        """First amplitude of each detector's block for observation ``iob``, cached."""
-        per_obs = {job: n * (self.order + 1) for job, n in self._obs_nview.items()}
-        return block_amp_offsets(self._amp_offset_cache, self._det_start, self._obs_dets, per_obs, iob, dets)
-
     def add_to_signal_multi(self, detectors, amplitudes, **kwargs):
         """All detectors and all views of an observation in one launch (device-resident buffers only)."""
         from .. import capi
 
-        if not self._check_enabled() or self._n_local == 0:
-            return
-        amps_to_device(amplitudes, f"{self.name}_amps")
-        for iob, ob in enumerate(self.data.obs):
-            dets = [d for d in detectors if d in self._obs_dets[iob]]
-            if len(dets) == 0:
-                continue
-            dd = ob.detdata[self.det_data]
+        for iob, ob, dets, dd in self._device_sweep(detectors, amplitudes):
             capi.dev.subharmonic_add_to_signal(self.order + 1, self.det_amp_offsets(iob, dets),
                                                accel_device_ptr(amplitudes.buffer), dd.indices(dets),
                                                accel_device_ptr(dd.buffer), ob.n_local_samples, ob.intervals[self.view].data)
@@ -262,25 +215,12 @@ class SubHarmonic(Template):
         """No flags, and the amplitudes are assigned: see the module docstring."""
         from .. import capi
 
-        if not self._check_enabled() or self._n_local == 0:
-            return
-        amps_to_device(amplitudes, f"{self.name}_amps")
-        for iob, ob in enumerate(self.data.obs):
-            dets = [d for d in detectors if d in self._obs_dets[iob]]
-            if len(dets) == 0:
-                continue
-            dd = ob.detdata[self.det_data]
+        for iob, ob, dets, dd in self._device_sweep(detectors, amplitudes):
             capi.dev.subharmonic_project_signal(self.order + 1, self.det_amp_offsets(iob, dets),
                                                 accel_device_ptr(amplitudes.buffer), dd.indices(dets),
                                                 accel_device_ptr(dd.buffer), ob.n_local_samples, ob.intervals[self.view].data)
-        amplitudes.accel_used(True)
 
-    def _add_to_signal(self, detector, amplitudes, use_accel=None, **kwargs):
-        if detector not in self._all_dets:
-            return
-        if use_accel:
-            self.add_to_signal_multi([detector], amplitudes)
-            return
+    def _add_to_signal_host(self, detector, amplitudes):
         norder = self.order + 1
         offset = self._det_start[detector]
         local = amplitudes.local
@@ -295,12 +235,7 @@ class SubHarmonic(Template):
                     row[vw.first:vw.last] += templates[order] * amp_view[order]
                 offset += norder
 
-    def _project_signal(self, detector, amplitudes, use_accel=None, **kwargs):
-        if detector not in self._all_dets:
-            return
-        if use_accel:
-            self.project_signal_multi([detector], amplitudes)
-            return
+    def _project_signal_host(self, detector, amplitudes):
         norder = self.order + 1
         offset = self._det_start[detector]
         local = amplitudes.local
@@ -326,11 +261,7 @@ class SubHarmonic(Template):
 
             amplitudes_in.accel_resident()
             amplitudes_out.accel_resident()
-            if not self._precond_on_dev:
-                accel_data_create(self._precond, f"{self.name}_precond", owner=self)
-                accel_data_update_device(self._precond, f"{self.name}_precond")
-                self._precond_on_dev = True
-            capi.dev.subharmonic_apply_precond(norder, self._n_local // norder, accel_device_ptr(self._precond),
+            capi.dev.subharmonic_apply_precond(norder, self._n_local // norder, self._mirrors["precond"].upload().ptr,
                                                accel_device_ptr(amplitudes_in.buffer), accel_device_ptr(amplitudes_out.buffer))
             return
         # subharmonic.py:224-236: one small dense product per block
@@ -339,7 +270,5 @@ class SubHarmonic(Template):
 
     def clear(self):
         """Release the device copy of the preconditioner and the host basis."""
-        if getattr(self, "_precond_on_dev", False):
-            accel_data_delete(self._precond, f"{self.name}_precond")
-        self._precond_on_dev = False
+        super().clear()
         self._templates = {}
