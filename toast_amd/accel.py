@@ -207,6 +207,77 @@ class accel_hold:
         return False
 
 
+def _host_key(obj):
+    """The host array whose address keys the device copy of ``obj``, WITHOUT synchronisation."""
+    return obj.buffer if hasattr(obj, "buffer") else obj.data
+
+
+class Resident:
+    """``obj`` made current on the device for one operator call, and what that took: ``created`` -- it had to be
+    registered, ``uploaded`` -- the host values had to be copied.  An object that is current there already costs no
+    native call; one whose buffer is empty (an observation without valid detectors) is left untouched.  The caller ends
+    with the release that fits what it did to the device copy; each does nothing for an object it found resident."""
+
+    def __init__(self, obj, name):
+        self.obj, self.created, self.uploaded = obj, False, False
+        if not obj.accel_in_use() and _host_key(obj).size > 0:
+            self.created = not obj.accel_exists()
+            if self.created:
+                obj.accel_create(name)
+            obj.accel_update_device()
+            self.uploaded = True
+
+    @property
+    def ptr(self):
+        return accel_device_ptr(_host_key(self.obj))
+
+    def write_back_unless_lazy(self, data):
+        """The kernels wrote it.  Eager coherence (``data.lazy_host`` False): back to the host and freed; lazy: it
+        stays resident for the operators that follow."""
+        if self.uploaded and not getattr(data, "lazy_host", False):
+            self.obj.accel_update_host()
+            self.obj.accel_delete()
+
+    def drop_if_created(self):
+        """It was only read and nobody else asked for a device copy: freed without a write-back."""
+        if self.created:
+            self.obj.accel_delete()
+
+    def host_stays_current(self):
+        """It was only read: the host copy is still right and becomes the current side again, so a later edit on the
+        host is uploaded instead of being shadowed by a stale device copy."""
+        if self.uploaded:
+            self.obj.accel_used(False)
+
+
+def make_resident(obj, name, borrowed=None):
+    """Make the device copy of ``obj`` current and leave it there.  ``borrowed``: a list that collects the objects this
+    call had to upload, for ``release_borrowed``."""
+    if Resident(obj, name).uploaded and borrowed is not None:
+        borrowed.append(obj)
+    return obj
+
+
+def release_borrowed(borrowed):
+    """``Resident.host_stays_current`` for the objects that ``make_resident`` collected."""
+    for obj in borrowed:
+        obj.accel_used(False)
+    del borrowed[:]
+
+
+def accel_place(obj, name, use_accel, zero_new=False):
+    """Make ``obj`` current where the kernel will look for it: on the device with ``use_accel``, else on the host.
+    ``zero_new``: an object not yet registered is created zeroed there and marked current without an upload."""
+    if not use_accel:
+        if obj.accel_in_use():
+            obj.accel_update_host()
+    elif zero_new and not obj.accel_exists():
+        obj.accel_create(name, zero_out=True)
+        obj.accel_used(True)
+    else:
+        make_resident(obj, name)
+
+
 class AcceleratorObject:
     """Mix-in for objects with a device copy (reference: accel.py:308-520).
 

@@ -5,6 +5,8 @@ kernel there (toast_hip_vec_axpby_dev), everything else follows the reference on
 
 import numpy as np
 
+from .. import capi
+from ..accel import accel_device_ptr
 from ..traits import Int, Unicode
 from .operator import Operator
 
@@ -60,10 +62,8 @@ class Combine(Operator):
             return False
         if fd.detector_shape != sd.detector_shape or rd.detector_shape != fd.detector_shape:
             return False
-        from .. import capi
-        from ..accel import accel_device_ptr
-
         if rd is not fd and rd is not sd:
+            # (not the residency helper: a result that is not registered yet is created WITHOUT an upload)
             if not rd.accel_exists():
                 rd.accel_create(self.result)
             elif not rd.accel_in_use():

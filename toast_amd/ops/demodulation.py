@@ -34,7 +34,8 @@ import numpy as np
 from scipy.signal import fftconvolve, firwin
 
 from .. import capi
-from ..accel import accel_data_create, accel_data_delete, accel_data_update_device, accel_device_ptr, accel_enabled
+from ..accel import (Resident, accel_data_create, accel_data_delete, accel_data_update_device, accel_device_ptr,
+                     accel_enabled, make_resident)
 from ..data import Data, Focalplane, IntervalList, Observation, Telescope, defaults
 from ..noise import Noise, name_UID
 from ..traits import Bool, Float, Instance, Int, TraitError, Unicode
@@ -434,21 +435,16 @@ class Demodulate(Operator):
         demodulated observation's shared data lives on the host like every other shared field."""
         if sout.data.size == 0:
             return
-        temporary = not sin.accel_exists()
-        if temporary:
-            sin.accel_create(self.shared_flags)
-        if not sin.accel_in_use():
-            sin.accel_update_device()
+        flags_in = Resident(sin, self.shared_flags)
         sout.accel_create(self.shared_flags)
         try:
-            capi.dev.demod_flags(n, wkernel, self.demod_flag_mask, self.nskip, offset, accel_device_ptr(sin.data), 1, n,
+            capi.dev.demod_flags(n, wkernel, self.demod_flag_mask, self.nskip, offset, flags_in.ptr, 1, n,
                                  [0], accel_device_ptr(sout.data), 1, sout.data.size, [0])
             sout.accel_used(True)
             sout.accel_update_host()
         finally:
             sout.accel_delete()
-            if temporary:
-                sin.accel_delete()
+            flags_in.drop_if_created()
 
     def _demodulate_flags(self, obs, demod_obs, dets, wkernel, offset, on_device=False):
         """Demodulate and downsample flags"""
@@ -469,12 +465,7 @@ class Demodulate(Operator):
             return
         fin, fout = obs.detdata[self.det_flags], demod_obs.detdata[self.det_flags]
         if on_device and fin.dtype == np.dtype(np.uint8):
-            temporary = False
-            if not fin.accel_exists():
-                fin.accel_create(self.det_flags)
-                temporary = True
-            if not fin.accel_in_use():
-                fin.accel_update_device()
+            flags_in = Resident(fin, self.det_flags)
             try:
                 in_row, out_row = [], []
                 for det in dets:
@@ -482,13 +473,13 @@ class Demodulate(Operator):
                         in_row.append(int(fin.indices([det])[0]))
                         out_row.append(int(fout.indices([f"{prefix}_{det}"])[0]))
                 capi.dev.demod_flags(obs.n_local_samples, wkernel, self.demod_flag_mask, self.nskip, offset,
-                                     accel_device_ptr(fin.buffer), fin.buffer.shape[0], fin.buffer.shape[1], in_row,
+                                     flags_in.ptr, fin.buffer.shape[0], fin.buffer.shape[1], in_row,
                                      accel_device_ptr(fout.buffer), fout.buffer.shape[0], fout.buffer.shape[1], out_row)
                 fout.accel_used(True)
             finally:
-                if temporary:
+                if flags_in.created:
                     capi.synchronize()
-                    fin.accel_delete()
+                    flags_in.drop_if_created()
             return
         if fout.accel_in_use():
             fout.accel_update_host()
@@ -552,11 +543,7 @@ class Demodulate(Operator):
         n = obs.n_local_samples
         flavors = self.det_data.split(";")
         for flavor in flavors:
-            dd = obs.detdata[flavor]
-            if not dd.accel_in_use():
-                if not dd.accel_exists():
-                    dd.accel_create(flavor)
-                dd.accel_update_device()
+            make_resident(obs.detdata[flavor], flavor)
             demod_obs.detdata[flavor].accel_used(True)
 
         def fir(in_rows, d_in, n_in_rows, taps, nskip, off, dd_out, out_names, **mod):
@@ -588,10 +575,7 @@ class Demodulate(Operator):
             wd = obs.detdata[wname]
             if wd.dtype != np.dtype(np.float64) or wd.sample_shape != (nnz,):
                 raise RuntimeError("Demodulate: the device path reads float64 Stokes weights")
-            if not wd.accel_in_use():
-                if not wd.accel_exists():
-                    wd.accel_create(wname)
-                wd.accel_update_device()
+            make_resident(wd, wname)
             wrows = [int(r) for r in wd.indices(part)]
             scratch = capi.device_malloc(nb * n * 8)
             factors = None

@@ -16,12 +16,14 @@ import re
 import numpy as np
 
 from ..accel import (
+    Resident,
     accel_data_create,
     accel_data_delete,
     accel_data_update_device,
     accel_data_update_host,
     accel_device_ptr,
     accel_enabled,
+    make_resident,
     native,
 )
 from ..data import defaults
@@ -203,28 +205,15 @@ class GroundFilter(Operator):
             templates = self.build_templates(obs)
             nt = templates.shape[0]
             dd = obs.detdata[self.det_data]
-            made_resident = False
-            if not dd.accel_in_use():
-                if not dd.accel_exists():
-                    dd.accel_create(self.det_data)
-                dd.accel_update_device()
-                made_resident = True
+            signal = Resident(dd, self.det_data)
             f_ptr, f_idx, fd = 0, None, None
             if self.det_flags is not None:
-                fd = obs.detdata[self.det_flags]
-                if not fd.accel_in_use():
-                    if not fd.accel_exists():
-                        fd.accel_create(self.det_flags)
-                    fd.accel_update_device()
+                fd = make_resident(obs.detdata[self.det_flags], self.det_flags)
                 f_ptr, f_idx = accel_device_ptr(fd.buffer), fd.indices(dets)
             s_ptr = 0
             common_good = np.ones(n, dtype=bool)
             if self.shared_flags is not None:
-                sf = obs.shared[self.shared_flags]
-                if not sf.accel_in_use():
-                    if not sf.accel_exists():
-                        sf.accel_create(self.shared_flags)
-                    sf.accel_update_device()
+                sf = make_resident(obs.shared[self.shared_flags], self.shared_flags)
                 s_ptr = accel_device_ptr(sf.data)
                 common_good = (sf.data & self.shared_flag_mask) == 0
             n_det = len(dets)
@@ -262,11 +251,7 @@ class GroundFilter(Operator):
                 accel_data_delete(cf, f"{self.name}_coeff")
             self.coefficients = {det: coeff[i] for i, det in enumerate(dets) if ok[i]}
             accel_data_delete(templates, f"{self.name}_templates")
-            if made_resident and not getattr(data, "lazy_host", False):
-                dd.accel_update_host()
-                dd.accel_delete()
-            else:
-                dd.accel_used(True)
+            signal.write_back_unless_lazy(data)
         comm = data.comm
         if comm.comm_world is not None:
             self.nsingular = int(comm.allreduce_scalar(self.nsingular, op="sum"))

@@ -11,6 +11,7 @@ import sys as _sys
 
 import numpy as np
 
+from ..accel import accel_device_ptr, make_resident
 from ..data import defaults
 from ..pixels import PixelData
 from ..traits import Bool, Float, Instance, Int, Unicode
@@ -251,7 +252,6 @@ class SolveAmplitudes(Operator):
             if rc.accel_in_use():
                 # the condition numbers were computed on the device: threshold them there
                 from .. import capi
-                from ..accel import accel_device_ptr
 
                 mask.accel_create(nm["rcond_mask"], zero_out=True)
                 mask.accel_used(True)
@@ -632,7 +632,6 @@ class MapMaker(Operator):
         """The same combination on the device (toast_hip_combine_flags_dev): nothing but the
         uint8 inputs cross PCIe, and those only if they are not resident yet."""
         from .. import capi
-        from ..accel import accel_device_ptr
 
         dets = ob.select_local_detectors(detectors, flagmask=binning.det_mask)
         ob.detdata.ensure(solver_flags, dtype=np.uint8, detectors=dets, accel=True)
@@ -642,19 +641,11 @@ class MapMaker(Operator):
         n_samp = ob.n_local_samples
         f_ptr, f_n, f_idx = 0, 0, np.zeros(len(dets), np.int32)
         if binning.det_flags is not None:
-            src = ob.detdata[binning.det_flags]
-            if not src.accel_in_use():
-                if not src.accel_exists():
-                    src.accel_create(binning.det_flags)
-                src.accel_update_device()
+            src = make_resident(ob.detdata[binning.det_flags], binning.det_flags)
             f_ptr, f_n, f_idx = accel_device_ptr(src.buffer), n_samp, src.indices(dets)
         s_ptr, s_n = 0, 0
         if binning.shared_flags is not None:
-            shared = ob.shared[binning.shared_flags]
-            if not shared.accel_in_use():
-                if not shared.accel_exists():
-                    shared.accel_create(binning.shared_flags)
-                shared.accel_update_device()
+            shared = make_resident(ob.shared[binning.shared_flags], binning.shared_flags)
             s_ptr, s_n = accel_device_ptr(shared.data), n_samp
         view = binning.pixel_pointing.view
         capi.dev.combine_flags(accel_device_ptr(sf.buffer), sf.indices(dets), f_ptr, f_n, f_idx,

@@ -8,29 +8,14 @@ src/toast/ops/copy.py, delete.py, reset.py.
 
 import numpy as np
 
-from ..accel import native
-from ..data import defaults
+from ..accel import accel_device_ptr, accel_place, make_resident, native
+from ..data import SharedData, defaults
 from ..pixels import PixelData, covariance_apply, covariance_invert, map_reduce_apply
 from ..traits import Bool, Float, ImplementationType, Instance, Int, List, Unicode
 from .operator import Operator
 from .pipeline import Pipeline, uncached_detector_sets
 
 _IMPLS = [ImplementationType.DEFAULT, ImplementationType.COMPILED]
-
-
-def _global_to(obj, name, use_accel, zero_new=False):
-    """Move a global PixelData where the kernel will look for it (mapmaker_utils.py:745-773)."""
-    if use_accel:
-        if not obj.accel_exists():
-            obj.accel_create(name, zero_out=zero_new)
-            if zero_new:
-                obj.accel_used(True)
-            else:
-                obj.accel_update_device()
-        elif not obj.accel_in_use():
-            obj.accel_update_device()
-    elif obj.accel_in_use():
-        obj.accel_update_host()
 
 
 class ScanMap(Operator):
@@ -62,7 +47,7 @@ class ScanMap(Operator):
         if self.weights is None:
             raise NotImplementedError("ScanMap without Stokes weights is not on the compiled path")
         map_dist = map_data.distribution
-        _global_to(map_data, self.map_key, use_accel)
+        accel_place(map_data, self.map_key, use_accel)
         name = {np.dtype(np.float64): "ops_scan_map_float64", np.dtype(np.float32): "ops_scan_map_float32",
                 np.dtype(np.int64): "ops_scan_map_int64", np.dtype(np.int32): "ops_scan_map_int32"}[map_data.dtype]
         kernel = getattr(native(), name)
@@ -143,22 +128,13 @@ class ScanMask(Operator):
             if use_accel:
                 # device pass (toast_hip_scan_mask_dev): pixels / flags / mask stay resident
                 from .. import capi
-                from ..accel import accel_device_ptr
-                from ..data import SharedData
 
                 for obj, nm in ((pd, self.pixels), (fd, self.det_flags), (mask_data, self.mask_key)):
-                    if not obj.accel_exists():
-                        obj.accel_create(nm)
-                    if not obj.accel_in_use():
-                        obj.accel_update_device()
+                    make_resident(obj, nm)
                 gkey = "_g2l_" + str(id(mask_dist))
                 if gkey not in data:
                     data[gkey] = SharedData(mask_dist.global_submap_to_local, "g2l")
-                g2l = data[gkey]
-                if not g2l.accel_exists():
-                    g2l.accel_create("g2l")
-                if not g2l.accel_in_use():
-                    g2l.accel_update_device()
+                g2l = make_resident(data[gkey], "g2l")
                 capi.dev.scan_mask(accel_device_ptr(g2l.data), accel_device_ptr(mask_data.buffer),
                                    mask_dist.n_pix_submap, self.mask_bits, self.det_flags_value, pd.indices(dets),
                                    accel_device_ptr(pd.buffer), fd.indices(dets), accel_device_ptr(fd.buffer),
@@ -217,10 +193,8 @@ class NoiseWeight(Operator):
             noise = ob[self.noise_model]
             detector_weights = np.array([noise.detector_weight(d) for d in dets], dtype=np.float64)
             dd = ob.detdata[self.det_data]
-            if use_accel and not dd.accel_in_use():
-                if not dd.accel_exists():
-                    dd.accel_create(self.det_data)
-                dd.accel_update_device()
+            if use_accel:
+                make_resident(dd, self.det_data)
             native().noise_weight(dd.arg(use_accel), dd.indices(dets), ob.intervals[self.view].data, detector_weights,
                                   use_accel)
 
@@ -272,20 +246,16 @@ class _MapBuilder(Operator):
     def _flag_args(self, ob, dets, use_accel):
         if self.det_flags is not None:
             fd = ob.detdata[self.det_flags]
-            if use_accel and not fd.accel_in_use():
-                if not fd.accel_exists():
-                    fd.accel_create(self.det_flags)
-                fd.accel_update_device()
+            if use_accel:
+                make_resident(fd, self.det_flags)
             flag_indx, flag_data = fd.indices(dets), fd.arg(use_accel)
         else:
             # reference quirk (mapmaker_utils.py:836-838): [-1]; our binding wants n_det entries
             flag_indx, flag_data = np.zeros(len(dets), dtype=np.int32), np.zeros((1, 1), dtype=np.uint8)
         if self.shared_flags is not None:
             sf = ob.shared[self.shared_flags]
-            if use_accel and not sf.accel_in_use():
-                if not sf.accel_exists():
-                    sf.accel_create(self.shared_flags)
-                sf.accel_update_device()
+            if use_accel:
+                make_resident(sf, self.shared_flags)
             shared = sf.data
         else:
             shared = np.zeros(1, dtype=np.uint8)
@@ -341,7 +311,7 @@ class BuildNoiseWeighted(_MapBuilder):
         else:
             data[self.zmap] = PixelData(dist, np.float64, n_value=self._weight_nnz(data, detectors))
             zmap = data[self.zmap]
-        _global_to(zmap, self.zmap, use_accel, zero_new=not zmap.accel_exists() and zmap.host_is_zero())
+        accel_place(zmap, self.zmap, use_accel, zero_new=not zmap.accel_exists() and zmap.host_is_zero())
         for ob in data.obs:
             dets = ob.select_local_detectors(selection=detectors, flagmask=self.det_mask)
             if self.noise_model not in ob:
@@ -368,16 +338,13 @@ class BuildNoiseWeighted(_MapBuilder):
         """One observation of the fused final binning (toast_hip_offset_clean_accumulate_dev): everything is on the
         device already -- the Pipeline staged this operator's inputs, the amplitudes are made resident here."""
         from .. import capi
-        from ..accel import accel_device_ptr
-        from ..data import SharedData
-        from .mapmaker_solve import SolverLHS
 
         tmpl, amps = clean
         iob = data.obs.index(ob)
-        SolverLHS._resident(amps, f"{tmpl.name}_amplitudes")
+        make_resident(amps, f"{tmpl.name}_amplitudes")
         if "_g2l_" + self.pixel_dist not in data:
             data["_g2l_" + self.pixel_dist] = SharedData(dist.global_submap_to_local, "g2l")
-        g2l = SolverLHS._resident(data["_g2l_" + self.pixel_dist], "g2l")
+        g2l = make_resident(data["_g2l_" + self.pixel_dist], "g2l")
         n_samp = ob.n_local_samples
         pd, wd, sd = ob.detdata[self.pixels], ob.detdata[self.weights], ob.detdata[self.det_data]
         if self.det_flags is not None:
@@ -428,8 +395,6 @@ class BuildNoiseWeightedOnTheFly(BuildNoiseWeighted):
 
     def _exec(self, data, detectors=None, use_accel=None, **kwargs):
         from .. import capi
-        from ..accel import accel_device_ptr
-        from ..data import SharedData
         from .pointing import compact_pixel_cache, otf_descriptor
 
         if not use_accel:
@@ -443,15 +408,11 @@ class BuildNoiseWeightedOnTheFly(BuildNoiseWeighted):
         else:
             data[self.zmap] = PixelData(dist, np.float64, n_value=nnz)
             zmap = data[self.zmap]
-        _global_to(zmap, self.zmap, True, zero_new=not zmap.accel_exists() and zmap.host_is_zero())
+        accel_place(zmap, self.zmap, True, zero_new=not zmap.accel_exists() and zmap.host_is_zero())
         gkey = "_g2l_" + self.pixel_dist
         if gkey not in data:
             data[gkey] = SharedData(dist.global_submap_to_local, "g2l")
-        g2l = data[gkey]
-        if not g2l.accel_exists():
-            g2l.accel_create("g2l")
-        if not g2l.accel_in_use():
-            g2l.accel_update_device()
+        g2l = make_resident(data[gkey], "g2l")
         view = self.pixel_pointing.view
         for ob in data.obs:
             dets = ob.select_local_detectors(selection=detectors, flagmask=self.det_mask)
@@ -467,11 +428,7 @@ class BuildNoiseWeightedOnTheFly(BuildNoiseWeighted):
                                               accel_device_ptr(g2l.data))
             pt = otf_descriptor(ob, dets, self.pixel_pointing, self.stokes_weights, compact=compact)
             n_samp = ob.n_local_samples
-            dd = ob.detdata[self.det_data]
-            if not dd.accel_in_use():
-                if not dd.accel_exists():
-                    dd.accel_create(self.det_data)
-                dd.accel_update_device()
+            dd = make_resident(ob.detdata[self.det_data], self.det_data)
             flag_indx, flag_data, shared = self._flag_args(ob, dets, True)
             f_ptr, f_n = (accel_device_ptr(flag_data), n_samp) if self.det_flags is not None else (0, 0)
             s_ptr, s_n = (accel_device_ptr(shared), n_samp) if self.shared_flags is not None else (0, 0)
@@ -479,11 +436,9 @@ class BuildNoiseWeightedOnTheFly(BuildNoiseWeighted):
             if clean is not None:
                 # zmap += A^T N^-1 (d - M a): the template subtraction inside the accumulate kernel (MapMaker's fused
                 # final binning, here with the pointing evaluated on the fly)
-                from .mapmaker_solve import SolverLHS
-
                 tmpl, amps = clean
                 iob = data.obs.index(ob)
-                SolverLHS._resident(amps, f"{tmpl.name}_amplitudes")
+                make_resident(amps, f"{tmpl.name}_amplitudes")
                 capi.dev.otf_offset_clean_accumulate(
                     pt, tmpl._step_length(tmpl.step_time, tmpl._obs_rate[iob]), tmpl.det_amp_offsets(iob, dets),
                     tmpl._obs_views[iob], accel_device_ptr(amps.buffer), accel_device_ptr(amps.local_flags),
@@ -525,7 +480,7 @@ class BuildHitMap(_MapBuilder):
         else:
             data[self.hits] = PixelData(dist, np.int64, n_value=1)
             hits = data[self.hits]
-        _global_to(hits, self.hits, use_accel, zero_new=not hits.accel_exists() and hits.host_is_zero())
+        accel_place(hits, self.hits, use_accel, zero_new=not hits.accel_exists() and hits.host_is_zero())
         for ob in data.obs:
             dets = ob.select_local_detectors(selection=detectors, flagmask=self.det_mask)
             if len(dets) == 0:
@@ -581,7 +536,7 @@ class BuildInverseCovariance(_MapBuilder):
             else:
                 data[self.hits] = PixelData(dist, np.int64, n_value=1)
             hits = data[self.hits]
-            _global_to(hits, self.hits, use_accel, zero_new=not hits.accel_exists() and hits.host_is_zero())
+            accel_place(hits, self.hits, use_accel, zero_new=not hits.accel_exists() and hits.host_is_zero())
         if self.inverse_covariance in data:
             if data[self.inverse_covariance].distribution != dist:
                 raise RuntimeError("Existing inv cov '{}' has different data distribution".format(
@@ -591,8 +546,8 @@ class BuildInverseCovariance(_MapBuilder):
             nnz = self._weight_nnz(data, detectors)
             data[self.inverse_covariance] = PixelData(dist, np.float64, n_value=nnz * (nnz + 1) // 2)
             invcov = data[self.inverse_covariance]
-        _global_to(invcov, self.inverse_covariance, use_accel,
-                   zero_new=not invcov.accel_exists() and invcov.host_is_zero())
+        accel_place(invcov, self.inverse_covariance, use_accel,
+                    zero_new=not invcov.accel_exists() and invcov.host_is_zero())
         zmap = None
         if self._signal_rides_along(use_accel):
             if self.signal_map not in data:
@@ -600,7 +555,7 @@ class BuildInverseCovariance(_MapBuilder):
             zmap = data[self.signal_map]
             if zmap.distribution != dist:
                 raise RuntimeError("Existing map '{}' has different data distribution".format(self.signal_map))
-            _global_to(zmap, self.signal_map, True, zero_new=not zmap.accel_exists() and zmap.host_is_zero())
+            accel_place(zmap, self.signal_map, True, zero_new=not zmap.accel_exists() and zmap.host_is_zero())
         self.signal_in_one_sweep = []
         for ob in data.obs:
             dets = ob.select_local_detectors(selection=detectors, flagmask=self.det_mask)
@@ -634,13 +589,10 @@ class BuildInverseCovariance(_MapBuilder):
         (toast_hip_build_cov_hits_signal_dev); everything is on the device already (the Pipeline staged the inputs).
         Returns whether ONE kernel did all three."""
         from .. import capi
-        from ..accel import accel_device_ptr
-        from ..data import SharedData
-        from .mapmaker_solve import SolverLHS
 
         if "_g2l_" + self.pixel_dist not in data:
             data["_g2l_" + self.pixel_dist] = SharedData(dist.global_submap_to_local, "g2l")
-        g2l = SolverLHS._resident(data["_g2l_" + self.pixel_dist], "g2l")
+        g2l = make_resident(data["_g2l_" + self.pixel_dist], "g2l")
         n_samp = ob.n_local_samples
         pd, wd, sd = ob.detdata[self.pixels], ob.detdata[self.weights], ob.detdata[self.signal]
         if sd.dtype != np.float64:

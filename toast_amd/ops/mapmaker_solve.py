@@ -9,6 +9,7 @@ src/toast/ops/mapmaker_solve.py:27-229 (SolverRHS), :232-521 (SolverLHS), :524-7
 
 import numpy as np
 
+from ..accel import make_resident
 from ..data import defaults
 from ..templates import AmplitudesMap
 from ..traits import Bool, ImplementationType, Instance, Int, List, Unicode
@@ -218,10 +219,10 @@ class SolverRHS(Operator):
         for _attempt in range(4):
             gen0 = capi.accel_generation()
             # the binned map of the pass above is an INPUT here (the left-hand side only uses that buffer as scratch)
-            SolverLHS._resident(data[self.binning.binned], self.binning.binned)
+            make_resident(data[self.binning.binned], self.binning.binned)
             for ob in data.obs:
                 if self.det_data in ob.detdata:
-                    SolverLHS._resident(ob.detdata[self.det_data], self.det_data)
+                    make_resident(ob.detdata[self.det_data], self.det_data)
             ctx = lhs._fused_prepare(data, detectors)
             if capi.accel_generation() == gen0:
                 break
@@ -339,17 +340,6 @@ class SolverLHS(Operator):
         if self.binning.stokes_weights.mode not in ("I", "IQU"):
             return False
         return True
-
-    @staticmethod
-    def _resident(obj, name):
-        """Make the device copy of an AcceleratorObject current and leave it there."""
-        if getattr(obj, "buffer", None) is not None and obj.buffer.size == 0:
-            return obj   # an observation without valid detectors: nothing to hold
-        if not obj.accel_exists():
-            obj.accel_create(name)
-        if not obj.accel_in_use():
-            obj.accel_update_device()
-        return obj
 
     def __del__(self):
         try:
@@ -611,8 +601,8 @@ class SolverLHS(Operator):
             if cached:
                 # do not drag the detector quaternions (4x the pixel volume) to the device again
                 for ob in data.obs:
-                    self._resident(ob.detdata[pixels_op.pixels], pixels_op.pixels)
-                    self._resident(ob.detdata[weights_op.weights], weights_op.weights)
+                    make_resident(ob.detdata[pixels_op.pixels], pixels_op.pixels)
+                    make_resident(ob.detdata[weights_op.weights], weights_op.weights)
             else:
                 pixels_op.apply(data, detectors=detectors, use_accel=True)
                 weights_op.apply(data, detectors=detectors, use_accel=True)
@@ -623,13 +613,13 @@ class SolverLHS(Operator):
         zmap = data[binning.binned]
         if not zmap.accel_exists():
             zmap.accel_create(binning.binned, zero_out=True)
-        cov = self._resident(data[binning.covariance], binning.covariance)
+        cov = make_resident(data[binning.covariance], binning.covariance)
         if "_g2l_" + binning.pixel_dist not in data:
             from ..data import SharedData
 
             data["_g2l_" + binning.pixel_dist] = SharedData(dist.global_submap_to_local, "g2l")
-        g2l = self._resident(data["_g2l_" + binning.pixel_dist], "g2l")
-        self._resident(amps_in, f"{tmpl.name}_in")
+        g2l = make_resident(data["_g2l_" + binning.pixel_dist], "g2l")
+        make_resident(amps_in, f"{tmpl.name}_in")
         if not amps_out.accel_exists():
             amps_out.accel_create(f"{tmpl.name}_out", zero_out=True)
         ctx = dict(on_the_fly=on_the_fly, nnz=nnz, nps=dist.n_pix_submap, n_local=dist.n_local_submap,
@@ -658,12 +648,12 @@ class SolverLHS(Operator):
                       nav=tmpl._obs_views[iob], n_samp=n_samp, ivl=ob.intervals[pixels_op.view].data,
                       detw=np.array([noise.detector_weight(d) for d in dets], dtype=np.float64))
             if binning.det_flags is not None:
-                fd = self._resident(ob.detdata[binning.det_flags], binning.det_flags)
+                fd = make_resident(ob.detdata[binning.det_flags], binning.det_flags)
                 ps.update(f_idx=fd.indices(dets), f_ptr=accel_device_ptr(fd.buffer), f_ns=n_samp)
             else:
                 ps.update(f_idx=np.zeros(len(dets), np.int32), f_ptr=0, f_ns=0)
             if binning.shared_flags is not None:
-                sf = self._resident(ob.shared[binning.shared_flags], binning.shared_flags)
+                sf = make_resident(ob.shared[binning.shared_flags], binning.shared_flags)
                 ps.update(s_ptr=accel_device_ptr(sf.data), s_n=n_samp)
             else:
                 ps.update(s_ptr=0, s_n=0)

@@ -20,7 +20,7 @@ split in the sample direction.
 import numpy as np
 
 from .. import capi
-from ..accel import accel_device_ptr, accel_enabled
+from ..accel import Resident, accel_device_ptr, accel_enabled, make_resident
 from ..data import defaults
 from ..noise import Noise, name_UID
 from ..traits import Bool, Float, Instance, Int, List, TraitError, Unicode
@@ -49,24 +49,6 @@ class _Scratch:
 
     def free(self):
         capi.device_free(self.ptr)
-
-
-class _Resident:
-    """The device copy of an observation's flag array: the resident one, or a temporary upload."""
-
-    def __init__(self, obj, name):
-        self.obj, self.temporary = obj, False
-        if not obj.accel_exists():
-            obj.accel_create(name)
-            obj._accel_update_device()
-            self.temporary = True
-        elif not obj.accel_in_use():
-            obj._accel_update_device()       # the host side stays the current one
-        self.ptr = accel_device_ptr(obj.buffer if hasattr(obj, "buffer") else obj.data)
-
-    def release(self):
-        if self.temporary:
-            self.obj.accel_delete()
 
 
 class NoiseEstim(Operator):
@@ -294,11 +276,7 @@ class NoiseEstim(Operator):
 
     # ------------------------------------------------------------------------------------------------ device path
     def _estimate_device(self, obs, dd, todo, times, plan):
-        if not dd.accel_in_use():
-            if not dd.accel_exists():
-                dd.accel_create(self.det_data)
-            dd.accel_update_device()
-            dd.accel_used(True)
+        make_resident(dd, self.det_data)
         n_rows, n = dd.buffer.shape
         held = []
         try:
@@ -308,13 +286,13 @@ class NoiseEstim(Operator):
                 sh = obs.shared[self.shared_flags]
                 if sh.data.dtype != np.uint8:
                     raise RuntimeError("NoiseEstim: shared flags must be uint8 on the device path")
-                held.append(_Resident(sh, self.shared_flags))
+                held.append(Resident(sh, self.shared_flags))
                 d_shared = held[-1].ptr
             if self.det_flags is not None:
                 fl = obs.detdata[self.det_flags]
                 if fl.dtype != np.dtype(np.uint8) or fl.buffer.shape[1] != n:
                     raise RuntimeError("NoiseEstim: detector flags must be uint8 on the device path")
-                held.append(_Resident(fl, self.det_flags))
+                held.append(Resident(fl, self.det_flags))
                 d_flags, n_flag_rows = held[-1].ptr, fl.buffer.shape[0]
             lagmax = plan["lagmax"]
             _, _, nreal1, nloc1, seg1 = plan["full"]
@@ -331,8 +309,9 @@ class NoiseEstim(Operator):
                 part = todo[b0:b0 + batch]
                 yield from self._device_batch(obs, dd, part, n_rows, n, d_shared, d_flags, n_flag_rows, plan)
         finally:
-            for h in held:
-                h.release()
+            for h in held:      # the flags were only read: the resident copy stays, a temporary upload goes
+                h.host_stays_current()
+                h.drop_if_created()
 
     def _device_batch(self, obs, dd, part, n_rows, n, d_shared, d_flags, n_flag_rows, plan):
         dev = capi.dev

@@ -4,7 +4,7 @@ rocFFT pipeline (reference: src/toast/ops/noise_filter.py:20-205 -> toast.fft.co
 import numpy as np
 
 from .. import fft as hipfft
-from ..accel import accel_enabled
+from ..accel import accel_enabled, make_resident
 from ..data import defaults
 from ..traits import Float, Int, Unicode
 from .operator import Operator
@@ -211,10 +211,8 @@ class NoiseFilter(Operator):
                         from .. import capi
 
                         capi.accel_update_device_wait(fdata.buffer, 0)       # the stream waits, the host does not
-                    elif not fdata.accel_in_use():
-                        if not fdata.accel_exists():
-                            fdata.accel_create(self.det_flags)
-                        fdata.accel_update_device()
+                    else:
+                        make_resident(fdata, self.det_flags)
                     hipfft.extend_flags_buffer(fdata.buffer, fdata.indices(dets), flag_mask, extend, or_row=shflg,
                                                use_accel=True)
                     if flags_in_flight:

@@ -8,25 +8,13 @@ construction, same ``exists -> skip`` logic; the kernels are the HIP library's.
 
 import numpy as np
 
-from ..accel import native
+from ..accel import accel_place, make_resident, native
 from ..data import defaults
 from ..pixels import PixelDistribution, unify_local_submaps
 from ..traits import Bool, Float, ImplementationType, Instance, Int, Unicode
 from .operator import Operator
 
 _IMPLS = [ImplementationType.DEFAULT, ImplementationType.COMPILED]
-
-
-def _shared_to(ob, name, use_accel):
-    """Put a shared object where the kernel will look for it (pointing_detector.py:168-177)."""
-    obj = ob.shared[name]
-    if use_accel:
-        if not obj.accel_in_use():
-            if not obj.accel_exists():
-                obj.accel_create(name)
-            obj.accel_update_device()
-    elif obj.accel_in_use():
-        obj.accel_update_host()
 
 
 # J2000 coordinate transforms: the rotation matrices of src/toast/qarray.py:676-768 (equatorial ->
@@ -149,9 +137,10 @@ class PointingDetectorSimple(Operator):
         if (self.coord_in is None) != (self.coord_out is None):
             raise RuntimeError("Input and output coordinate systems should both be None or valid")
         for ob in data.obs:
-            _shared_to(ob, self.effective_boresight(ob), use_accel)
+            bore_key = self.effective_boresight(ob)
+            accel_place(ob.shared[bore_key], bore_key, use_accel)
             if self.shared_flags is not None:
-                _shared_to(ob, self.shared_flags, use_accel)
+                accel_place(ob.shared[self.shared_flags], self.shared_flags, use_accel)
         for ob in data.obs:
             dets = ob.select_local_detectors(detectors, flagmask=self.det_mask)
             exists = ob.detdata.ensure(self.quats, sample_shape=(4,), dtype=np.float64, detectors=dets,
@@ -219,12 +208,12 @@ def otf_descriptor(ob, dets, pixels_op, weights_op, compact=None):
 
     dp = (pixels_op if pixels_op is not None else weights_op).detector_pointing
     bore_key = dp.effective_boresight(ob)
-    _shared_to(ob, bore_key, True)
+    make_resident(ob.shared[bore_key], bore_key)
     bore = accel_device_ptr(ob.shared[bore_key].data)
     n_samp = ob.n_local_samples
     d_flags, n_flags = 0, 0
     if dp.shared_flags is not None:
-        _shared_to(ob, dp.shared_flags, True)
+        make_resident(ob.shared[dp.shared_flags], dp.shared_flags)
         d_flags, n_flags = accel_device_ptr(ob.shared[dp.shared_flags].data), n_samp
     focalplane = ob.telescope.focalplane
     fp_quats = np.array([focalplane[d]["quat"] for d in dets], dtype=np.float64).reshape(len(dets), 4)
@@ -235,7 +224,7 @@ def otf_descriptor(ob, dets, pixels_op, weights_op, compact=None):
     gamma = np.zeros(len(dets), dtype=np.float64)
     d_hwp, n_hwp, extra_tab = 0, 0, 0
     if nnz == 3 and weights_op.hwp_angle is not None and weights_op.hwp_angle in ob.shared:
-        _shared_to(ob, weights_op.hwp_angle, True)
+        make_resident(ob.shared[weights_op.hwp_angle], weights_op.hwp_angle)
         d_hwp, n_hwp = accel_device_ptr(ob.shared[weights_op.hwp_angle].data), n_samp
         gamma = np.array([focalplane[d][weights_op.fp_gamma] for d in dets], dtype=np.float64)
         # (cos 4 hwp, sin 4 hwp) per time sample, built once per observation and shared by all
@@ -250,9 +239,10 @@ def otf_descriptor(ob, dets, pixels_op, weights_op, compact=None):
             capi.dev.hwp_table(d_hwp, n_samp, accel_device_ptr(tab.data))
             tab.accel_used(True)
         tab = ob.shared[tkey]
-        if not tab.accel_exists():      # evicted: the values live on the host copy
-            tab.accel_create(tkey)
-            tab.accel_update_device()
+        # evicted: the values live on the host copy.  The guard stays: a table that is registered with the host current
+        # (its values were fetched, never edited) is used as it is, without another upload.
+        if not tab.accel_exists():
+            make_resident(tab, tkey)
         extra_tab = accel_device_ptr(tab.data)
     extra = {}
     if compact is not None:
@@ -588,7 +578,7 @@ class StokesWeights(Operator):
                 if self.hwp_angle is None or self.hwp_angle not in ob.shared:
                     hwp_data = np.zeros(1, dtype=np.float64)
                 else:
-                    _shared_to(ob, self.hwp_angle, use_accel)
+                    accel_place(ob.shared[self.hwp_angle], self.hwp_angle, use_accel)
                     hwp_data = ob.shared[self.hwp_angle].data
                     for idet, d in enumerate(dets):
                         det_gamma[idet] = focalplane[d][self.fp_gamma]

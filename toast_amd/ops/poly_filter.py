@@ -32,12 +32,14 @@ import re
 import numpy as np
 
 from ..accel import (
+    Resident,
     accel_data_create,
     accel_data_delete,
     accel_data_update_device,
     accel_data_update_host,
     accel_device_ptr,
     accel_enabled,
+    make_resident,
     native,
 )
 from ..data import defaults, detector_direction
@@ -77,47 +79,29 @@ def _positive(name, value):
 
 
 class _Resident:
-    """Timestreams, detector flags and shared flags of one observation on the device, the way GroundFilter._exec
-    makes them resident; ``release`` leaves the timestreams there under ``data.lazy_host``."""
+    """Timestreams, detector flags and shared flags of one observation on the device; ``release`` leaves the
+    timestreams there under ``data.lazy_host``, the flags stay in any case."""
 
     def __init__(self, obs, det_data, det_flags, shared_flags):
         self.dd = obs.detdata[det_data]
         if self.dd.dtype != np.dtype(np.float64):
             raise RuntimeError(f"detdata '{det_data}' is {self.dd.dtype}: the device filters work in place on float64 "
                                "timestreams (the reference converts other types to float64 and back)")
-        self.made_resident = False
-        if not self.dd.accel_in_use():
-            if not self.dd.accel_exists():
-                self.dd.accel_create(det_data)
-            self.dd.accel_update_device()
-            self.made_resident = True
-        self.sig_ptr = accel_device_ptr(self.dd.buffer)
+        self.signal = Resident(self.dd, det_data)
+        self.sig_ptr = self.signal.ptr
         self.flag_ptr, self.fd = 0, None
         if det_flags is not None:
-            self.fd = obs.detdata[det_flags]
-            if not self.fd.accel_in_use():
-                if not self.fd.accel_exists():
-                    self.fd.accel_create(det_flags)
-                self.fd.accel_update_device()
+            self.fd = make_resident(obs.detdata[det_flags], det_flags)
             self.flag_ptr = accel_device_ptr(self.fd.buffer)
-        self.shared_ptr, self.sf = 0, None
+        self.shared_ptr = 0
         if shared_flags is not None:
-            self.sf = obs.shared[shared_flags]
-            if not self.sf.accel_in_use():
-                if not self.sf.accel_exists():
-                    self.sf.accel_create(shared_flags)
-                self.sf.accel_update_device()
-            self.shared_ptr = accel_device_ptr(self.sf.data)
+            self.shared_ptr = accel_device_ptr(make_resident(obs.shared[shared_flags], shared_flags).data)
 
     def flag_index(self, dets):
         return self.fd.indices(dets) if self.fd is not None else None
 
     def release(self, data):
-        if self.made_resident and not getattr(data, "lazy_host", False):
-            self.dd.accel_update_host()
-            self.dd.accel_delete()
-        else:
-            self.dd.accel_used(True)
+        self.signal.write_back_unless_lazy(data)
 
 
 class PolyFilter(Operator):

@@ -16,7 +16,7 @@ Two paths, chosen by where ``det_data`` lives:
 import numpy as np
 
 from .. import capi
-from ..accel import accel_device_ptr, accel_enabled
+from ..accel import accel_device_ptr, accel_enabled, make_resident
 from ..data import defaults
 from ..traits import Bool, Int, TraitError, Unicode
 from .operator import Operator
@@ -105,11 +105,7 @@ class SimNoise(Operator):
             if on_device:
                 if not accel_enabled():
                     raise RuntimeError("SimNoise: use_accel=True needs the HIP library and an assigned device")
-                if not dd.accel_in_use():
-                    if not dd.accel_exists():
-                        dd.accel_create(self.det_data)
-                    dd.accel_update_device()
-                    dd.accel_used(True)
+                make_resident(dd, self.det_data)
                 ptr, rows, weights = [0], [], []
                 for key in keys:
                     for det in dets:

@@ -6,7 +6,7 @@ import numpy as np
 
 from .. import fft as hipfft
 from .. import rng
-from ..accel import accel_enabled
+from ..accel import Resident, accel_enabled
 from ..data import defaults
 from ..noise import name_UID
 from ..traits import Bool, Float, Int, Unicode
@@ -79,33 +79,22 @@ class TimeConstant(Operator):
                 extend = hipfft.impulse_extents_pole(len(dets), n_samp, rate, taus, invert)
                 if np.any(extend == n_samp):
                     raise RuntimeError("Impulse response spreads to all samples")
-            on_dev = dd.accel_in_use()
-            made_resident = False
-            if not on_dev and accel_enabled():
+            on_dev = dd.accel_in_use() or accel_enabled()
+            if on_dev:
                 # one page-locked upload instead of pageable staging; with lazy host coherence the filtered
                 # timestream stays resident for the operators that follow
-                if not dd.accel_exists():
-                    dd.accel_create(self.det_data)
-                dd.accel_update_device()
-                on_dev = made_resident = True
+                signal = Resident(dd, self.det_data)
             hipfft.convolve_buffer_pole(dd.arg(on_dev), idx, rate, taus, invert, use_accel=on_dev)
-            if made_resident and not getattr(data, "lazy_host", False):
-                dd.accel_update_host()
-                dd.accel_delete()
+            if on_dev:
+                signal.write_back_unless_lazy(data)
             if extend is not None:
                 # shared flags + extend_flags + first / last samples (fft.py:935-945) in one device pass
                 fdata = obs.detdata[self.det_flags]
                 if accel_enabled():
-                    flags_made_resident = not fdata.accel_in_use()
-                    if flags_made_resident:
-                        if not fdata.accel_exists():
-                            fdata.accel_create(self.det_flags)
-                        fdata.accel_update_device()
+                    flags = Resident(fdata, self.det_flags)
                     hipfft.extend_flags_buffer(fdata.buffer, fdata.indices(dets), self.det_flag_mask, extend,
                                                or_row=shflg, use_accel=True)
-                    if flags_made_resident and not getattr(data, "lazy_host", False):
-                        fdata.accel_update_host()
-                        fdata.accel_delete()
+                    flags.write_back_unless_lazy(data)
                 else:
                     hipfft.extend_flags_buffer(fdata.data, fdata.indices(dets), self.det_flag_mask, extend, or_row=shflg)
 

@@ -12,6 +12,7 @@ import numpy as np
 
 from .accel import (
     AcceleratorObject,
+    Resident,
     accel_data_create,
     accel_data_delete,
     accel_data_present,
@@ -20,6 +21,7 @@ from .accel import (
     accel_data_update_host,
     accel_device_ptr,
     accel_hold,
+    make_resident,
     native,
 )
 
@@ -485,20 +487,13 @@ class PixelData(AcceleratorObject):
 
         @contextlib.contextmanager
         def ctx():
-            moved = not self.accel_in_use()
-            created = False
-            if moved:
-                if not self.accel_exists():
-                    self.accel_create(self._accel_name)
-                    created = True
-                self.accel_update_device()
+            mine = Resident(self, self._accel_name)
             try:
                 yield
             finally:
-                if moved:
+                if mine.uploaded:
                     self.accel_update_host()
-                    if created:
-                        self.accel_delete()
+                    mine.drop_if_created()
 
         return ctx()
 
@@ -648,13 +643,6 @@ def _mapnnz(npp):
     return int(((np.sqrt(8 * npp.n_value) - 1) / 2) + 0.5)
 
 
-def _ensure_on_device(obj, name):
-    if not obj.accel_in_use():
-        if not obj.accel_exists():
-            obj.accel_create(name)
-        obj.accel_update_device()
-
-
 def _owner_computes_on_device(pd):
     w = pd.distribution._world()
     return w is not None and pd._device_collectives(w)
@@ -689,7 +677,7 @@ class create_local_apply(_LocalFunc):
         from . import capi
 
         with accel_hold(m):
-            _ensure_on_device(self.cov, "covariance")
+            make_resident(self.cov, "covariance")
         capi.dev.comm_map_reduce_apply(m.buffer.size // m.n_value, self.mapnnz, accel_device_ptr(self.cov.buffer),
                                        accel_device_ptr(m.buffer), reduce=reduce)
 
@@ -757,7 +745,7 @@ class create_local_multiply(_LocalFunc):
         from . import capi
 
         with accel_hold(npp1):
-            _ensure_on_device(self.other, "covariance2")
+            make_resident(self.other, "covariance2")
         capi.dev.comm_cov_mult(npp1.buffer.size // npp1.n_value, self.mapnnz, accel_device_ptr(npp1.buffer),
                                accel_device_ptr(self.other.buffer))
 
@@ -783,7 +771,7 @@ def covariance_apply(npp, m, use_alltoallv=False):
     on_dev = m.accel_in_use()
     if on_dev:
         with accel_hold(m):
-            _ensure_on_device(npp, "covariance")
+            make_resident(npp, "covariance")
     elif npp.accel_in_use():
         npp.accel_update_host()
     native().cov_apply_diag(npp.distribution.n_local_submap, npp.distribution.n_pix_submap, mapnnz,
@@ -826,7 +814,7 @@ def covariance_multiply(npp1, npp2, use_alltoallv=False):
         on_dev = npp1.accel_in_use()
         if on_dev:
             with accel_hold(npp1):
-                _ensure_on_device(npp2, "covariance2")
+                make_resident(npp2, "covariance2")
         elif npp2.accel_in_use():
             npp2.accel_update_host()
         native().cov_mult_diag(npp1.distribution.n_local_submap, npp1.distribution.n_pix_submap, mapnnz,

@@ -22,7 +22,9 @@ from ..accel import (
     accel_data_update_device,
     accel_data_update_host,
     accel_device_ptr,
+    make_resident,
     native,
+    release_borrowed,
 )
 from ..data import defaults
 from ..traits import Any, Bool, Float, ImplementationType, Int, TraitConfig, Unicode
@@ -139,13 +141,7 @@ class Amplitudes(AcceleratorObject):
         """Make the device copy current and keep working there: later arithmetic (``+=``,
         ``axpby``, ``dot`` ...) runs in device kernels (toast_hip_vec_*_dev) until
         ``accel_update_host``."""
-        if self._n_local == 0:
-            return self
-        if not self.accel_exists():
-            self.accel_create(name)
-        if not self.accel_in_use():
-            self.accel_update_device()
-        return self
+        return make_resident(self, name)
 
     def _device_pair(self, other):
         """True when the operation should run on the device: either operand's device copy is
@@ -945,26 +941,6 @@ class Offset(Template):
 
 
 # ---- used by the shared methods of Template and by the set-up code of the templates
-def make_resident(obj, name, borrowed=None):
-    """Make the device copy of ``obj`` current.  ``borrowed``: a list that collects the objects this call had to upload,
-    for ``release_borrowed`` -- set-up code that only READS them hands the host side back as the current one."""
-    if not obj.accel_in_use():
-        if not obj.accel_exists():
-            obj.accel_create(name)
-        obj.accel_update_device()
-        if borrowed is not None:
-            borrowed.append(obj)
-    return obj
-
-
-def release_borrowed(borrowed):
-    """The objects were only read on the device: the host copy is still right and becomes the current side again, so a
-    later edit on the host is uploaded instead of being shadowed by a stale device copy."""
-    for obj in borrowed:
-        obj.accel_used(False)
-    del borrowed[:]
-
-
 def block_amp_offsets(cache, det_start, obs_dets, per_obs, iob, dets):
     """First amplitude of each detector's block for observation ``iob`` in a detector-major layout where observation
     ``job`` contributes ``per_obs[job]`` amplitudes to every detector it holds; cached in ``cache``."""
