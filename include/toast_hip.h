@@ -815,7 +815,10 @@ int toast_hip_template_offset_banded_cholesky_dev(
  *     d_gram_flagged[d][r][c] = the same sum over samples with good shared flags that detector d flags
  *     d_n_flagged[d]          = the number of those samples
  *   so that bin_invcov of detector d is d_gram_common - d_gram_flagged[d].  All four outputs are
- *   overwritten.  d_det_flags / d_shared_flags may be NULL (no flags of that kind).
+ *   overwritten.  d_det_flags / d_shared_flags may be NULL (no flags of that kind).  The signal of
+ *   a sample with good[d][i] == 0 is not multiplied by 0 but replaced by 0: a NaN or Inf there
+ *   reaches no projection (the reference's `signal[i] * good[i]` would hand it on), while one in a
+ *   good sample makes row d of d_proj, and only that row, NaN.
  * toast_hip_template_subtract_dev: signal[d][i] -= sum_{r >= first_template} coeff[d][r] T[r][i]
  *   for ALL samples, the sum accumulated from zero in template order (add_templates into a zeroed
  *   buffer, then `ref -= fit`: groundfilter.py:384-393).  d_coeff is [n_det][n_template].

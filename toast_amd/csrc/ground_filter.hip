@@ -16,6 +16,7 @@
 //                         (bin_invcov: a detector's Gram matrix differs from the common one only by its
 //                         own flagged samples -- ~1 % of them -- instead of n_template^2/2 FMAs for
 //                         every det-sample)
+//   k_template_mirror     the two Gram kernels add into upper triangles; the lower ones are copies
 //   k_template_subtract   signal[d][i] -= sum_r coeff[d][r] T[r][i]           (add_templates + `ref -= fit`)
 //
 // All of them are HBM / LDS bound: 9 B (signal + flag) per det-sample for the projection, 16 B for
@@ -97,10 +98,9 @@ __global__ __launch_bounds__(kThreads) void k_template_gram(
         if (good) acc += tr[i] * tc[i];
     }
     const double total = block_sum(acc, scratch);
-    if (threadIdx.x == 0 && total != 0.0) {
-        atomicAdd(&gram[r * n_template + c], total);
-        if (c != r) atomicAdd(&gram[c * n_template + r], total);
-    }
+    // upper triangle only: k_template_mirror copies it, so that G is symmetric to the bit however the atomics of the
+    // slices are ordered
+    if (threadIdx.x == 0 && total != 0.0) atomicAdd(&gram[r * n_template + c], total);
 }
 
 // proj[d][r] = sum_i T[r][i] signal[d][i] good[d][i].  One WAVE per (slice of samples, DPW
@@ -226,18 +226,28 @@ __global__ __launch_bounds__(kThreads) void k_template_gram_flagged(
                     const double * __restrict__ tc = templates + c * n_samp + base;
                     double acc = 0.0;
                     for (int q = 0; q < nq; ++q) acc += tr[queue[q]] * tc[queue[q]];
-                    if (acc != 0.0) {
-                        atomicAdd(&out[r * n_template + c], acc);
-                        if (c != r) atomicAdd(&out[c * n_template + r], acc);
-                    }
+                    if (acc != 0.0) atomicAdd(&out[r * n_template + c], acc);   // upper triangle: k_template_mirror
                 }
             }
         }
         __syncthreads();
     }
-    if (one_pair && threadIdx.x < n_pair && slice_acc != 0.0) {
-        atomicAdd(&out[my_r * n_template + my_c], slice_acc);
-        if (my_c != my_r) atomicAdd(&out[my_c * n_template + my_r], slice_acc);
+    if (one_pair && threadIdx.x < n_pair && slice_acc != 0.0) atomicAdd(&out[my_r * n_template + my_c], slice_acc);
+}
+
+// The Gram kernels add into the upper triangles only; M[c][r] = M[r][c] afterwards.  Matrix 0 is G, matrix 1 + d is D_d.
+// (Adding into both triangles left them different in the last bits once three slices shared an entry: the atomics of
+// the blocks reach [r][c] and [c][r] in different orders.  The reference's bin_invcov copies, toast_tod_filter.cpp:208.)
+__global__ __launch_bounds__(kThreads) void k_template_mirror(int64_t n_template, int64_t n_matrix, double * __restrict__ gram,
+                                                              double * __restrict__ dgram) {
+    const int64_t per = n_template * n_template;
+    const int64_t total = per * n_matrix;
+    for (int64_t idx = (int64_t)blockIdx.x * kThreads + threadIdx.x; idx < total; idx += (int64_t)gridDim.x * kThreads) {
+        const int64_t m = idx / per, e = idx - m * per;
+        const int64_t r = e / n_template, c = e - r * n_template;
+        if (r <= c) continue;
+        double * __restrict__ mat = (m == 0) ? gram : dgram + (m - 1) * per;
+        mat[r * n_template + c] = mat[c * n_template + r];
     }
 }
 
@@ -362,6 +372,12 @@ int toast_hip_template_fit_dev(const double * d_templates, int64_t n_template, i
             hipLaunchKernelGGL(k_template_gram_flagged, dim3((unsigned)((n_samp + fslice - 1) / fslice), (unsigned)n_det),
                                dim3(kThreads), 0, st, d_templates, n_template, n_samp, fidx, d_det_flags, det_flag_mask,
                                d_shared_flags, shared_flag_mask, fslice, d_gram_flagged, d_n_flagged);
+            check_launch();
+        }
+        if (n_template > 1) {
+            const int64_t n_matrix = 1 + (d_det_flags != nullptr ? n_det : 0);   // without flags D stays the zeros it was set to
+            hipLaunchKernelGGL(k_template_mirror, flat_grid(n_matrix * n_template * n_template), dim3(kThreads), 0, st,
+                               n_template, n_matrix, d_gram_common, d_gram_flagged);
             check_launch();
         }
     });
