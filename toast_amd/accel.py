@@ -187,6 +187,123 @@ def accel_device_ptr(data):
     return int(native().accel_device_ptr(_key(data)))
 
 
+class DeviceMirror:
+    """A host array that a template derives at set-up, its device copy under one registration name, and which side is
+    current: host only, both, or device newer (then the first ``host`` access fetches the values, once)."""
+
+    def __init__(self, buffer, name):
+        self.buffer = buffer        # the host array WITHOUT synchronisation: the accelerator key
+        self.name = name
+        self.on_device = False      # registered on the device?
+        self.stale = False          # device newer than host?
+
+    def create(self, zero_out=False):
+        """Register without an upload, as the side that kernels write; ``written()`` once they were launched."""
+        accel_data_create(self.buffer, self.name, zero_out=zero_out, owner=self)
+        self.on_device = True
+        return self
+
+    def upload(self):
+        """Make sure the host values are on the device (copied once; the host array does not change afterwards)."""
+        if not self.on_device:
+            self.create()
+            accel_data_update_device(self.buffer, self.name)
+        return self
+
+    @property
+    def ptr(self):
+        return accel_device_ptr(self.buffer)
+
+    def written(self):
+        self.stale = True
+
+    @property
+    def host(self):
+        """The host array, brought up to date first."""
+        if self.stale:
+            self.stale = False
+            accel_data_update_host(self.buffer, self.name)
+        return self.buffer
+
+    def drop(self, fetch=True):
+        """Release the device copy; ``fetch``: somebody may still read the values on the host."""
+        if self.on_device:
+            if fetch:
+                _ = self.host
+            accel_data_delete(self.buffer, self.name)
+        self.on_device = self.stale = False
+
+
+class device_scratch:
+    """``with device_scratch(prefix, owner=op) as s: ...`` -- small host arrays mirrored on the device for the span of a
+    few kernel calls, registered as ``f"{prefix}_{key}"`` (the bare key when ``prefix`` is None).  The role says what is
+    copied: ``inp`` up at registration, ``out`` down on a normal exit, ``inout`` both, ``work`` neither; each returns its
+    host array.  A normal exit synchronizes once, downloads in registration order and releases everything; an exception
+    (also one from a later registration) only releases.  Empty arrays are never registered: their pointer is 0."""
+
+    def __init__(self, prefix=None, owner=None, kind=KIND_DEFAULT):
+        self._prefix, self._owner, self._kind = prefix, owner, kind
+        self._entries = {}      # key -> (host array, registration name, downloaded on a normal exit?)
+
+    def __enter__(self):
+        return self
+
+    def _add(self, key, arr, upload, download):
+        name = key if self._prefix is None else f"{self._prefix}_{key}"
+        accel_data_create(arr, name, owner=self._owner, kind=self._kind)
+        self._entries[key] = (arr, name, download)
+        if upload:
+            accel_data_update_device(arr, name)
+        return arr
+
+    def inp(self, key, arr):
+        return self._add(key, arr, True, False)
+
+    def out(self, key, arr):
+        return self._add(key, arr, False, True)
+
+    def inout(self, key, arr):
+        return self._add(key, arr, True, True)
+
+    def work(self, key, arr):
+        return self._add(key, arr, False, False)
+
+    def ptr(self, key):
+        return accel_device_ptr(self._entries[key][0])
+
+    def fetch(self, key):
+        """The host needs one entry inside the block: wait for the kernels and download it."""
+        arr, name, _ = self._entries[key]
+        if _key(arr).size > 0:
+            native().accel_synchronize()
+        return accel_data_update_host(arr, name)
+
+    def __exit__(self, exc_type, exc, tb):
+        live = [entry for entry in self._entries.values() if _key(entry[0]).size > 0]
+        self._entries = {}
+        unwinding = exc is not None
+        try:
+            if not unwinding and live:
+                native().accel_synchronize()
+                for arr, name, download in live:
+                    if download:
+                        accel_data_update_host(arr, name)
+        except BaseException:
+            unwinding = True
+            raise
+        finally:
+            failed = None
+            for arr, name, _ in live:
+                try:
+                    accel_data_delete(arr, name)
+                except Exception as err:
+                    failed = failed or err
+            # (every entry was tried; a release that fails while an error is on its way out does not replace that error)
+            if failed is not None and not unwinding:
+                raise failed
+        return False
+
+
 class accel_hold:
     """``with accel_hold(a, b): ...`` -- the device copies of ``a`` and ``b`` are not evicted inside the block
     (``Data.accel_evict`` skips held objects).  For code outside a Pipeline that allocates device memory while it

@@ -34,8 +34,7 @@ import numpy as np
 from scipy.signal import fftconvolve, firwin
 
 from .. import capi
-from ..accel import (Resident, accel_data_create, accel_data_delete, accel_data_update_device, accel_device_ptr,
-                     accel_enabled, make_resident)
+from ..accel import Resident, accel_device_ptr, accel_enabled, device_scratch, make_resident
 from ..data import Data, Focalplane, IntervalList, Observation, Telescope, defaults
 from ..noise import Noise, name_UID
 from ..traits import Bool, Float, Instance, Int, TraitError, Unicode
@@ -577,46 +576,43 @@ class Demodulate(Operator):
                 raise RuntimeError("Demodulate: the device path reads float64 Stokes weights")
             make_resident(wd, wname)
             wrows = [int(r) for r in wd.indices(part)]
-            scratch = capi.device_malloc(nb * n * 8)
-            factors = None
-            try:
-                if self.do_2f:
-                    # sequential per detector: on the host, with the reference's statements
-                    factors = np.empty((2 * nb, n), dtype=np.float64)
-                    host_w = np.array(wd.data)
-                    wd.accel_used(True)             # the download changed nothing: the device copy is still current
-                    for b, det in enumerate(part):
-                        qw, uw = host_w[wd.indices([det])[0]].T[comp_q:comp_q + 2]
-                        if "QU" in self.mode:
-                            # remove polarization efficiency from the Q/U weights
-                            qw = qw * (1 / np.sqrt(qw**2 + uw**2))
-                        factors[b], factors[nb + b] = half_angle_factors(qw)
-                    accel_data_create(factors, "demod_2f_factors")
-                    accel_data_update_device(factors, "demod_2f_factors")
-                for flavor in flavors:
-                    dd, out = obs.detdata[flavor], demod_obs.detdata[flavor]
-                    d_in = accel_device_ptr(dd.buffer)
-                    rows = list(range(nb))
-                    if "QU" in self.mode:
-                        dev.demod_fir(n, bandpass4f.bpf, 1, 0, d_in, dd.buffer.shape[0], n, dd.indices(part), scratch, nb,
-                                      n, rows)
-                        fir(rows + rows, scratch, nb, lowpass.lpf, self.nskip, offset, out,
-                            [f"demod4r_{d}" for d in part] + [f"demod4i_{d}" for d in part],
-                            mod_mode=capi.DEMOD_MOD_WEIGHTS, d_mod=accel_device_ptr(wd.buffer),
-                            n_mod_rows=wd.buffer.shape[0], mod_stride=n * nnz, mod_row=wrows + wrows,
-                            mod_comp=[comp_q] * nb + [comp_q + 1] * nb, nnz=nnz, comp_q=comp_q)
+            with device_scratch() as s:
+                scratch = capi.device_malloc(nb * n * 8)
+                try:
                     if self.do_2f:
-                        dev.demod_fir(n, bandpass2f.bpf, 1, 0, d_in, dd.buffer.shape[0], n, dd.indices(part), scratch, nb,
-                                      n, rows)
-                        fir(rows + rows, scratch, nb, lowpass.lpf, self.nskip, offset, out,
-                            [f"demod2r_{d}" for d in part] + [f"demod2i_{d}" for d in part],
-                            mod_mode=capi.DEMOD_MOD_ARRAY, d_mod=accel_device_ptr(factors), n_mod_rows=2 * nb,
-                            mod_stride=n, mod_row=list(range(2 * nb)))
-            finally:
-                capi.synchronize()
-                capi.device_free(scratch)
-                if factors is not None:
-                    accel_data_delete(factors, "demod_2f_factors")
+                        # sequential per detector: on the host, with the reference's statements
+                        factors = np.empty((2 * nb, n), dtype=np.float64)
+                        host_w = np.array(wd.data)
+                        wd.accel_used(True)             # the download changed nothing: the device copy is still current
+                        for b, det in enumerate(part):
+                            qw, uw = host_w[wd.indices([det])[0]].T[comp_q:comp_q + 2]
+                            if "QU" in self.mode:
+                                # remove polarization efficiency from the Q/U weights
+                                qw = qw * (1 / np.sqrt(qw**2 + uw**2))
+                            factors[b], factors[nb + b] = half_angle_factors(qw)
+                        s.inp("demod_2f_factors", factors)
+                    for flavor in flavors:
+                        dd, out = obs.detdata[flavor], demod_obs.detdata[flavor]
+                        d_in = accel_device_ptr(dd.buffer)
+                        rows = list(range(nb))
+                        if "QU" in self.mode:
+                            dev.demod_fir(n, bandpass4f.bpf, 1, 0, d_in, dd.buffer.shape[0], n, dd.indices(part), scratch,
+                                          nb, n, rows)
+                            fir(rows + rows, scratch, nb, lowpass.lpf, self.nskip, offset, out,
+                                [f"demod4r_{d}" for d in part] + [f"demod4i_{d}" for d in part],
+                                mod_mode=capi.DEMOD_MOD_WEIGHTS, d_mod=accel_device_ptr(wd.buffer),
+                                n_mod_rows=wd.buffer.shape[0], mod_stride=n * nnz, mod_row=wrows + wrows,
+                                mod_comp=[comp_q] * nb + [comp_q + 1] * nb, nnz=nnz, comp_q=comp_q)
+                        if self.do_2f:
+                            dev.demod_fir(n, bandpass2f.bpf, 1, 0, d_in, dd.buffer.shape[0], n, dd.indices(part), scratch,
+                                          nb, n, rows)
+                            fir(rows + rows, scratch, nb, lowpass.lpf, self.nskip, offset, out,
+                                [f"demod2r_{d}" for d in part] + [f"demod2i_{d}" for d in part],
+                                mod_mode=capi.DEMOD_MOD_ARRAY, d_mod=s.ptr("demod_2f_factors"), n_mod_rows=2 * nb,
+                                mod_stride=n, mod_row=list(range(2 * nb)))
+                finally:
+                    capi.synchronize()
+                    capi.device_free(scratch)
 
     # ------------------------------------------------------------------------------------------------ noise
     def _demodulate_noise(self, obs, demod_obs, dets, fsample, hwp_rate, lowpass, bandpass2f, bandpass4f):

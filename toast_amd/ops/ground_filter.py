@@ -19,12 +19,10 @@ from ..accel import (
     Resident,
     accel_data_create,
     accel_data_delete,
-    accel_data_update_device,
-    accel_data_update_host,
     accel_device_ptr,
     accel_enabled,
+    device_scratch,
     make_resident,
-    native,
 )
 from ..data import defaults
 from ..traits import Bool, Float, Int, Unicode
@@ -113,55 +111,52 @@ class GroundFilter(Operator):
         if nt == 0:
             raise RuntimeError("GroundFilter: no templates requested")
         templates = np.empty((nt, n), dtype=np.float64)
-        scratch = {"x": x, "phase": phase}
-        direction = None
-        if self.split_template:
-            direction = np.zeros(n, dtype=np.int32)
-            for ival in obs.intervals[self.leftright_interval]:
-                direction[ival.first:ival.last] = 1
-            for ival in obs.intervals[self.rightleft_interval]:
-                direction[ival.first:ival.last] = 2
-            scratch["direction"] = direction
-            scratch["row"] = np.empty(max(n_poly, 1) * n, dtype=np.float64)
-        if ibin is not None:
-            scratch["ibin"] = ibin
-        name = f"{self.name}_templates"
-        accel_data_create(templates, name, owner=self)
-        for key, arr in scratch.items():
-            accel_data_create(arr, f"{self.name}_{key}", owner=self)
-            if key != "row":
-                accel_data_update_device(arr, f"{self.name}_{key}")
-        t_ptr = accel_device_ptr(templates)
-        row_ptr = lambda r: t_ptr + 8 * n * r  # noqa: E731
-        if n_trend > 0:
-            # the offset is not part of the trend: it belongs to the ground template
-            D.legendre_templates(accel_device_ptr(x), n, 1, n_trend + 1, row_ptr(0))
-        cursor = n_trend
-        if n_poly > 0:
-            if not self.split_template:
-                D.legendre_templates(accel_device_ptr(phase), n, 0, n_poly, row_ptr(cursor))
-                cursor += n_poly
-            else:
-                tmp = accel_device_ptr(scratch["row"])
-                D.legendre_templates(accel_device_ptr(phase), n, 0, n_poly, tmp)
-                for r in range(n_poly):
-                    for value in (1, 2):  # without the left-right samples, without the right-left ones
-                        D.template_select(tmp + 8 * n * r, accel_device_ptr(direction), value, False, n, row_ptr(cursor))
+        accel_data_create(templates, f"{self.name}_templates", owner=self)
+        try:
+            with device_scratch(self.name, owner=self) as s:
+                s.inp("x", x)
+                s.inp("phase", phase)
+                if self.split_template:
+                    direction = np.zeros(n, dtype=np.int32)
+                    for ival in obs.intervals[self.leftright_interval]:
+                        direction[ival.first:ival.last] = 1
+                    for ival in obs.intervals[self.rightleft_interval]:
+                        direction[ival.first:ival.last] = 2
+                    s.inp("direction", direction)
+                    s.work("row", np.empty(max(n_poly, 1) * n, dtype=np.float64))
+                if ibin is not None:
+                    s.inp("ibin", ibin)
+                t_ptr = accel_device_ptr(templates)
+                row_ptr = lambda r: t_ptr + 8 * n * r  # noqa: E731
+                if n_trend > 0:
+                    # the offset is not part of the trend: it belongs to the ground template
+                    D.legendre_templates(s.ptr("x"), n, 1, n_trend + 1, row_ptr(0))
+                cursor = n_trend
+                if n_poly > 0:
+                    if not self.split_template:
+                        D.legendre_templates(s.ptr("phase"), n, 0, n_poly, row_ptr(cursor))
+                        cursor += n_poly
+                    else:
+                        tmp = s.ptr("row")
+                        D.legendre_templates(s.ptr("phase"), n, 0, n_poly, tmp)
+                        for r in range(n_poly):
+                            for value in (1, 2):  # without the left-right samples, without the right-left ones
+                                D.template_select(tmp + 8 * n * r, s.ptr("direction"), value, False, n, row_ptr(cursor))
+                                cursor += 1
+                for b in bins:
+                    if not self.split_template:
+                        D.template_select(0, s.ptr("ibin"), int(b), True, n, row_ptr(cursor))
                         cursor += 1
-        for b in bins:
-            if not self.split_template:
-                D.template_select(0, accel_device_ptr(ibin), int(b), True, n, row_ptr(cursor))
-                cursor += 1
-            else:
-                tmp = accel_device_ptr(scratch["row"])
-                D.template_select(0, accel_device_ptr(ibin), int(b), True, n, tmp)
-                for value in (1, 2):
-                    D.template_select(tmp, accel_device_ptr(direction), value, False, n, row_ptr(cursor))
-                    cursor += 1
-        assert cursor == nt
-        native().accel_synchronize()
-        for key, arr in scratch.items():
-            accel_data_delete(arr, f"{self.name}_{key}")
+                    else:
+                        tmp = s.ptr("row")
+                        D.template_select(0, s.ptr("ibin"), int(b), True, n, tmp)
+                        for value in (1, 2):
+                            D.template_select(tmp, s.ptr("direction"), value, False, n, row_ptr(cursor))
+                            cursor += 1
+                assert cursor == nt
+        except BaseException:
+            accel_data_delete(templates, f"{self.name}_templates")
+            raise
         return templates
 
     # ------------------------------------------------------------------ fit (host, tiny systems)
@@ -203,54 +198,47 @@ class GroundFilter(Operator):
                 continue
             n = obs.n_local_samples
             templates = self.build_templates(obs)
-            nt = templates.shape[0]
-            dd = obs.detdata[self.det_data]
-            signal = Resident(dd, self.det_data)
-            f_ptr, f_idx, fd = 0, None, None
-            if self.det_flags is not None:
-                fd = make_resident(obs.detdata[self.det_flags], self.det_flags)
-                f_ptr, f_idx = accel_device_ptr(fd.buffer), fd.indices(dets)
-            s_ptr = 0
-            common_good = np.ones(n, dtype=bool)
-            if self.shared_flags is not None:
-                sf = make_resident(obs.shared[self.shared_flags], self.shared_flags)
-                s_ptr = accel_device_ptr(sf.data)
-                common_good = (sf.data & self.shared_flag_mask) == 0
-            n_det = len(dets)
-            proj = np.zeros((n_det, nt))
-            gram_common = np.zeros((nt, nt))
-            gram_flagged = np.zeros((n_det, nt, nt))
-            n_flagged = np.zeros(n_det, dtype=np.int64)
-            outs = {"proj": proj, "gram": gram_common, "dgram": gram_flagged, "nflag": n_flagged}
-            for key, arr in outs.items():
-                accel_data_create(arr, f"{self.name}_{key}", owner=self)
-            D.template_fit(accel_device_ptr(templates), nt, n, dd.indices(dets), accel_device_ptr(dd.buffer), f_idx, f_ptr,
-                           self.det_flag_mask, s_ptr, self.shared_flag_mask, accel_device_ptr(proj),
-                           accel_device_ptr(gram_common), accel_device_ptr(gram_flagged), accel_device_ptr(n_flagged))
-            native().accel_synchronize()
-            for key, arr in outs.items():
-                accel_data_update_host(arr, f"{self.name}_{key}")
-                accel_data_delete(arr, f"{self.name}_{key}")
-            # good samples per detector: the commonly good ones minus those only this detector flags
-            n_good = int(np.count_nonzero(common_good)) - n_flagged
-            coeff, ok = self.solve(proj, gram_common, gram_flagged, n_good)
-            for i, det in enumerate(dets):
-                if not ok[i]:
-                    # all samples flagged: mark the detector (groundfilter.py:474-480)
-                    cur = obs.local_detector_flags.get(det, 0)
-                    obs.update_local_detector_flags({det: cur | self.ground_flag_mask})
-            fit_dets = [det for i, det in enumerate(dets) if ok[i]]
-            if len(fit_dets) > 0:
-                offset = 0 if self.detrend else (self.trend_order or 0)
-                cf = np.ascontiguousarray(coeff[ok])
-                accel_data_create(cf, f"{self.name}_coeff", owner=self)
-                accel_data_update_device(cf, f"{self.name}_coeff")
-                D.template_subtract(accel_device_ptr(templates), nt, offset, n, dd.indices(fit_dets),
-                                    accel_device_ptr(dd.buffer), accel_device_ptr(cf))
-                native().accel_synchronize()
-                accel_data_delete(cf, f"{self.name}_coeff")
-            self.coefficients = {det: coeff[i] for i, det in enumerate(dets) if ok[i]}
-            accel_data_delete(templates, f"{self.name}_templates")
+            try:
+                nt = templates.shape[0]
+                dd = obs.detdata[self.det_data]
+                signal = Resident(dd, self.det_data)
+                f_ptr, f_idx, fd = 0, None, None
+                if self.det_flags is not None:
+                    fd = make_resident(obs.detdata[self.det_flags], self.det_flags)
+                    f_ptr, f_idx = accel_device_ptr(fd.buffer), fd.indices(dets)
+                s_ptr = 0
+                common_good = np.ones(n, dtype=bool)
+                if self.shared_flags is not None:
+                    sf = make_resident(obs.shared[self.shared_flags], self.shared_flags)
+                    s_ptr = accel_device_ptr(sf.data)
+                    common_good = (sf.data & self.shared_flag_mask) == 0
+                n_det = len(dets)
+                with device_scratch(self.name, owner=self) as s:
+                    proj = s.out("proj", np.zeros((n_det, nt)))
+                    gram_common = s.out("gram", np.zeros((nt, nt)))
+                    gram_flagged = s.out("dgram", np.zeros((n_det, nt, nt)))
+                    n_flagged = s.out("nflag", np.zeros(n_det, dtype=np.int64))
+                    D.template_fit(accel_device_ptr(templates), nt, n, dd.indices(dets), accel_device_ptr(dd.buffer), f_idx,
+                                   f_ptr, self.det_flag_mask, s_ptr, self.shared_flag_mask, s.ptr("proj"), s.ptr("gram"),
+                                   s.ptr("dgram"), s.ptr("nflag"))
+                # good samples per detector: the commonly good ones minus those only this detector flags
+                n_good = int(np.count_nonzero(common_good)) - n_flagged
+                coeff, ok = self.solve(proj, gram_common, gram_flagged, n_good)
+                for i, det in enumerate(dets):
+                    if not ok[i]:
+                        # all samples flagged: mark the detector (groundfilter.py:474-480)
+                        cur = obs.local_detector_flags.get(det, 0)
+                        obs.update_local_detector_flags({det: cur | self.ground_flag_mask})
+                fit_dets = [det for i, det in enumerate(dets) if ok[i]]
+                if len(fit_dets) > 0:
+                    offset = 0 if self.detrend else (self.trend_order or 0)
+                    with device_scratch(self.name, owner=self) as s:
+                        s.inp("coeff", np.ascontiguousarray(coeff[ok]))
+                        D.template_subtract(accel_device_ptr(templates), nt, offset, n, dd.indices(fit_dets),
+                                            accel_device_ptr(dd.buffer), s.ptr("coeff"))
+                self.coefficients = {det: coeff[i] for i, det in enumerate(dets) if ok[i]}
+            finally:
+                accel_data_delete(templates, f"{self.name}_templates")
             signal.write_back_unless_lazy(data)
         comm = data.comm
         if comm.comm_world is not None:

@@ -460,21 +460,15 @@ class PixelsHealpix(Operator):
         """pointing_detector + pixels_healpix in one kernel, no quaternion buffer.  ``hit_submaps``
         is the host in/out array of the reference interface: staged through the memory manager."""
         from .. import capi
-        from ..accel import (accel_data_create, accel_data_delete, accel_data_update_device, accel_data_update_host,
-                             accel_device_ptr)
+        from ..accel import accel_device_ptr, device_scratch
 
         pt = otf_descriptor(ob, dets, self, None)
         pd = ob.detdata[self.pixels]
-        hs = np.ascontiguousarray(hit_submaps)
-        accel_data_create(hs, "hit_submaps")
-        try:
-            accel_data_update_device(hs, "hit_submaps")
+        with device_scratch() as s:
+            hs = s.inout("hit_submaps", np.ascontiguousarray(hit_submaps))
             capi.dev.otf_pixels_healpix(pt, pd.indices(dets), accel_device_ptr(pd.buffer), ob.n_local_samples,
-                                        ob.intervals[view].data, accel_device_ptr(hs), self._n_submap,
+                                        ob.intervals[view].data, s.ptr("hit_submaps"), self._n_submap,
                                         self._n_pix_submap)
-            accel_data_update_host(hs, "hit_submaps")
-        finally:
-            accel_data_delete(hs, "hit_submaps")
         if hs is not hit_submaps:
             hit_submaps[:] = hs
         pd.accel_used(True)

@@ -33,12 +33,9 @@ import numpy as np
 
 from ..accel import (
     Resident,
-    accel_data_create,
-    accel_data_delete,
-    accel_data_update_device,
-    accel_data_update_host,
     accel_device_ptr,
     accel_enabled,
+    device_scratch,
     make_resident,
     native,
 )
@@ -163,17 +160,12 @@ class PolyFilter(Operator):
             status = np.zeros((len(dets), starts.size), dtype=np.int32)
             if len(dets) > 0 and starts.size > 0 and self.order >= 0:
                 res = _Resident(obs, self.det_data, self.det_flags, self.shared_flags)
-                outs = {"coeff": coeff, "status": status}
-                for key, arr in outs.items():
-                    accel_data_create(arr, f"{self.name}_{key}", owner=self)
-                D.filter_polynomial(self.order, obs.n_local_samples, res.dd.indices(dets), res.sig_ptr,
-                                    res.flag_index(dets), res.flag_ptr, self.det_flag_mask, res.shared_ptr,
-                                    self.shared_flag_mask, starts, stops, accel_device_ptr(coeff),
-                                    accel_device_ptr(status))
-                native().accel_synchronize()
-                for key, arr in outs.items():
-                    accel_data_update_host(arr, f"{self.name}_{key}")
-                    accel_data_delete(arr, f"{self.name}_{key}")
+                with device_scratch(self.name, owner=self) as s:
+                    s.out("coeff", coeff)
+                    s.out("status", status)
+                    D.filter_polynomial(self.order, obs.n_local_samples, res.dd.indices(dets), res.sig_ptr,
+                                        res.flag_index(dets), res.flag_ptr, self.det_flag_mask, res.shared_ptr,
+                                        self.shared_flag_mask, starts, stops, s.ptr("coeff"), s.ptr("status"))
                 res.release(data)
             self.coefficients[obs.name] = coeff
             self.status[obs.name] = status
@@ -385,15 +377,11 @@ class PolyFilter2D(Operator):
     def _device(self, obs, data, D, dets, det_group, n_group, templates, starts, stops):
         res = _Resident(obs, self.det_data, self.det_flags, self.shared_flags)
         n = obs.n_local_samples
-        coeff = np.zeros((n, n_group, templates.shape[1]))
-        accel_data_create(coeff, f"{self.name}_coeff", owner=self)
-        accel_data_update_device(coeff, f"{self.name}_coeff")
-        D.filter_poly2d(self.order, n, res.dd.indices(dets), res.sig_ptr, res.flag_index(dets), res.flag_ptr,
-                        self.det_flag_mask, res.shared_ptr, self.shared_flag_mask, self.poly_flag_mask, det_group, n_group,
-                        templates, starts, stops, d_coeff=accel_device_ptr(coeff))
-        native().accel_synchronize()
-        accel_data_update_host(coeff, f"{self.name}_coeff")
-        accel_data_delete(coeff, f"{self.name}_coeff")
+        with device_scratch(self.name, owner=self) as s:
+            coeff = s.inout("coeff", np.zeros((n, n_group, templates.shape[1])))
+            D.filter_poly2d(self.order, n, res.dd.indices(dets), res.sig_ptr, res.flag_index(dets), res.flag_ptr,
+                            self.det_flag_mask, res.shared_ptr, self.shared_flag_mask, self.poly_flag_mask, det_group,
+                            n_group, templates, starts, stops, d_coeff=s.ptr("coeff"))
         # the flags changed on the device copy, which is the current one: the host follows lazily through ``.data``
         res.release(data)
         return coeff
@@ -532,61 +520,41 @@ class CommonModeFilter(Operator):
                 # templates [1, sum -> mean] and the hit counts; the sum is row 1
                 templates = np.zeros((2, n))
                 templates[0] = 1.0
-                hits = np.zeros(n, dtype=np.int64)
-                work = {"templates": templates, "hits": hits}
-                for key, arr in work.items():
-                    accel_data_create(arr, f"{self.name}_{key}", owner=self)
-                    accel_data_update_device(arr, f"{self.name}_{key}")
-                t_ptr, h_ptr = accel_device_ptr(templates), accel_device_ptr(hits)
-                sum_ptr = t_ptr + 8 * n
-                D.sum_detectors(n, sidx, res.sig_ptr, fidx, res.flag_ptr, self.det_flag_mask, res.shared_ptr,
-                                self.shared_flag_mask, sum_ptr, h_ptr)
-                self._regress(obs, D, res, local_dets, sidx, fidx, templates, hits, value)
-                native().accel_synchronize()
-                for key, arr in work.items():
-                    accel_data_delete(arr, f"{self.name}_{key}")
+                with device_scratch(self.name, owner=self) as s:
+                    s.inp("templates", templates)
+                    s.inp("hits", np.zeros(n, dtype=np.int64))
+                    D.sum_detectors(n, sidx, res.sig_ptr, fidx, res.flag_ptr, self.det_flag_mask, res.shared_ptr,
+                                    self.shared_flag_mask, s.ptr("templates") + 8 * n, s.ptr("hits"))
+                    self._regress(obs, D, res, local_dets, sidx, fidx, s, n, value)
             if res is not None:
                 native().accel_synchronize()
                 res.release(data)
 
-    def _regress(self, obs, D, res, local_dets, sidx, fidx, templates, hits, value):
+    def _regress(self, obs, D, res, local_dets, sidx, fidx, s, n, value):
         """polyfilter.py:943-970 with the GroundFilter regression kernels: the "shared flags" of the fit are
-        ``hits == 0``, the detector flags zero the signal in the projection only, the subtraction covers all samples."""
-        n = hits.size
-        native().accel_synchronize()
-        accel_data_update_host(hits, f"{self.name}_hits")
-        nohit = (hits == 0).astype(np.uint8)
-        D.subtract_mean(n, np.zeros(0, dtype=np.int32), res.sig_ptr, accel_device_ptr(templates) + 8 * n,
-                        accel_device_ptr(hits))       # no rows: only sum -> mean where hits != 0 (toast_hip.h)
+        ``hits == 0``, the detector flags zero the signal in the projection only, the subtraction covers all samples.
+        ``s``: the caller's device scratch with ``templates`` (row 1: the sum) and ``hits``; it releases what is added."""
+        nohit = (s.fetch("hits") == 0).astype(np.uint8)
+        D.subtract_mean(n, np.zeros(0, dtype=np.int32), res.sig_ptr, s.ptr("templates") + 8 * n,
+                        s.ptr("hits"))       # no rows: only sum -> mean where hits != 0 (toast_hip.h)
         n_det = len(local_dets)
-        proj = np.zeros((n_det, 2))
-        gram = np.zeros((2, 2))
-        dgram = np.zeros((n_det, 2, 2))
-        nflag = np.zeros(n_det, dtype=np.int64)
-        outs = {"nohit": nohit, "proj": proj, "gram": gram, "dgram": dgram, "nflag": nflag}
-        for key, arr in outs.items():
-            accel_data_create(arr, f"{self.name}_{key}", owner=self)
-        accel_data_update_device(nohit, f"{self.name}_nohit")
-        D.template_fit(accel_device_ptr(templates), 2, n, sidx, res.sig_ptr, fidx, res.flag_ptr, self.det_flag_mask,
-                       accel_device_ptr(nohit), 1, accel_device_ptr(proj), accel_device_ptr(gram), accel_device_ptr(dgram),
-                       accel_device_ptr(nflag))
-        native().accel_synchronize()
-        for key in ("proj", "gram"):
-            accel_data_update_host(outs[key], f"{self.name}_{key}")
-        coeff = regress_coefficients(proj, gram)
+        s.inp("nohit", nohit)
+        # (the host reads the projection and the common Gram matrix here, and nothing else of the fit)
+        s.work("proj", np.zeros((n_det, 2)))
+        s.work("gram", np.zeros((2, 2)))
+        s.work("dgram", np.zeros((n_det, 2, 2)))
+        s.work("nflag", np.zeros(n_det, dtype=np.int64))
+        D.template_fit(s.ptr("templates"), 2, n, sidx, res.sig_ptr, fidx, res.flag_ptr, self.det_flag_mask, s.ptr("nohit"), 1,
+                       s.ptr("proj"), s.ptr("gram"), s.ptr("dgram"), s.ptr("nflag"))
+        coeff = regress_coefficients(s.fetch("proj"), s.fetch("gram"))
         if coeff is None:
             # matrix is singular, flag these dets (polyfilter.py:965-970)
             for det in local_dets:
                 obs.update_local_detector_flags({det: defaults.det_mask_invalid})
         else:
-            accel_data_create(coeff, f"{self.name}_coeff", owner=self)
-            accel_data_update_device(coeff, f"{self.name}_coeff")
-            D.template_subtract(accel_device_ptr(templates), 2, 0, n, sidx, res.sig_ptr, accel_device_ptr(coeff))
-            native().accel_synchronize()
-            accel_data_delete(coeff, f"{self.name}_coeff")
+            s.inp("coeff", coeff)
+            D.template_subtract(s.ptr("templates"), 2, 0, n, sidx, res.sig_ptr, s.ptr("coeff"))
             self.coefficients[(obs.name, value)] = {det: coeff[i] for i, det in enumerate(local_dets)}
-        for key, arr in outs.items():
-            accel_data_delete(arr, f"{self.name}_{key}")
 
     def _finalize(self, data, **kwargs):
         return

@@ -15,6 +15,7 @@ import numpy as np
 
 from ..accel import (
     AcceleratorObject,
+    DeviceMirror,
     accel_data_create,
     accel_data_delete,
     accel_data_present,
@@ -22,6 +23,7 @@ from ..accel import (
     accel_data_update_device,
     accel_data_update_host,
     accel_device_ptr,
+    device_scratch,
     make_resident,
     native,
     release_borrowed,
@@ -377,53 +379,6 @@ class AmplitudesMap(dict):
                 v.accel_delete()
 
 
-class DeviceMirror:
-    """A host array that a template derives at set-up, its device copy under one registration name, and which side is
-    current: host only, both, or device newer (then the first ``host`` access fetches the values, once)."""
-
-    def __init__(self, buffer, name):
-        self.buffer = buffer        # the host array WITHOUT synchronisation: the accelerator key
-        self.name = name
-        self.on_device = False      # registered on the device?
-        self.stale = False          # device newer than host?
-
-    def create(self, zero_out=False):
-        """Register without an upload, as the side that kernels write; ``written()`` once they were launched."""
-        accel_data_create(self.buffer, self.name, zero_out=zero_out, owner=self)
-        self.on_device = True
-        return self
-
-    def upload(self):
-        """Make sure the host values are on the device (copied once; the host array does not change afterwards)."""
-        if not self.on_device:
-            self.create()
-            accel_data_update_device(self.buffer, self.name)
-        return self
-
-    @property
-    def ptr(self):
-        return accel_device_ptr(self.buffer)
-
-    def written(self):
-        self.stale = True
-
-    @property
-    def host(self):
-        """The host array, brought up to date first."""
-        if self.stale:
-            self.stale = False
-            accel_data_update_host(self.buffer, self.name)
-        return self.buffer
-
-    def drop(self, fetch=True):
-        """Release the device copy; ``fetch``: somebody may still read the values on the host."""
-        if self.on_device:
-            if fetch:
-                _ = self.host
-            accel_data_delete(self.buffer, self.name)
-        self.on_device = self.stale = False
-
-
 class Template(TraitConfig):
     """Base class of timestream templates (templates/template.py), and what the templates of this package share: the
     selection of detectors, the detector-major amplitude layout, residency of what a sweep reads, and the device mirrors
@@ -710,45 +665,42 @@ class Offset(Template):
         capi.dev.memset(bad_ptr, 0, bad_bytes)
         # an amplitude that no (detector, observation) block claims stays cut, like a baseline without samples
         self._amp_flags[:] = 1
-        flag_name = f"{self.name}_init_flags"
-        accel_data_create(self._amp_flags, flag_name)
-        accel_data_update_device(self._amp_flags, flag_name)
         # (the variances stay on the device under the name the preconditioner looks for; host copy on demand)
-        var = self._mirrors["offsetvar"].create(zero_out=True)
+        var = self._mirrors["offsetvar"]
         try:
-            for iob, ob in enumerate(new_data.obs):
-                dets = [d for d in self._all_dets if d in self._obs_dets[iob]]
-                if len(dets) == 0:
-                    continue
-                step_length = self._step_length(self.step_time, self._obs_rate[iob])
-                # lengths of the baselines of one detector of this observation, view after view
-                lens = []
-                for ivw, vw in enumerate(ob.intervals[self._bounds_view]):
-                    n_amp_view = int(self._obs_views[iob][ivw])
-                    if n_amp_view == 0:
+            with device_scratch(self.name) as s:
+                s.inout("init_flags", self._amp_flags)
+                var.create(zero_out=True)
+                for iob, ob in enumerate(new_data.obs):
+                    dets = [d for d in self._all_dets if d in self._obs_dets[iob]]
+                    if len(dets) == 0:
                         continue
-                    a = np.full(n_amp_view, step_length, dtype=np.int64)
-                    a[-1] = (vw.last - vw.first) - (n_amp_view - 1) * step_length
-                    lens.append(a)
-                lens = np.concatenate(lens) if lens else np.zeros(0, dtype=np.int64)
-                offs = self.det_amp_offsets(iob, dets)
-                w = np.ones(len(dets), dtype=np.float64)
-                if self.noise_model is not None:
-                    w = np.array([ob[self.noise_model].detector_weight(d) for d in dets], dtype=np.float64)
-                if self.det_flags is not None:
-                    f_idx, f_ptr = self._det_flag_args(ob, dets)
-                    capi.dev.offset_count_flagged(step_length, offs, self._obs_views[iob], bad_ptr, f_idx, f_ptr,
-                                                  self.det_flag_mask, ob.n_local_samples,
-                                                  ob.intervals[self._bounds_view].data)
-                capi.dev.offset_variance(offs, w, lens, bad_ptr, self.good_fraction,
-                                         accel_device_ptr(self._amp_flags), var.ptr)
-            accel_data_update_host(self._amp_flags, flag_name)
-            var.written()
+                    step_length = self._step_length(self.step_time, self._obs_rate[iob])
+                    # lengths of the baselines of one detector of this observation, view after view
+                    lens = []
+                    for ivw, vw in enumerate(ob.intervals[self._bounds_view]):
+                        n_amp_view = int(self._obs_views[iob][ivw])
+                        if n_amp_view == 0:
+                            continue
+                        a = np.full(n_amp_view, step_length, dtype=np.int64)
+                        a[-1] = (vw.last - vw.first) - (n_amp_view - 1) * step_length
+                        lens.append(a)
+                    lens = np.concatenate(lens) if lens else np.zeros(0, dtype=np.int64)
+                    offs = self.det_amp_offsets(iob, dets)
+                    w = np.ones(len(dets), dtype=np.float64)
+                    if self.noise_model is not None:
+                        w = np.array([ob[self.noise_model].detector_weight(d) for d in dets], dtype=np.float64)
+                    if self.det_flags is not None:
+                        f_idx, f_ptr = self._det_flag_args(ob, dets)
+                        capi.dev.offset_count_flagged(step_length, offs, self._obs_views[iob], bad_ptr, f_idx, f_ptr,
+                                                      self.det_flag_mask, ob.n_local_samples,
+                                                      ob.intervals[self._bounds_view].data)
+                    capi.dev.offset_variance(offs, w, lens, bad_ptr, self.good_fraction, s.ptr("init_flags"), var.ptr)
+                var.written()
         except BaseException:
             var.drop(fetch=False)
             raise
         finally:
-            accel_data_delete(self._amp_flags, flag_name)
             capi.device_release(bad_ptr, bad_bytes)
 
     def _init_variances_host(self, new_data):

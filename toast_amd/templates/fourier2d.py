@@ -25,7 +25,7 @@ observation and the view.  Amplitudes shared between the processes of a detector
 import numpy as np
 import scipy.signal
 
-from ..accel import accel_data_create, accel_data_delete, accel_data_update_device, accel_device_ptr, native
+from ..accel import accel_device_ptr, device_scratch
 from ..data import defaults, detector_direction
 from ..traits import Bool, Float, Int, Unicode
 from . import Amplitudes, DeviceMirror, Template, release_borrowed
@@ -226,17 +226,14 @@ class Fourier2D(Template):
             weights = self._det_weights(ob, dets)
             w2 = np.ascontiguousarray([self._templates[iob][d] ** 2 * w for d, w in zip(dets, weights)], dtype=np.float64)
             borrowed = []
-            w2_name = f"{self.name}_w2"
-            accel_data_create(w2, w2_name)
             try:
-                accel_data_update_device(w2, w2_name)
-                f_idx, f_ptr = self._det_flag_args(ob, dets, borrowed)
-                capi.dev.fourier2d_norms(nmode, accel_device_ptr(w2), self._obs_view_offset[iob], f_idx, f_ptr,
-                                         self.det_flag_mask, len(dets), ob.n_local_samples, ob.intervals[self.view].data,
-                                         norms.ptr)
-                native().accel_synchronize()      # (w2 is released below)
+                with device_scratch(self.name) as s:
+                    s.inp("w2", w2)
+                    f_idx, f_ptr = self._det_flag_args(ob, dets, borrowed)
+                    capi.dev.fourier2d_norms(nmode, s.ptr("w2"), self._obs_view_offset[iob], f_idx, f_ptr,
+                                             self.det_flag_mask, len(dets), ob.n_local_samples,
+                                             ob.intervals[self.view].data, norms.ptr)
             finally:
-                accel_data_delete(w2, w2_name)
                 release_borrowed(borrowed)
         norms.written()
 
@@ -258,12 +255,9 @@ class Fourier2D(Template):
     def _device_table(self, key, build):
         """A small table registered on the device once per template, released by ``clear()``."""
         if key not in self._dev_tables:
-            arr = np.ascontiguousarray(build(), dtype=np.float64)
-            name = f"{self.name}_table{len(self._dev_tables)}"
-            accel_data_create(arr, name, owner=self)
-            accel_data_update_device(arr, name)
-            self._dev_tables[key] = (arr, name)
-        return accel_device_ptr(self._dev_tables[key][0])
+            self._dev_tables[key] = DeviceMirror(np.ascontiguousarray(build(), dtype=np.float64),
+                                                 f"{self.name}_table{len(self._dev_tables)}")
+        return self._dev_tables[key].upload().ptr
 
     def _template_table(self, iob, dets):
         return self._device_table(("T", iob, tuple(dets)), lambda: [self._templates[iob][d] for d in dets])
@@ -351,7 +345,7 @@ class Fourier2D(Template):
         d_in, d_out = accel_device_ptr(amplitudes_in.buffer), accel_device_ptr(amplitudes_out.buffer)
         for first, view_len, taps, n_fft, key in self._prior_plan():
             capi.dev.fourier2d_add_prior(nmode, view_len, d_in + 8 * first, d_out + 8 * first, taps, n_fft,
-                                         accel_device_ptr(self._dev_tables[key][0]), self._filter_scale, self._work[0])
+                                         self._dev_tables[key].ptr, self._filter_scale, self._work[0])
 
     def _add_prior(self, amplitudes_in, amplitudes_out, use_accel=None, **kwargs):
         from ..accel import accel_enabled
@@ -391,7 +385,7 @@ class Fourier2D(Template):
 
     def device_tables(self):
         """The host keys of everything this template has registered on the device (tests / inspection)."""
-        keys = [arr for arr, _ in self._dev_tables.values()]
+        keys = [m.buffer for m in self._dev_tables.values()]
         return keys + [m.buffer for m in self._mirrors.values() if m.on_device]
 
     def clear(self):
@@ -399,8 +393,8 @@ class Fourier2D(Template):
         from .. import capi
 
         super().clear()          # (fetches first: somebody may still read the norms on the host)
-        for arr, name in self._dev_tables.values():
-            accel_data_delete(arr, name)
+        for mirror in self._dev_tables.values():
+            mirror.drop(fetch=False)
         self._dev_tables = {}
         ptr, nbytes = self._work
         if ptr:

@@ -13,7 +13,7 @@ import numpy as np
 import scipy.linalg
 import scipy.optimize
 
-from ..accel import accel_data_create, accel_data_delete, accel_data_update_device, accel_device_ptr
+from ..accel import DeviceMirror, accel_device_ptr
 
 _LOW_FREQ = 1.0e-10  # offset.py:549: |f| below this is treated as this frequency
 
@@ -169,16 +169,16 @@ class OffsetPrior:
                     raise RuntimeError(f"{self.name}: banded preconditioner is not positive definite at width {width}")
 
     # ------------------------------------------------------------------ device tables
-    def _register(self, key, arr):
+    def _table(self, key, arr):
+        """The mirror of one table, not yet on the device: ``upload()`` it, or ``create()`` it for kernels to fill."""
         arr = np.ascontiguousarray(arr)
         if arr.size == 0:
             arr = np.zeros(1, dtype=arr.dtype)
-        self._tables[key] = arr
-        accel_data_create(arr, f"{self.name}_prior_{key}", owner=self)
-        accel_data_update_device(arr, f"{self.name}_prior_{key}")
+        self._tables[key] = DeviceMirror(arr, f"{self.name}_prior_{key}")
+        return self._tables[key]
 
     def _ptr(self, key):
-        return accel_device_ptr(self._tables[key])
+        return self._tables[key].ptr
 
     @property
     def _max_seg(self):
@@ -188,7 +188,7 @@ class OffsetPrior:
         if self._on_device:
             return
         n_seg = self.seg_start.size - 1
-        self._register("seg_start", self.seg_start)
+        self._table("seg_start", self.seg_start).upload()
 
         def pack(rows):
             start = np.zeros(n_seg, dtype=np.int64)
@@ -205,14 +205,14 @@ class OffsetPrior:
             return start, length, np.concatenate(pool) if pool else np.zeros(1)
 
         fs, fl, fp = pack(self.filters)
-        self._register("filt_start", fs)
-        self._register("filt_len", fl)
-        self._register("filters", fp)
+        self._table("filt_start", fs).upload()
+        self._table("filt_len", fl).upload()
+        self._table("filters", fp).upload()
         if self.precond_width <= 1:
             ps, pl, pp = pack(self.precond)
-            self._register("pre_start", ps)
-            self._register("pre_len", pl)
-            self._register("pre_filters", pp)
+            self._table("pre_start", ps).upload()
+            self._table("pre_len", pl).upload()
+            self._table("pre_filters", pp).upload()
         elif self.factor_on_device:
             self._factor_on_device()
         else:
@@ -231,10 +231,10 @@ class OffsetPrior:
                     f[:n - k, k] = cb[k, :n - k]  # L[i + k][i]: unknown i feeds i + k going forward
                     b[k:, k] = cb[k, :n - k]      # L[i][i - k]: unknown i feeds i - k going backward
             self.max_width = int(width.max()) if n_seg else 1
-            self._register("band_width", width)
-            self._register("band_start", start)
-            self._register("forward", fwd)
-            self._register("backward", bwd)
+            self._table("band_width", width).upload()
+            self._table("band_start", start).upload()
+            self._table("forward", fwd).upload()
+            self._table("backward", bwd).upload()
         self._on_device = True
 
     def _band_layout(self, width):
@@ -244,30 +244,21 @@ class OffsetPrior:
             start[1:] = np.cumsum(n_amp[:-1] * width[:-1])
         return start, int(np.sum(n_amp * width))
 
-    def _create(self, key, arr):
-        """Device buffer keyed by ``arr`` without an upload (``arr`` is never touched)."""
-        self._tables[key] = arr
-        accel_data_create(arr, f"{self.name}_prior_{key}", owner=self)
-
-    def _drop(self, key):
-        accel_data_delete(self._tables.pop(key), f"{self.name}_prior_{key}")
-
     def _factor_on_device(self):
         """Banded Cholesky factors of all segments in one launch
         (toast_hip_template_offset_banded_cholesky_dev), widening the band of the segments that
         are not positive definite the way the reference does (offset.py:546-566)."""
         from .. import capi
-        from ..accel import accel_data_update_host, native
+        from ..accel import native
 
         n_seg = self.seg_start.size - 1
         n_amp = np.diff(self.seg_start)
         centre = np.array([f.size // 2 for f in self.filters], dtype=np.int64)
         try_width = np.full(n_seg, self.precond_width, dtype=np.int64)
         dscale = np.array([1.0 if d != 0 else 0.0 for d in self.detnoise], dtype=np.float64)
-        self._register("diag_scale", dscale)
-        self._register("offset_var", np.ascontiguousarray(self._offsetvar))
-        status = np.zeros(max(n_seg, 1), dtype=np.int32)
-        self._create("status", status)
+        self._table("diag_scale", dscale).upload()
+        self._table("offset_var", np.ascontiguousarray(self._offsetvar)).upload()
+        status = self._table("status", np.zeros(max(n_seg, 1), dtype=np.int32)).create()
         while True:
             wband = np.minimum(try_width, centre)
             width = np.maximum(wband, np.minimum(try_width, n_amp)).astype(np.int32)
@@ -287,18 +278,18 @@ class OffsetPrior:
             start, total = self._band_layout(width)
             for key, arr in (("toep_start", tstart), ("toep_len", wband.astype(np.int32)),
                              ("toeplitz", np.concatenate(pool)), ("band_width", width), ("band_start", start)):
-                self._register(key, arr)
+                self._table(key, arr).upload()
             # the factor tables exist on the device only; the host arrays are untouched keys
-            self._create("forward", np.empty(max(total, 1), dtype=np.float64))
-            self._create("backward", np.empty(max(total, 1), dtype=np.float64))
+            self._table("forward", np.empty(max(total, 1), dtype=np.float64)).create()
+            self._table("backward", np.empty(max(total, 1), dtype=np.float64)).create()
             capi.dev.memset(self._ptr("backward"), 0, 8 * max(total, 1))
             capi.dev.offset_banded_cholesky(n_seg, self._ptr("seg_start"), self._ptr("band_width"), int(width.max()),
                                             self._ptr("band_start"), self._ptr("toep_start"), self._ptr("toep_len"),
                                             self._ptr("toeplitz"), self._ptr("diag_scale"), self._ptr("offset_var"),
                                             self._ptr("forward"), self._ptr("backward"), self._ptr("status"))
             native().accel_synchronize()
-            accel_data_update_host(status, f"{self.name}_prior_status")
-            failed = np.nonzero(status[:n_seg])[0]
+            status.written()
+            failed = np.nonzero(status.host[:n_seg])[0]
             if failed.size == 0:
                 break
             for i in failed:
@@ -308,31 +299,29 @@ class OffsetPrior:
                     raise RuntimeError(f"{self.name}: banded preconditioner of segment {i} is not positive "
                                        f"definite at the maximum width {int(try_width[i])}")
             for key in ("toep_start", "toep_len", "toeplitz", "band_width", "band_start", "forward", "backward"):
-                self._drop(key)
+                self._tables.pop(key).drop(fetch=False)
         self.max_width = int(width.max())
         for key in ("toep_start", "toep_len", "toeplitz", "diag_scale", "offset_var", "status"):
-            self._drop(key)
+            self._tables.pop(key).drop(fetch=False)
 
     def banded_factor(self, iseg):
         """Lower banded factor of one segment in scipy's layout, read back from the device tables
         (tests / inspection)."""
-        from ..accel import accel_data_update_host
-
         if not self.factor_on_device:
             return self.precond[iseg]
         self.to_device()
-        fwd = self._tables["forward"]
-        accel_data_update_host(fwd, f"{self.name}_prior_forward")
-        w = int(self._tables["band_width"][iseg])
+        self._tables["forward"].written()      # (by the factorisation; the host array is an untouched key until now)
+        fwd = self._tables["forward"].host
+        w = int(self._tables["band_width"].buffer[iseg])
         n = int(self.seg_start[iseg + 1] - self.seg_start[iseg])
-        s0 = int(self._tables["band_start"][iseg])
+        s0 = int(self._tables["band_start"].buffer[iseg])
         cb = fwd[s0:s0 + n * w].reshape(n, w).T.copy()
         cb[0] = 1.0 / cb[0]
         return cb
 
     def clear(self):
-        for key, arr in self._tables.items():
-            accel_data_delete(arr, f"{self.name}_prior_{key}")
+        for mirror in self._tables.values():
+            mirror.drop(fetch=False)
         self._tables = {}
         self._on_device = False
 

@@ -18,7 +18,7 @@ A (detector, view) without a single good sample makes the reference fail inside 
 
 import numpy as np
 
-from ..accel import accel_data_create, accel_data_delete, accel_data_update_host, accel_device_ptr
+from ..accel import accel_device_ptr, device_scratch
 from ..data import defaults
 from ..traits import Int, Unicode
 from . import Amplitudes, DeviceMirror, Template, release_borrowed
@@ -137,20 +137,14 @@ class SubHarmonic(Template):
                 continue
             borrowed = []
             f_idx, f_ptr = self._det_flag_args(ob, dets, borrowed)
-            g = np.zeros((len(dets), n_view, norder, norder), dtype=np.float64)
-            n = np.zeros((len(dets), n_view), dtype=np.int64)
-            g_name, n_name = f"{self.name}_gram", f"{self.name}_ngood"
-            accel_data_create(g, g_name)
-            accel_data_create(n, n_name)
             try:
-                capi.dev.subharmonic_precond_build(norder, f_idx, f_ptr, self.det_flag_mask, self._det_weights(ob, dets),
-                                                   ob.n_local_samples, ob.intervals[self.view].data, accel_device_ptr(g),
-                                                   accel_device_ptr(n))
-                accel_data_update_host(g, g_name)
-                accel_data_update_host(n, n_name)
+                with device_scratch(self.name) as s:
+                    g = s.out("gram", np.zeros((len(dets), n_view, norder, norder), dtype=np.float64))
+                    n = s.out("ngood", np.zeros((len(dets), n_view), dtype=np.int64))
+                    capi.dev.subharmonic_precond_build(norder, f_idx, f_ptr, self.det_flag_mask, self._det_weights(ob, dets),
+                                                       ob.n_local_samples, ob.intervals[self.view].data, s.ptr("gram"),
+                                                       s.ptr("ngood"))
             finally:
-                accel_data_delete(g, g_name)
-                accel_data_delete(n, n_name)
                 release_borrowed(borrowed)
             for k, blk in enumerate(self._blocks(iob, dets)):
                 gram[blk:blk + n_view] = g[k]
