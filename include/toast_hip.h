@@ -1125,31 +1125,16 @@ int toast_hip_fft_extend_flags(uint8_t * flags, int64_t n_flag_rows, const int32
                                int64_t n_samp, uint8_t mask, const int32_t * extents, int edges,
                                const uint8_t * or_row, int use_accel);
 /* Points per thread (16 or 8; anything else = default) of the row pass, the forward and the inverse
- * column pass of the fused kernels: 16 = 256-thread workgroups with radix-16 stages, 8 = 512-thread
- * workgroups with radix-8 stages and twice the waves per SIMD.  Defaults 8 / 8 / 8; start-up value
- * from TOAST_HIP_FFT_POINTS="rows,cols_fwd,cols_inv". */
+ * column pass of the fused kernels that keep their tile in LDS: 16 = 256-thread workgroups with radix-16
+ * stages, 8 = 512-thread workgroups with radix-8 stages and twice the waves per SIMD.  Defaults 8 / 8 / 8;
+ * start-up value from TOAST_HIP_FFT_POINTS="rows,cols_fwd,cols_inv". */
 void toast_hip_fft_points(int rows, int cols_fwd, int cols_inv);
-/* Row pass of the fused kernels: 2 (default) = the tile in registers and the LDS only an exchange buffer, 16 points per
- * lane: a row of N2 = 2048 bins in two waves, the row pair (k1, N1 - k1) in one workgroup, three workgroups per CU
- * (csrc/fft_reg.hip); 3 = 32 points per lane, one row per wave, two workgroups per CU; 0 = both rows of a pair interleaved
- * in one 64 KB LDS tile; 1 = one row per 32 KB LDS tile (experiment: register bound, slower).  Start-up value from
- * TOAST_HIP_FFT_ROWS=reg|reg32|lds|split.  Same results to rounding. */
-void toast_hip_fft_rows_split(int split);
-/* Column passes of the fused kernels: 1 (default) = the tile in registers (csrc/fft_reg.hip) for n_fft 2^22 and 2^23
- * (N2 = 2048, even n_samp / padding: 128- and 64-byte pieces where the LDS tile gives 64 and 32), 2 = for n_fft 2^21 too,
- * 0 = the tile in LDS (k_fft_cols) at every length.  Start-up value from TOAST_HIP_FFT_COLS=reg|reg9|lds.  Same results
- * to rounding. */
-void toast_hip_fft_cols_reg(int on);
-/* Row length of the four-step factorisation M = N1 x N2 of the fused kernels: 2048 (64 KB row-pair tiles, two
- * workgroups per CU in the row pass, 128-byte pieces in the column passes) or 1024 (32 KB tiles, four workgroups per
- * CU, 64-byte pieces; only for M <= 2^20).  Start-up value from TOAST_HIP_FFT_N2.  Same results to rounding. */
-void toast_hip_fft_rows_n2(int n2);
 /* Host only, no device needed: the order in which the forward column pass of the fused kernels takes its n_tiles column
  * tiles (cols_per_tile complex columns each) so that the tiles reading the same 128-byte lines of the timestream -- directly
  * and as the two mirror images of the padded series, set_rfft_input, src/toast/fft.py:163-188 -- run on one XCD (workgroup
  * b runs on XCD b mod 8 and takes tile order[b]).  Returns n_tiles and fills order[0 .. n_tiles), or 0 when the geometry
  * (n_samp, n_buffer, n_reflect) does not split into classes that fill the 8 XCDs evenly: the pass then keeps contiguous
- * column ranges per XCD.  TOAST_HIP_FFT_XCD=0|1 switches it off. */
+ * column ranges per XCD. */
 int toast_hip_fft_mirror_tile_order(int64_t n_samp, int64_t n_buffer, int64_t n_reflect, int64_t n_tiles,
                                     int64_t cols_per_tile, int32_t * order);
 /* HBM bytes per timestream sample that the passes of that implementation move (accounting for
@@ -1173,8 +1158,8 @@ int toast_hip_fft_convolve_dev(
  * src/toast/fft.py:318-336].  tau: n_det time constants in seconds (host), indexed like per-detector kernels -- by
  * position in data_index, not by buffer row.  invert = 0 multiplies by K (TimeConstant(deconvolve=True)), invert = 1 by
  * 1 / K (the detector's low-pass response).  DC removal, the real Nyquist bin, padding, apodisation and crop as
- * toast_hip_fft_convolve.  The fused kernels always run their default row passes for this kernel kind
- * (toast_hip_fft_points / _rows_split / _rows_n2 do not apply to it); toast_hip_fft_select does.
+ * toast_hip_fft_convolve.  The fused kernels always run their 8-point row pass for this kernel kind (the rows entry
+ * of toast_hip_fft_points does not apply to it); toast_hip_fft_select does.
  * toast_hip_fft_impulse_extents_pole: toast_hip_fft_impulse_extents for these kernels [ref: src/toast/fft.py:836-872
  * with the kernel function of src/toast/ops/time_constant.py:155-168 and the multiply of src/toast/fft.py:318-336]. */
 int toast_hip_fft_convolve_pole(

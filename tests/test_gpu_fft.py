@@ -284,13 +284,11 @@ def test_fused_complex_kernels_and_common_kernel(pf, deconvolve):
         assert np.max(np.abs(got - want)) < (1e-11 if deconvolve else TOL) * np.max(np.abs(want))
 
 
-@pytest.mark.parametrize("rows", ["reg", "reg32", "pair", "split"])
 @pytest.mark.parametrize("tables", ["lds-complex", "lds-dense", "global-dense", "global-complex"])
-def test_fused_kernel_table_paths(pf, rows, tables):
+def test_fused_kernel_table_paths(pf, tables):
     """Row pass of the fused pipeline: kernel tables in LDS (few knots) or in global memory (many), interval search
     with several knots inside one block of N1 bins (dense knot vectors: the walk from the per-row-element hint), real
-    and complex kernels; the three layouts of the row pass (one row per wave in registers / row pair per 64 KB LDS tile /
-    one row per 32 KB LDS tile with the mirrored last butterfly)."""
+    and complex kernels."""
     from oracle import fft_oracle as fo
 
     rate, n_det = 200.0, 3
@@ -308,27 +306,27 @@ def test_fused_kernel_table_paths(pf, rows, tables):
         freq = np.linspace(0.0, rate / 2, 400)
         phase = True
     kernels = _noise_kernels(freq, n_det, complex_phase=phase)
-    pf.set_rows_mode(rows)
-    try:
-        for n_samp in (9000, 100001, 720000):
-            rng = np.random.default_rng(n_samp)
-            data = rng.standard_normal((n_det, n_samp)).cumsum(axis=1) * 0.01 + rng.standard_normal((n_det, n_samp))
-            want = data.copy()
-            fo.convolve(want, rate, kernel_freq=freq, kernels=kernels)
-            got = data.copy()
-            pf.convolve(got, rate, kernel_freq=freq, kernels=kernels)
-            assert np.max(np.abs(got - want)) < TOL * np.max(np.abs(want)), (n_samp, tables, rows)
-    finally:
-        pf.set_rows_mode("reg")
+    for n_samp in (9000, 100001, 720000):
+        rng = np.random.default_rng(n_samp)
+        data = rng.standard_normal((n_det, n_samp)).cumsum(axis=1) * 0.01 + rng.standard_normal((n_det, n_samp))
+        want = data.copy()
+        fo.convolve(want, rate, kernel_freq=freq, kernels=kernels)
+        got = data.copy()
+        pf.convolve(got, rate, kernel_freq=freq, kernels=kernels)
+        assert np.max(np.abs(got - want)) < TOL * np.max(np.abs(want)), (n_samp, tables)
 
 
 @pytest.mark.parametrize("n_samp", [720000, 1100000, 1440000, 2200000, 2880000])
 def test_register_tile_passes_against_lds_tile_passes(pf, n_samp):
-    """csrc/fft_reg.hip (round 5): the row pass with the tile in registers (16 points per lane: "reg"; 32: "reg32") and the column passes with the tile in registers
-    (n_fft 2^21 / 2^22 / 2^23: column tiles of 512 x 8, 1024 x 8, 2048 x 4) against the oracle and against the LDS-tile
-    kernels of fft_fused.hip, per-detector kernels, rows through an index."""
+    """The column passes with the tile in registers (csrc/fft_reg.hip; n_fft 2^21 / 2^22 / 2^23: column tiles of
+    512 x 8, 1024 x 8, 2048 x 4) against the oracle and against the LDS-tile column kernels of fft_fused.hip, which
+    remain the fallback for unaligned timestreams: the same values once in a 16-byte-aligned device buffer and once in
+    a buffer whose first row starts 8 bytes past a 16-byte boundary (n_samp is even, so every row is then misaligned
+    and Params::aligned is 0).  Per-detector kernels, rows through an index."""
+    import torch
     from oracle import fft_oracle as fo
 
+    assert n_samp % 2 == 0
     rng = np.random.default_rng(n_samp + 5)
     rate, n_det, rows = 200.0, 3, 4
     freq = np.concatenate([[0.0], np.geomspace(1e-5, rate / 2, 70)])
@@ -338,28 +336,27 @@ def test_register_tile_passes_against_lds_tile_passes(pf, n_samp):
     want = np.ascontiguousarray(buf[idx])
     fo.convolve(want, rate, kernel_freq=freq, kernels=kernels)
     scale = np.max(np.abs(want))
+    stream = torch.cuda.current_stream().cuda_stream
     out = {}
-    try:
-        for cols, rowmode in (("reg9", "reg"), ("lds", "pair"), ("reg9", "pair"), ("lds", "reg"), ("reg9", "reg32")):
-            pf.set_cols_mode(cols)
-            pf.set_rows_mode(rowmode)
-            got = buf.copy()
-            pf.convolve_buffer(got, idx, rate, freq, kernels)
-            assert np.max(np.abs(got[idx] - want)) < TOL * scale, (cols, rowmode)
-            assert np.array_equal(got[1], buf[1])
-            out[(cols, rowmode)] = got
-    finally:
-        pf.set_cols_mode("reg")
-        pf.set_rows_mode("reg")
-    for key, got in out.items():
-        assert np.max(np.abs(got - out[("lds", "pair")])) < 1e-13 * scale, key
+    for offset in (0, 1):       # in doubles
+        t = torch.zeros(rows * n_samp + 2, dtype=torch.float64, device="cuda")
+        assert t.data_ptr() % 16 == 0
+        view = t[offset:offset + rows * n_samp].view(rows, n_samp)
+        view.copy_(torch.from_numpy(buf))
+        assert view.data_ptr() % 16 == 8 * offset
+        pf.convolve_dev(view.data_ptr(), idx, n_samp, rate, freq, kernels, stream=stream)
+        torch.cuda.synchronize()
+        got = view.cpu().numpy()
+        assert np.max(np.abs(got[idx] - want)) < TOL * scale, offset
+        assert np.array_equal(got[1], buf[1]), offset
+        out[offset] = got
+    assert np.max(np.abs(out[0] - out[1])) < 1e-13 * scale
 
 
 @pytest.mark.parametrize("tables", ["lds-real", "lds-complex", "global-dense"])
-def test_fused_rows_of_1024(pf, tables):
-    """The fused kernels with rows of N2 = 1024 (32 KB row-pair tiles, four workgroups per CU in the row pass; 64-byte
-    pieces in the column passes) against the oracle and against the N2 = 2048 factorisation, for every N1 that the
-    half-size rows allow (n_fft 2^13 .. 2^21) plus a length that falls back to N2 = 2048 (n_fft 2^22)."""
+def test_fused_table_kinds_at_every_short_length(pf, tables):
+    """The fused kernels (rows of N2 = 2048) against the oracle for real, complex and too-large-for-LDS kernel tables
+    at n_fft 2^13 .. 2^22."""
     from oracle import fft_oracle as fo
 
     rate, n_det = 200.0, 3
@@ -370,22 +367,14 @@ def test_fused_rows_of_1024(pf, tables):
     else:
         freq, phase = np.concatenate([[0.0], np.geomspace(1e-4, rate / 2, 70)]), False
     kernels = _noise_kernels(freq, n_det, complex_phase=phase)
-    try:
-        for n_samp in (2100, 9000, 33000, 100001, 400000, 720000, 1100000):
-            rng = np.random.default_rng(n_samp)
-            data = rng.standard_normal((n_det, n_samp)).cumsum(axis=1) * 0.01 + rng.standard_normal((n_det, n_samp))
-            want = data.copy()
-            fo.convolve(want, rate, kernel_freq=freq, kernels=kernels)
-            out = {}
-            for n2 in (2048, 1024):
-                pf.set_rows_n2(n2)
-                got = data.copy()
-                pf.convolve(got, rate, kernel_freq=freq, kernels=kernels)
-                assert np.max(np.abs(got - want)) < TOL * np.max(np.abs(want)), (n_samp, tables, n2)
-                out[n2] = got
-            assert np.max(np.abs(out[1024] - out[2048])) < 1e-13 * np.max(np.abs(want))
-    finally:
-        pf.set_rows_n2(2048)
+    for n_samp in (2100, 9000, 33000, 100001, 400000, 720000, 1100000):
+        rng = np.random.default_rng(n_samp)
+        data = rng.standard_normal((n_det, n_samp)).cumsum(axis=1) * 0.01 + rng.standard_normal((n_det, n_samp))
+        want = data.copy()
+        fo.convolve(want, rate, kernel_freq=freq, kernels=kernels)
+        got = data.copy()
+        pf.convolve(got, rate, kernel_freq=freq, kernels=kernels)
+        assert np.max(np.abs(got - want)) < TOL * np.max(np.abs(want)), (n_samp, tables)
 
 
 @pytest.mark.parametrize("n_samp", [6000, 50001, 300000])

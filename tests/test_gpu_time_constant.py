@@ -154,10 +154,11 @@ def test_batches_keep_their_time_constants(pf, n_samp):
 
 
 @pytest.mark.parametrize("n_samp", [720000, 1100003])
-def test_long_lengths_and_experiment_switches(pf, n_samp):
+def test_long_lengths_both_directions(pf, n_samp):
     """n_fft 2^21 (LDS forward columns, 16-point register inverse columns) and 2^22 (odd length: the unaligned column
-    passes, four columns per tile) against the restatement, both directions.  Then with the row-pass switches away from their
-    defaults: an analytic call has no instantiation of those row passes and runs the default ones -- the same bits."""
+    passes, four columns per tile) against the restatement, both directions.  Then with the rows entry of the points
+    switch away from its default: an analytic call has no 16-point row instantiation and runs the default one -- the
+    same bits."""
     rng = np.random.default_rng(n_samp)
     rate = 200.0
     taus = np.array([2e-3, 20e-3])
@@ -174,17 +175,13 @@ def test_long_lengths_and_experiment_switches(pf, n_samp):
         assert err < TOL[direction]
         got[direction] = g
     try:
-        for mode, rows_points, n2 in (("pair", 16, 1024), ("split", 16, 2048), ("reg32", 8, 1024)):
-            pf.set_rows_mode(mode)
-            pf.set_points(rows_points, 0, 0)
-            pf.set_rows_n2(n2)
+        pf.set_points(16, 0, 0)
+        for direction in ("convolve", "deconvolve"):
             g = data.copy()
-            pf.convolve(g, rate, kernel_func=pf.SinglePole(taus, deconvolve=(mode == "split")))
-            assert np.array_equal(g, got["deconvolve" if mode == "split" else "convolve"]), mode
+            pf.convolve(g, rate, kernel_func=pf.SinglePole(taus, deconvolve=direction == "deconvolve"))
+            assert np.array_equal(g, got[direction]), direction
     finally:
-        pf.set_rows_mode("reg")
         pf.set_points()
-        pf.set_rows_n2(2048)
 
 
 def _run_operator(resident, **traits):

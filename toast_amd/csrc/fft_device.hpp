@@ -12,11 +12,10 @@ constexpr int kLT = 12;             // log2 of the tile (4096 complex doubles = 
 constexpr int kTile = 1 << kLT;
 // LDS budget of the row pass for the kernel tables (two 64 KB tiles + tables per CU: 2 x (64 + 15) KB <= 160 KB)
 constexpr int kTabLdsMax = 15 * 1024;
-// ... and with 32 KB tiles (N2 = 1024): four workgroups per CU, 4 x (32 + 7.5) KB <= 160 KB
-constexpr int kTabLdsHalf = 7 * 1024 + 512;
-// Every kernel is a template on P = points per thread (kTile / P threads per workgroup):
+// The LDS-tile kernels are templates on P = points per thread (kTile / P threads per workgroup):
 //   P = 16: 256 threads, radix-16 ends, one LDS round trip fewer per transform, ~250 VGPRs -> 2 waves / SIMD
-//   P = 8:  512 threads, radix-8 stages, ~100 VGPRs -> 4 waves / SIMD (two workgroups per CU either way: LDS)
+//   P = 8:  512 threads, radix-8 stages, ~100 VGPRs -> 4 waves / SIMD (two workgroups per CU either way: LDS);
+//           the default, measured faster (profiles/r02_f_fft_points.txt)
 
 // ------------------------------------------------------------------------------------------
 // complex helpers (explicit fma: the library is built with -ffp-contract=off)
@@ -263,6 +262,10 @@ __device__ __forceinline__ double2 tw_big(const Tables & tb, int64_t e) {
     return cmul(cmul(a, b), c);
 }
 
+// The host sets xcd_order = 2 and stream_hint = 0 or 1, N2 = 2048 always, and gives the register column kernel of
+// pass 1 its fwd_seq wherever the tiles divide.  The kernels still carry the run-time branches for the other values
+// (xcd_order != 2, the higher stream_hint bits, fwd_seq == nullptr, blockIdx.x > 0 in k_fft_rows): pruning them changes
+// timed code and is left to a change that measures it.
 struct Params {
     double * tod;                 // [rows, n_samp]
     const int32_t * d_idx;        // row of detector b

@@ -22,11 +22,15 @@
 //   pass 3  k_fft_cols<INV>   twiddle, inverse FFT of length N1 down the columns, crop and scale
 //                             straight into the timestream (no crop pass)
 //
-// Every FFT inside a pass is a Stockham autosort transform on a tile of 4096 complex doubles held
-// by 256 threads x 16 points: radix-16 / 8 / 4 / 2 butterflies in registers, tile exchanges
-// through 64 KB of LDS (XOR-swizzled against bank conflicts), the first and last radix-16 stage
-// go straight from / to global memory.  The inverse transforms reuse the forward code on data with
+// Every FFT inside a pass of this file is a Stockham autosort transform on a tile of 4096 complex
+// doubles held by 512 threads x 8 points (or 256 x 16): radix-8 (16) / 4 / 2 butterflies in registers,
+// tile exchanges through 64 KB of LDS (XOR-swizzled against bank conflicts), the first and last
+// radix-8 (16) stage go straight from / to global memory.  The inverse transforms reuse the forward code on data with
 // real and imaginary parts swapped (ifft(z) = swap(fft(swap(z)))).
+//
+// These LDS-tile kernels serve every length and any alignment.  Where fft_reg.hip has a kernel that
+// keeps the tile in registers it runs instead: the row pairs of pass 2 at every length, the column
+// passes of aligned timestreams at n_fft 2^21 .. 2^23 (the table at convolve_any below).
 //
 // Algorithmic HBM bytes per timestream sample: pass 1 reads 8 (+ mirror
 // re-reads served by L2) and writes 8 n_fft / n_samp, pass 2 reads and writes 8 n_fft / n_samp,
@@ -41,10 +45,8 @@
 #include <functional>
 #include <map>
 #include <mutex>
-#include <string>
 #include <vector>
 
-#include "runtime.hpp"
 #include "runtime.hpp"
 #include "fft_device.hpp"
 
@@ -53,7 +55,6 @@ namespace fused_fft {
 
 // fft_reg.hip
 bool rows_reg_supported(const Params & p);
-void launch_rows_reg(const Params & p, unsigned n_det, bool tab_lds, size_t tab_bytes, hipStream_t st);
 void launch_rows_reg16(const Params & p, unsigned n_det, bool tab_lds, size_t tab_bytes, hipStream_t st);
 void launch_rows_reg16_pole(const Params & p, unsigned n_det, hipStream_t st);
 void pack_tables(const Params & p, char * blob, int64_t n_kern, hipStream_t st);
@@ -61,25 +62,12 @@ bool cols_reg_supported(const Params & p, int min_log_n1);
 int cols_reg_log_c(int log_n1);
 int cols_reg_twiddles(int log_n1, int * out);
 void launch_cols_reg(const Params & p, bool inv, unsigned n_det, hipStream_t st);
-// column passes: 1 (default) = tile in registers where fft_reg.hip has a kernel for the length (n_fft 2^21 .. 2^23,
-// aligned timestreams), 0 = tile in LDS (k_fft_cols).  TOAST_HIP_FFT_COLS=reg|lds
-namespace {
-int g_cols_mode = -1;      // 0: LDS tiles, 1: register tiles for N1 >= 1024 (default), 2: register tiles for N1 >= 512 too
-}
-static int cols_mode() {
-    if (g_cols_mode < 0) {
-        const char * e = std::getenv("TOAST_HIP_FFT_COLS");
-        const std::string v = (e != nullptr) ? std::string(e) : std::string();
-        g_cols_mode = (v == "lds") ? 0 : (v == "reg9") ? 2 : 1;
-    }
-    return g_cols_mode;
-}
-static bool cols_reg_for(const Params & p) { return cols_mode() != 0 && cols_reg_supported(p, cols_mode() == 2 ? 9 : 10); }
-// pass 3 at N1 = 512 (n_fft 2^21) runs in registers unless the LDS tile is asked for at every length (mode 0): there the
-// forward LDS-tile kernel and the register kernel are a tie (2.75-3.07 against 2.94-2.97 ms from box to box), the inverse
-// register kernel with 16 points per lane is 10 % ahead (same tile geometry: 8 columns)
-static bool cols_inv_reg_for(const Params & p) { return cols_mode() != 0 && cols_reg_supported(p, 9); }
-void set_cols_reg(int on) { g_cols_mode = (on == 2) ? 2 : (on ? 1 : 0); }
+// Column passes with the tile in registers (fft_reg.hip; aligned timestreams only): passes 1 and 3 at N1 = 1024 / 2048
+// (n_fft 2^22 / 2^23), pass 3 alone at N1 = 512 (n_fft 2^21) -- there the forward LDS-tile kernel and a register kernel
+// were a tie, the inverse register kernel with 16 points per lane is 10 % ahead (profiles/r05_a section 10).  Everything
+// else runs k_fft_cols, the tile in LDS.
+static bool cols_reg_for(const Params & p) { return cols_reg_supported(p, 10); }
+static bool cols_inv_reg_for(const Params & p) { return cols_reg_supported(p, 9); }
 
 // pass 1 (INV = false) and pass 3 (INV = true): transforms of length N1 down the columns
 template <int LT, int P, bool INV>
@@ -175,7 +163,7 @@ __global__ __launch_bounds__((1 << LT) / P, (P == 16 ? 2 : 4)) void k_fft_cols(c
 
 
 // pass 2: rows (k1, N1 - k1) [block 0: rows 0 and N1 / 2]
-// LT = log2 of the tile = 2 N2: 12 (N2 = 2048, 64 KB, two workgroups per CU) or 11 (N2 = 1024, 32 KB, four per CU)
+// LT = log2 of the tile = 2 N2: 12 (N2 = 2048, 64 KB, two workgroups per CU)
 // POLE: the analytic single-pole kernel (PoleTab, one double per detector) instead of the tabulated ones
 template <int LT, int P, bool TLDS, bool POLE = false>
 __global__ __launch_bounds__((1 << LT) / P, (P == 16 ? 2 : 4)) void k_fft_rows(const Params p) {
@@ -301,67 +289,6 @@ __global__ __launch_bounds__((1 << LT) / P, (P == 16 ? 2 : 4)) void k_fft_rows(c
     PHASE_SINCE_ENTRY(15);      // the workgroup's whole life
 }
 
-// pass 2, row pairs (k1, N1 - k1) with 0 < k1 < N1 / 2: ONE row (N2 = 2048 elements, 32 KB of LDS) in the tile at
-// a time, so that four or five workgroups share a CU instead of two (the passes are latency bound:
-// profiles/r02_c_pmc_hot_kernels.txt).  Bin k of row k1 pairs with bin M - k = element N2 - 1 - q of row N1 - k1.  The
-// last radix-P butterfly of the second row's transform is computed by the MIRRORED thread (u = T - 1 - tid), which
-// leaves both members of each of the thread's P pairs in its own registers: unpacking, kernel and repacking need no
-// LDS round trip, and the first butterfly of that row's inverse transform starts from the same registers.
-template <int P, int WPE, bool TLDS>
-__global__ __launch_bounds__((kTile / 2) / P, WPE) void k_fft_rows_split(const Params p) {
-    constexpr int LT = kLT - 1;
-    constexpr int T = (1 << LT) / P;
-    extern __shared__ double2 sm[];
-    const int tid = threadIdx.x;
-    const int b = blockIdx.y;
-    const int g = blockIdx.x + 1;
-    const int64_t n1 = int64_t(1) << p.log_n1;
-    const int64_t m = n1 << LT;
-    double2 * __restrict__ row_a = p.work + (int64_t)b * m + ((int64_t)g << LT);
-    double2 * __restrict__ row_b = p.work + (int64_t)b * m + ((n1 - g) << LT);
-    double2 va[P], vb[P];
-#pragma unroll
-    for (int k = 0; k < P; ++k) va[k] = row_a[tid + k * T];
-#pragma unroll
-    for (int k = 0; k < P; ++k) vb[k] = row_b[tid + k * T];
-    const int um = T - 1 - tid;
-    const auto kt = KTabSel<TLDS>::make(p, p.per_det ? (int64_t)(p.det0 + b) : 0,
-                                        reinterpret_cast<char *>(sm + (kTile / 2)), tid, T);
-    tile_fft_t<LT, P>(va, sm, tid, LT, p.tb.wtile, tid, tid);      // va[j] = Z[g + N1 (tid + j T)]
-    tile_fft_t<LT, P>(vb, sm, tid, LT, p.tb.wtile, tid, um);       // vb[j] = Z[M - (g + N1 (tid + (P-1-j) T))]
-
-    {
-        // a thread's bins k = k0 + N1 T j are N / (2 P) apart: unpacking twiddles w_N^k0 times the constants w_2P^j
-        constexpr double c16[8] = {1.0, 0.92387953251128673848, 0.70710678118654752440, 0.38268343236508977173,
-                                   0.0, -0.38268343236508977173, -0.70710678118654752440, -0.92387953251128673848};
-        constexpr double s16[8] = {0.0, 0.38268343236508977173, 0.70710678118654752440, 0.92387953251128673848,
-                                   1.0, 0.92387953251128673848, 0.70710678118654752440, 0.38268343236508977173};
-        static_assert(P == 8 || P == 4, "k_fft_rows_split: 4 or 8 points per thread");
-        const int k0 = g + ((int)n1) * tid;
-        const int dk = ((int)n1) * T;
-        const double2 w0 = tw_big(p.tb, k0);
-        int lo_a[P], lo_b[P];
-#pragma unroll
-        for (int j = 0; j < P; ++j) {
-            lo_a[j] = kernel_interval(kt, k0 + dk * j);
-            lo_b[j] = kernel_interval(kt, (int)m - (k0 + dk * j));
-        }
-#pragma unroll
-        for (int j = 0; j < P; ++j) {
-            const int k = k0 + dk * j;
-            const double2 wk = (j == 0) ? w0 : cmul(w0, make_double2(c16[j * (8 / P)], -s16[j * (8 / P)]));
-            pair_update_reg(va[j], vb[P - 1 - j], false, wk, kernel_eval(kt, lo_a[j], k),
-                            kernel_eval(kt, lo_b[j], (int)m - k), p.deconvolve);
-        }
-    }
-    tile_fft_t<LT, P>(vb, sm, tid, LT, p.tb.wtile, um, tid);
-#pragma unroll
-    for (int k = 0; k < P; ++k) row_b[tid + k * T] = vb[k];
-    tile_fft_t<LT, P>(va, sm, tid, LT, p.tb.wtile, tid, tid);
-#pragma unroll
-    for (int k = 0; k < P; ++k) row_a[tid + k * T] = va[k];
-}
-
 // interval of the kernel's piecewise cubics at bin q N1 (frequency q N1 fstep), q = 0 .. N2 + 1
 // (threads n_block .. n_block + N1 - 1: the interval at every bin of the first block, hint0)
 __global__ void k_knot_hint(const double * __restrict__ knots, int n_knot, double fstep, int log_n1, int64_t n_block,
@@ -456,8 +383,6 @@ static Plan & get_plan(int64_t n_fft, hipStream_t st) {
         set(reinterpret_cast<const void *>(&k_fft_rows<kLT, 8, false>), lds);
         set(reinterpret_cast<const void *>(&k_fft_rows<kLT, 16, true>), lds_tab);
         set(reinterpret_cast<const void *>(&k_fft_rows<kLT, 8, true>), lds_tab);
-        set(reinterpret_cast<const void *>(&k_fft_rows<kLT - 1, 8, false>), lds / 2);
-        set(reinterpret_cast<const void *>(&k_fft_rows<kLT - 1, 8, true>), lds / 2 + kTabLdsHalf);
         set(reinterpret_cast<const void *>(&k_fft_rows<kLT, 8, false, true>), lds);
         attr_set = true;
     }
@@ -646,8 +571,9 @@ static const int32_t * chain_order_for(Plan & pl, int64_t n_samp, int64_t n_buff
 }
 
 namespace {
-// points per thread of (row pass, forward column pass, inverse column pass); measured best at cfg-3:
-// 8 / 8 / 8 (profiles/r02_f_fft_points.txt; the inverse column pass moved from 16 to 8 with the XCD-aware tile order)
+// points per thread of the LDS-tile kernels in (row pass, forward column pass, inverse column pass); measured best at
+// cfg-3: 8 / 8 / 8 (profiles/r02_f_fft_points.txt; the inverse column pass moved from 16 to 8 with the XCD-aware tile
+// order).  TOAST_HIP_FFT_POINTS="rows,cols_fwd,cols_inv" / toast_hip_fft_points: the one remaining experiment switch
 int g_points[3] = {0, 0, 0};
 void read_points() {
     if (g_points[0] != 0) return;
@@ -669,33 +595,6 @@ int points_of(int pass) {
     read_points();
     return g_points[pass];
 }
-// row pass: 2 (default) = tile in registers, 16 points per lane: a row in two waves, three workgroups per CU
-// (k_fft_rows_reg16, fft_reg.hip); 3 = 32 points per lane, one row per wave (k_fft_rows_reg); 0 = row pair per 64 KB LDS
-// tile (k_fft_rows); 1 = one row per 32 KB tile (k_fft_rows_split: experiment; needs more registers than four
-// workgroups per CU leave).  TOAST_HIP_FFT_ROWS=reg|reg32|lds|split / toast_hip_fft_rows_split(mode)
-namespace {
-int g_rows_split = -1;
-}
-int rows_split() {
-    if (g_rows_split < 0) {
-        const char * e = std::getenv("TOAST_HIP_FFT_ROWS");
-        const std::string v = (e != nullptr) ? std::string(e) : std::string();
-        g_rows_split = (v == "split") ? 1 : (v == "lds") ? 0 : (v == "reg32") ? 3 : 2;
-    }
-    return g_rows_split;
-}
-void set_rows_split(int split) { g_rows_split = (split >= 1 && split <= 3) ? split : 0; }
-namespace {
-int g_rows_n2 = -1;
-}
-int rows_n2() {
-    if (g_rows_n2 < 0) {
-        const char * e = std::getenv("TOAST_HIP_FFT_N2");
-        g_rows_n2 = (e != nullptr && std::atoi(e) == 1024) ? 1024 : 2048;
-    }
-    return g_rows_n2;
-}
-void set_rows_n2(int n2) { g_rows_n2 = (n2 == 1024) ? 1024 : 2048; }
 void set_points(int rows, int cols_fwd, int cols_inv) {
     g_points[0] = 0;
     read_points();       // defaults
@@ -715,9 +614,16 @@ double pipeline_bytes_per_sample(int64_t n_samp, int64_t n_fft) {
 }
 
 // d_tau != nullptr: the analytic single-pole kernel K = 1 + i 2 pi tau f of detector d (d_tau[d], seconds; `deconvolve`
-// then means "multiply by 1 / K") instead of the tabulated kernels -- no hints, no packed tables, and always the default
-// row passes (k_fft_rows for the self-paired rows, k_fft_rows_reg16 for the others, N2 = 2048) whatever the experiment
-// switches say: the other row passes have no analytic instantiation.
+// then means "multiply by 1 / K") instead of the tabulated kernels -- no hints, no packed tables.
+//
+// One pipeline per length (n_fft = 2 N1 N2, N2 = 2048; "aligned" = Params::aligned):
+//   pass 1   aligned and N1 = 1024 / 2048: k_fft_cols_reg<., false>;  otherwise k_fft_cols<kLT, P, false>
+//   pass 2   k_fft_rows<kLT, P, .> for the self-paired rows 0 and N1 / 2, k_fft_rows_reg16 for the pairs (g, N1 - g)
+//   pass 3   aligned and N1 = 512: k_fft_cols_inv16<9>;  aligned and N1 = 1024 / 2048: k_fft_cols_reg<., true>;
+//            otherwise k_fft_cols<kLT, P, true>
+// P = 8 points per thread unless toast_hip_fft_points asks for 16 (points_of above).  The other variants that were
+// measured against these and lost (rows of 1024, one row per 32 KB tile, 32 points per lane, hints in LDS, tables in
+// global memory by choice) are gone; DESIGN.md section 6 lists where each result is recorded.
 static void convolve_any(double * d_tod, const int32_t * d_idx, int64_t n_det, int64_t n_samp, int64_t n_fft,
                          int64_t n_buffer, int64_t n_reflect, double fstep, const double * d_knots, int64_t n_knot,
                          const double * d_mag, const double * d_ang, int per_det, int deconvolve, const double * d_tau,
@@ -735,10 +641,7 @@ static void convolve_any(double * d_tod, const int32_t * d_idx, int64_t n_det, i
     p.n_fft = n_fft;
     p.n_buffer = n_buffer;
     p.n_reflect = n_reflect;
-    // Rows of N2 = 2048 (64 KB pair tiles) or, for M <= 2^20, of N2 = 1024 (32 KB pair tiles: four workgroups per CU in
-    // the row pass; the column passes then move 64-byte instead of 128-byte pieces).  TOAST_HIP_FFT_N2=1024|2048.
-    p.log_n2 = kLT - 1;
-    if (!pole && rows_n2() == 1024 && log_m >= 11 && log_m <= 20) p.log_n2 = kLT - 2;
+    p.log_n2 = kLT - 1;          // rows of N2 = 2048: a row pair is one 64 KB tile
     p.log_n1 = log_m - p.log_n2;
     p.tb.wtile = pl.tables;
     p.tb.t0 = pl.tables + kTile;
@@ -757,31 +660,17 @@ static void convolve_any(double * d_tod, const int32_t * d_idx, int64_t n_det, i
     p.aligned = ((n_buffer % 2) == 0 && (n_samp % 2) == 0 && (n_reflect % 2) == 0 &&
                  (reinterpret_cast<uintptr_t>(d_tod) % 16) == 0 && (reinterpret_cast<uintptr_t>(d_apod) % 16) == 0)
                     ? 1 : 0;
-    {
-        static int xo = -1;
-        if (xo < 0) {
-            const char * e = std::getenv("TOAST_HIP_FFT_XCD");
-            // 0: tiles in launch order; 1: a contiguous eighth of the columns per XCD; 2 (default): pass 1 with the mirror
-            // partners of a tile on one XCD where the geometry allows it (else as 1), passes 3 as 1
-            xo = (e != nullptr && e[0] == '0') ? 0 : (e != nullptr && e[0] == '1') ? 1 : 2;
-        }
-        p.xcd_order = xo;
-        static int sh = -1;
-        if (sh < 0) {
-            const char * e = std::getenv("TOAST_HIP_FFT_STREAM_HINT");
-            // default 1: pass 1 writes the work array with non-temporal stores (profiles/r04_c section 5: the window table
-            // and the mirrored re-reads of the timestream then stay in L2; every other bit measured neutral or worse)
-            sh = (e != nullptr && e[0] != '\0') ? std::atoi(e) : 1;
-        }
-        p.stream_hint = sh;
-        // ... but not with two columns per tile (N1 = 2048, n_fft 2^23): a non-temporal store sends every 32-byte piece to
-        // memory on its own, 61 -> 90 ms per call; with four columns (64-byte pieces, 2^22) it still gains 1.5 %
-        // (profiles/r04_c section 6)
-        static const bool forced = std::getenv("TOAST_HIP_FFT_STREAM_HINT") != nullptr;
-        // (pass 1 of the register kernels: plain stores at every length -- 49.4 against 51.6 ms per call at 2^23, 44.5
-        // against 47.2 at 2^22, profiles/r05_a)
-        if (!forced && (cols_reg_for(p) || (kLT - p.log_n1) < 2)) p.stream_hint &= ~1;
-    }
+    // Column tiles: pass 1 with the mirror partners of a tile on one XCD where the geometry allows it (tile_order below),
+    // else -- and pass 3 always -- a contiguous eighth of the columns per XCD.
+    p.xcd_order = 2;
+    // Pass 1 writes the work array with non-temporal stores (bit 0; profiles/r04_c section 5: the window table and the
+    // mirrored re-reads of the timestream then stay in L2; every other bit measured neutral or worse) ...
+    p.stream_hint = 1;
+    // ... but not with two columns per tile (N1 = 2048, n_fft 2^23): a non-temporal store sends every 32-byte piece to
+    // memory on its own, 61 -> 90 ms per call; with four columns (64-byte pieces, 2^22) it still gains 1.5 %
+    // (profiles/r04_c section 6); and not in pass 1 of the register kernels: plain stores at every length -- 49.4 against
+    // 51.6 ms per call at 2^23, 44.5 against 47.2 at 2^22 (profiles/r05_a)
+    if (cols_reg_for(p) || (kLT - p.log_n1) < 2) p.stream_hint &= ~1;
     // unnormalised inverse of length M on un-halved packing factors: 1 / (4 M), a power of two
     p.scale = 1.0 / (4.0 * (double)m);
 
@@ -815,59 +704,36 @@ static void convolve_any(double * d_tod, const int32_t * d_idx, int64_t n_det, i
         hipLaunchKernelGGL(k_knot_hint, dim3((unsigned)((n_hint + n_hint0 + 255) / 256)), dim3(256), 0, st, d_knots,
                            (int)n_knot, fstep, p.log_n1, n_hint, d_hint, d_hint16, d_hint0);
     }
-    if (blob_bytes && rows_split() >= 2) pack_tables(p, scratch + hint_bytes, n_kern, st);
-    static int tab_lds_env = -1;
-    if (tab_lds_env < 0) {
-        const char * e = std::getenv("TOAST_HIP_FFT_TABLES");      // "global": experiment switch
-        tab_lds_env = (e != nullptr && std::string(e) == "global") ? 0 : 1;
-    }
-    const bool half_rows = p.log_n2 == kLT - 2;
-    const bool tab_lds = tab_lds_env && n_knot < 65535 && tab_bytes <= (size_t)(half_rows ? kTabLdsHalf : kTabLdsMax);
+    if (blob_bytes) pack_tables(p, scratch + hint_bytes, n_kern, st);
+    const bool tab_lds = n_knot < 65535 && tab_bytes <= (size_t)kTabLdsMax;
     const size_t lds = kTile * sizeof(double2);
     const size_t lds_rows = lds + (tab_lds ? tab_bytes : 0);
-    const size_t lds_split = lds / 2 + (tab_lds ? tab_bytes : 0);
     const bool cols_reg = cols_reg_for(p);
     const int log_c = cols_reg ? cols_reg_log_c(p.log_n1) : (kLT - p.log_n1);               // columns per tile
     const unsigned n_col_tiles = (unsigned)(int64_t(1) << (p.log_n2 - log_c));               // N2 / C
     p.tile_order = nullptr;
-    if (p.xcd_order == 2 && p.aligned) {
+    if (p.aligned) {
         p.tile_order = tile_order_for(pl, n_samp, n_buffer, n_reflect, (int64_t)n_col_tiles, int64_t(1) << log_c, st);
     }
-    // pass 1 of the register kernels: segments of the tile chain x groups of detectors per XCD (TOAST_HIP_FFT_FWD_SEG="k,g",
-    // "0": the two-dimensional grid with tile_order)
+    // pass 1 of the register kernels: a one-dimensional grid in which every XCD works through its piece of the tile chain
+    // in segments of eight tiles (four 128-byte line columns at N1 = 2048) x all detectors of the batch -- the tiles that
+    // run side by side on an XCD read the same window entries and share written lines (profiles/r05_a).
+    // Where the tiles do not divide: the two-dimensional grid with tile_order.
     p.fwd_seq = nullptr;
     p.fwd_k = p.fwd_g = p.fwd_tiles = p.fwd_dets = 0;
     if (cols_reg) {
-        static int seg_k = -1, seg_g = -1;
-        if (seg_k < 0) {
-            seg_k = 8;          // eight tiles (four 128-byte line columns at N1 = 2048) x all detectors of the batch: the tiles
-            seg_g = 1 << 20;    // that run side by side on an XCD read the same window entries and share written lines
-                                // (4 before pass 1 was freed of its scratch traffic; now 46.1-46.4 against 46.9-47.2 ms at 2^23)
-            const char * e = std::getenv("TOAST_HIP_FFT_FWD_SEG");
-            if (e != nullptr) {
-                int a = 0, b = 0;
-                const int n = std::sscanf(e, "%d,%d", &a, &b);
-                if (n == 2 && a > 0 && b > 0) {
-                    seg_k = a;
-                    seg_g = b;
-                } else if (n >= 1 && a == 0) {
-                    seg_k = 0;
-                }
-            }
-        }
+        constexpr int seg_k = 8, seg_g = 1 << 20;
         const int64_t tpx = (int64_t)n_col_tiles / 8;
-        if (seg_k > 0 && (n_col_tiles % 8u) == 0u && tpx % seg_k == 0) {
+        if ((n_col_tiles % 8u) == 0u && tpx % seg_k == 0) {
             p.fwd_seq = chain_order_for(pl, n_samp, n_buffer, n_reflect, (int64_t)n_col_tiles, int64_t(1) << log_c, st);
             p.fwd_k = seg_k;
             p.fwd_g = seg_g;
             p.fwd_tiles = (int)n_col_tiles;
         }
     }
-    const unsigned n_row_tiles = (unsigned)((int64_t(1) << p.log_n1) / 2);                 // N1 / 2
     for (int64_t det0 = 0; det0 < n_det; det0 += batch) {
         const int64_t nb = (n_det - det0 < batch) ? (n_det - det0) : batch;
         p.det0 = (int)det0;
-        // points per thread of each pass: TOAST_HIP_FFT_POINTS="rows,cols_fwd,cols_inv" / toast_hip_fft_points
         if (cols_reg) {
             p.fwd_dets = (int)nb;
             launch_cols_reg(p, false, (unsigned)nb, st);
@@ -876,45 +742,24 @@ static void convolve_any(double * d_tod, const int32_t * d_idx, int64_t n_det, i
         } else {
             hipLaunchKernelGGL((k_fft_cols<kLT, 16, false>), dim3(n_col_tiles, (unsigned)nb), dim3(kTile / 16), lds, st, p);
         }
+        // pass 2: rows 0 and N1 / 2 (the self-paired ones; all there are at N1 = 2), then the pairs (g, N1 - g)
+        const dim3 g_self(1, (unsigned)nb);
         if (pole) {
-            // rows 0 and N1 / 2 (all there are at N1 = 2), then the pairs (g, N1 - g)
-            hipLaunchKernelGGL((k_fft_rows<kLT, 8, false, true>), dim3(1, (unsigned)nb), dim3(kTile / 8), lds, st, p);
+            hipLaunchKernelGGL((k_fft_rows<kLT, 8, false, true>), g_self, dim3(kTile / 8), lds, st, p);
             if (rows_reg_supported(p)) launch_rows_reg16_pole(p, (unsigned)nb, st);
         } else {
-            const bool reg_rows = rows_split() >= 2 && !half_rows && rows_reg_supported(p);
-            const bool split = rows_split() == 1 && !half_rows;
-            // split / registers: rows 0 and N1 / 2 only (self-paired)
-            const dim3 g_pair((split || reg_rows) ? 1 : n_row_tiles, (unsigned)nb);
-            if (half_rows) {
-                const size_t lds_half = lds / 2 + (tab_lds ? tab_bytes : 0);
+            if (points_of(0) == 8) {
                 if (tab_lds) {
-                    hipLaunchKernelGGL((k_fft_rows<kLT - 1, 8, true>), g_pair, dim3(kTile / 16), lds_half, st, p);
+                    hipLaunchKernelGGL((k_fft_rows<kLT, 8, true>), g_self, dim3(kTile / 8), lds_rows, st, p);
                 } else {
-                    hipLaunchKernelGGL((k_fft_rows<kLT - 1, 8, false>), g_pair, dim3(kTile / 16), lds_half, st, p);
-                }
-            } else if (split || points_of(0) == 8) {
-                if (tab_lds) {
-                    hipLaunchKernelGGL((k_fft_rows<kLT, 8, true>), g_pair, dim3(kTile / 8), lds_rows, st, p);
-                } else {
-                    hipLaunchKernelGGL((k_fft_rows<kLT, 8, false>), g_pair, dim3(kTile / 8), lds_rows, st, p);
+                    hipLaunchKernelGGL((k_fft_rows<kLT, 8, false>), g_self, dim3(kTile / 8), lds_rows, st, p);
                 }
             } else if (tab_lds) {
-                hipLaunchKernelGGL((k_fft_rows<kLT, 16, true>), g_pair, dim3(kTile / 16), lds_rows, st, p);
+                hipLaunchKernelGGL((k_fft_rows<kLT, 16, true>), g_self, dim3(kTile / 16), lds_rows, st, p);
             } else {
-                hipLaunchKernelGGL((k_fft_rows<kLT, 16, false>), g_pair, dim3(kTile / 16), lds_rows, st, p);
+                hipLaunchKernelGGL((k_fft_rows<kLT, 16, false>), g_self, dim3(kTile / 16), lds_rows, st, p);
             }
-            if (reg_rows) {
-                if (rows_split() == 2) launch_rows_reg16(p, (unsigned)nb, tab_lds, tab_bytes, st);
-                else launch_rows_reg(p, (unsigned)nb, tab_lds, tab_bytes, st);
-            }
-            if (split && n_row_tiles > 1) {
-                const dim3 gr(n_row_tiles - 1, (unsigned)nb), bl(kTile / 16);
-                if (tab_lds) {
-                    hipLaunchKernelGGL((k_fft_rows_split<8, 2, true>), gr, bl, lds_split, st, p);
-                } else {
-                    hipLaunchKernelGGL((k_fft_rows_split<8, 2, false>), gr, bl, lds_split, st, p);
-                }
-            }
+            if (rows_reg_supported(p)) launch_rows_reg16(p, (unsigned)nb, tab_lds, tab_bytes, st);
         }
         if (cols_reg || cols_inv_reg_for(p)) {
             launch_cols_reg(p, true, (unsigned)nb, st);

@@ -6,18 +6,18 @@
 // barriers per tile, and 84 % of a workgroup's life spent in chains of butterfly -> LDS exchange -> barrier with
 // nothing saturated (profiles/r04_c section 1).  A CU has 512 KB of vector registers and 160 KB of LDS, so here
 //
-//   * a lane holds 32 points (128 VGPRs of data, 2 waves per SIMD); a wave of the row pass holds one whole row of
-//     N2 = 2048 points, a pair of waves of a column pass one tile of N1 x C points;
+//   * a lane holds 16 points in the row pass and in pass 3 at N1 = 512 (64 VGPRs of data), 32 points in the column
+//     passes at N1 = 1024 / 2048 (128 VGPRs of data, 2 waves per SIMD);
 //   * the LDS is only the exchange buffer between two Stockham stages, and real and imaginary parts cross it one
-//     after the other: 8 bytes per point, 16 KB per wave;
-//   * a row is transformed by ONE wave: 2048 = 16 x 8 x 16, two exchanges, no workgroup barrier at all (the LDS
-//     executes a wave's accesses in order); the two rows (k1, N1 - k1) whose bins pair up in the real-FFT unpacking
-//     belong to two waves of a workgroup, the second of which computes its last butterflies with mirrored lane
-//     indices so that both members of a bin pair sit in the same lane -- the pairing costs two barriers and one
-//     16 KB round trip per wave;
-//   * twice the rows in flight per CU (8 instead of 4) and 32 independent points per lane between dependent steps.
+//     after the other: 8 bytes per point;
+//   * a row of N2 = 2048 points is transformed by two waves: 2048 = 16 x 8 x 16, two exchanges; the two rows
+//     (k1, N1 - k1) whose bins pair up in the real-FFT unpacking belong to the two halves of a workgroup, the second
+//     of which computes its last butterflies with mirrored lane indices so that both members of a bin pair sit in
+//     the same lane -- the pairing costs two barriers and one round trip through the partner's buffer.
 //
-// Rows 0 and N1 / 2 (the self-paired ones) stay with k_fft_rows of fft_fused.hip.
+// Rows 0 and N1 / 2 (the self-paired ones) stay with k_fft_rows of fft_fused.hip, and so do the column passes of
+// unaligned timestreams and of the lengths without a kernel here (k_fft_cols).  The row pass with 32 points per lane
+// (one row per wave, two waves per SIMD) lost to the 16-point one and is gone: profiles/r05_a section 3.
 #include <hip/hip_runtime.h>
 
 #undef TOAST_FFT_PHASE_CLOCK
@@ -28,23 +28,6 @@
 
 namespace toast_hip {
 namespace fused_fft {
-
-// Experimental build (TOAST_HIP_EXTRA_FLAGS=-DTOAST_FFT_REG_CLOCK): lane 0 of every wave adds the 100 MHz wall-clock
-// ticks between phase boundaries to g_reg_ticks (read with toast_hip_fft_reg_ticks).
-#if defined(TOAST_FFT_REG_CLOCK)
-__device__ unsigned long long g_reg_ticks[16];
-# define RCLK_DECL unsigned long long rc_t = wall_clock64()
-# define RCLK_MARK(i)                                                              \
-    do {                                                                           \
-        asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");                \
-        const unsigned long long rc_n = wall_clock64();                            \
-        if ((threadIdx.x & 63) == 0) atomicAdd(&g_reg_ticks[i], rc_n - rc_t);      \
-        rc_t = rc_n;                                                               \
-    } while (0)
-#else
-# define RCLK_DECL
-# define RCLK_MARK(i)
-#endif
 
 template <>
 struct Log2<32> {
@@ -214,18 +197,6 @@ __device__ __forceinline__ void reg_exchange(double2 (&v)[P], double * smd, int 
     }
 }
 
-// One row of 2048 points in one wave, 32 points per lane: 2048 = 16 x 8 x 16.  In: v[i] = element l + 64 i, or
-// (mirror_in) the layout a mirrored last stage left; out: the same, or (mirror_out) v[b + 2 j] = element
-// 127 - (l + 64 b) + 128 j.
-__device__ __forceinline__ void row_fft_2048(double2 (&v)[32], double * smd, int l, bool mirror_in, bool mirror_out,
-                                             const double2 * __restrict__ s_w) {
-    reg_butterflies<11, 32, 16>(v, l, mirror_in, 0, s_w);
-    reg_exchange<11, 32, 16, 8, 0>(v, smd, l, mirror_in, false);
-    reg_butterflies<11, 32, 8>(v, l, false, 4, s_w + 128);
-    reg_exchange<11, 32, 8, 16, 4>(v, smd, l, false, mirror_out);
-    reg_butterflies<11, 32, 16>(v, l, mirror_out, 7, nullptr);
-}
-
 // The kernel tables of one detector as the row pass keeps them in LDS (KTabSel<true>::make's layout), packed once per
 // call so that a workgroup copies one contiguous block with 16-byte loads.
 __global__ void k_pack_tables(const Params p, char * blob) {
@@ -267,125 +238,10 @@ __device__ __forceinline__ int kernel_interval_pre(const KTab<H> & t, int k, int
 // the analytic kernel has no intervals
 __device__ __forceinline__ int kernel_interval_pre(const PoleTab &, int, int, int, int) { return 0; }
 
-// pass 2 for the row pairs (g, N1 - g), 0 < g < N1 / 2, N2 = 2048: 256 threads = two pairs, one row per wave
-template <bool TLDS, bool CPLX>
-__global__ __launch_bounds__(256, 2) void k_fft_rows_reg(const Params p) {
-    extern __shared__ double2 sm[];           // 4 x 16 KB exchange buffers, then the kernel tables
-    const int tid = threadIdx.x;
-    const int l = tid & 63;
-    const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int side = w & 1;                   // 0: row g, 1: row N1 - g
-    const int b = blockIdx.y;
-    const int n1 = 1 << p.log_n1;
-    const int64_t m = (int64_t)n1 << 11;
-    int g = 1 + 2 * (int)blockIdx.x + (w >> 1);
-    const bool live = g < (n1 >> 1);
-    if (!live) g = (n1 >> 1) - 1;             // an odd pair out repeats its neighbour's work and stores nothing
-    const int64_t row = side ? (n1 - g) : g;
-    RCLK_DECL;
-    const int64_t kern = p.per_det ? (int64_t)(p.det0 + b) : 0;
-    double2 * s_w = sm + 4 * (kPadRow / 2);                       // 144 stage twiddles
-    char * s_tab = reinterpret_cast<char *>(s_w + 144);           // the kernel tables
-    // Everything the kernel will ever ask global memory for is asked for here, together: the tables, then the row.
-    uint4 tc[4];
-    const int n_chunk = TLDS ? (p.tab_bytes >> 4) : 0;
-    if (TLDS) {
-        const uint4 * __restrict__ g_tab = reinterpret_cast<const uint4 *>(p.tab_blob + kern * (int64_t)p.tab_bytes);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) tc[j] = (tid + 256 * j < n_chunk) ? g_tab[tid + 256 * j] : make_uint4(0, 0, 0, 0);
-    }
-    const double2 tws = (tid < 144) ? p.wrow[tid] : make_double2(0.0, 0.0);
-    int lo_g = __builtin_amdgcn_readfirstlane(p.knot_hint0[g]);
-    int lo_ng = __builtin_amdgcn_readfirstlane(p.knot_hint0[n1 - g]);
-    // w_N^k = w_N^g w_4096^q = (w_N^g w_4096^l) w_64^r for bin k = g + N1 q, q = l + 64 r
-    double2 w0 = cmul(tw_big(p.tb, g), p.tb.wtile[l]);
-    const double2 * __restrict__ rowp = p.work + (int64_t)b * m + (row << 11) + l;
-    double2 v[32];
-#pragma unroll
-    for (int i = 0; i < 32; ++i) v[i] = rowp[64 * i];
-    if (TLDS) {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            if (tid + 256 * j < n_chunk) reinterpret_cast<uint4 *>(s_tab)[tid + 256 * j] = tc[j];
-        }
-    }
-    if (tid < 144) s_w[tid] = tws;
-    asm volatile("" : "+v"(w0.x), "+v"(w0.y), "+s"(lo_g), "+s"(lo_ng));   // here, not where they are first used
-    __syncthreads();
-    KTab<typename KTabSel<TLDS>::H> kt;
-    if constexpr (TLDS) {
-        const int n_coef = 4 * (p.n_knot - 1);
-        const double * s_knots = reinterpret_cast<const double *>(s_tab);
-        kt.knots = s_knots;
-        kt.mc = s_knots + p.n_knot;
-        kt.ac = CPLX ? kt.mc + n_coef : nullptr;
-        kt.hint = reinterpret_cast<const typename KTabSel<TLDS>::H *>(kt.mc + n_coef * (CPLX ? 2 : 1));
-        kt.hint0 = p.knot_hint0;
-        kt.log_n1 = p.log_n1;
-        kt.fstep = p.fstep;
-    } else {
-        kt = KTabSel<false>::make(p, kern, nullptr, tid, 256);
-        if (!CPLX) kt.ac = nullptr;
-    }
-    double2 * own = sm + w * (kPadRow / 2);
-    double2 * oth = sm + (w ^ 1) * (kPadRow / 2);
-    double * smd = reinterpret_cast<double *>(own);
-    RCLK_MARK(0);       // entry -> row and tables landed
-
-    {
-        row_fft_2048(v, smd, l, false, side != 0, s_w);
-        RCLK_MARK(1);       // forward transform
-
-        // Bin k = g + N1 q of row g (element q = l + 64 r of wave `side 0`: register r) pairs with bin M - k = element
-        // 2047 - q of row N1 - g, which the mirrored last stage of wave `side 1` left in the same lane, in register
-        // 30 + 2 (r & 1) - r.  Each wave works on ITS registers 0 .. 15 and hands registers 16 .. 31 to its partner
-        // through its own buffer: own register i meets the partner's register 16 + jj, jj = 14 + 2 (i & 1) - i, on both
-        // sides, so one section of code serves both waves (the roles za / zb are selected by `side`).
-#pragma unroll
-        for (int j = 0; j < 16; ++j) own[j * 64 + l] = v[16 + j];
-        __syncthreads();
-        RCLK_MARK(2);       // hand-over + barrier
-#pragma unroll
-        for (int i = 0; i < 16; ++i) {
-            const int jj = 14 + 2 * (i & 1) - i;
-            const int r = side ? (16 + jj) : i;            // register of row g = the element's high bits
-            const int k = g + n1 * (l + 64 * r);
-            const double2 part = oth[jj * 64 + l];
-            const double2 mine = v[i];
-            // (component-wise selects: a conditional expression on the structs selects their ADDRESSES and pushes the
-            // whole register array into scratch memory)
-            double2 za = make_double2(side ? part.x : mine.x, side ? part.y : mine.y);
-            double2 zb = make_double2(side ? mine.x : part.x, side ? mine.y : part.y);
-            const double2 w64 = make_double2(side ? kC64[16 + jj] : kC64[i], side ? -kS64[16 + jj] : -kS64[i]);
-            const double2 wk = cmul(w0, w64);
-            pair_update_reg(za, zb, false, wk, kernel_eval(kt, kernel_interval_pre(kt, k, g, lo_g, lo_ng), k),
-                            kernel_eval(kt, kernel_interval_pre(kt, (int)m - k, g, lo_g, lo_ng), (int)m - k), p.deconvolve);
-            v[i] = make_double2(side ? zb.x : za.x, side ? zb.y : za.y);
-            oth[jj * 64 + l] = make_double2(side ? za.x : zb.x, side ? za.y : zb.y);
-        }
-        RCLK_MARK(3);       // bin pairs
-        __syncthreads();
-#pragma unroll
-        for (int j = 0; j < 16; ++j) v[16 + j] = own[j * 64 + l];
-        RCLK_MARK(4);       // barrier + take-back
-    }
-    row_fft_2048(v, smd, l, side != 0, false, s_w);
-    RCLK_MARK(5);       // inverse transform
-
-    if (live) {
-        // the addresses are formed again from an opaque copy of the lane index: kept alive from the loads, 32 of them
-        // would take 64 of the lane's registers through the whole kernel
-        double2 * __restrict__ outp = p.work + (int64_t)b * m + (row << 11) + opaque_vgpr(l);
-#pragma unroll
-        for (int i = 0; i < 32; ++i) outp[64 * i] = v[i];
-    }
-    RCLK_MARK(6);       // stores
-}
-
-// The same pass with SIXTEEN points per lane: a row of 2048 in two waves, the row pair (g, N1 - g) in one workgroup of 256
-// threads.  Half the registers (64 of data), 35 KB of exchange buffers per workgroup instead of 70: three workgroups per CU
-// = three waves per SIMD where k_fft_rows_reg has two -- the pass is bound by how badly two waves per SIMD overlap their
-// waits (profiles/r05_a section 3), not by instructions or bytes.  Element q = l + 128 i of a row sits in lane l (0 .. 127 of
+// Pass 2 for the row pairs (g, N1 - g), 0 < g < N1 / 2, N2 = 2048, SIXTEEN points per lane: a row of 2048 in two waves, the
+// row pair in one workgroup of 256 threads.  64 registers of data and 35 KB of exchange buffers per workgroup: three or four
+// workgroups per CU -- the pass is bound by how badly few waves per SIMD overlap their waits (profiles/r05_a section 3:
+// 32 points per lane, two waves per SIMD, was slower), not by instructions or bytes.  Element q = l + 128 i of a row sits in lane l (0 .. 127 of
 // the row's half of the workgroup), register i; the mirrored last stage of the second row leaves element 127 - l + 128 j in
 // register j, so bin q of row g meets bin 2047 - q of row N1 - g in the same lane, register 15 - i.  The exchanges
 // synchronise with workgroup barriers (both rows run the same sequence).
@@ -398,7 +254,7 @@ __device__ __forceinline__ void row_fft_2048_p16(double2 (&v)[16], double * smd,
     reg_butterflies<11, 16, 16>(v, l, mirror_out, 7, nullptr);
 }
 
-// HG (the default; TOAST_HIP_FFT_HINTS=lds turns it off): the 16-bit interval hints (4 KB, two look-ups per bin, the same for
+// HG (always set when TLDS is; only those instantiations are launched): the 16-bit interval hints (4 KB, two look-ups per bin, the same for
 // every workgroup: cache resident) stay in global memory -- 40 172 B of LDS instead of 44 272: FOUR workgroups per CU
 // instead of three (cfg-3 call 18.59-18.65 -> 18.33-18.43 ms, the 2^23 call 42.5-42.7 -> 41.5 ms; profiles/r06_c)
 // POLE (with TLDS = CPLX = HG = false): the analytic single-pole kernel, PoleTab of fft_device.hpp -- no table copy, no
@@ -506,8 +362,8 @@ __global__ __launch_bounds__(256, 3) void k_fft_rows_reg16(const Params p) {
 // Tile = N1 rows x C columns = 2^LT points, 32 per lane, T = 2^LT / 32 threads; element e = k1 C + c sits in thread
 // e mod T, register e / T, so a lane owns ONE column (c = tid mod C) and a load / store instruction of a wave covers
 // 64 / C consecutive rows of C adjacent columns: pieces of 16 C bytes.
-//   n_fft 2^21:  N1 =  512, C = 8 (128-byte pieces), LT = 12, 128 threads, 512 = 16 x 4 x 8 (fft_fused.hip: C = 8);
-//                pass 3: 256 threads of 16 points (k_fft_cols_inv16)
+//   n_fft 2^21:  N1 =  512, C = 8 (128-byte pieces), LT = 12, 512 = 16 x 4 x 8 (fft_fused.hip: C = 8); pass 3 only:
+//                256 threads of 16 points (k_fft_cols_inv16)
 //   n_fft 2^22:  N1 = 1024, C = 8 (128-byte pieces), LT = 13, 256 threads, 1024 = 16 x 4 x 16 (fft_fused.hip: C = 4)
 //   n_fft 2^23:  N1 = 2048, C = 4 ( 64-byte pieces), LT = 13, 256 threads, 2048 = 16 x 8 x 16 (fft_fused.hip: C = 2:
 //                every 128-byte line is shared by four tiles and crosses HBM 2.3 times, profiles/r04_c section 6)
@@ -809,7 +665,7 @@ __global__ __launch_bounds__((1 << ColPlan<LOGN>::LT) / 32, (INV ? 2 : TOAST_FFT
 }
 
 // Pass 3 with SIXTEEN points per lane, for N1 = 512 (n_fft 2^21): the 4096-point tile in 256 threads, 120 registers, 35 KB
-// of LDS: four workgroups = four waves per SIMD, where k_fft_cols_reg<9, true> has two (2024 against 2204 us per 512
+// of LDS: four workgroups = four waves per SIMD, where 32 points per lane (k_fft_cols_reg) had two (2024 against 2204 us per 512
 // detectors; the LDS-tile kernel: 2252).  At N1 = 1024 / 2048 the tile's exchange buffer (70 KB) allows two workgroups
 // either way and 16 points per lane lose (3175 against 2500 us at 2^23: profiles/r05_a section 10).
 template <int LOGN>
@@ -872,34 +728,8 @@ __global__ __launch_bounds__((1 << ColPlan<LOGN>::LT) / 16, 4) void k_fft_cols_i
 // ------------------------------------------------------------------------------------------
 bool rows_reg_supported(const Params & p) { return p.log_n2 == 11 && p.log_n1 >= 2; }
 
-// LDS of one workgroup of k_fft_rows_reg: four exchange buffers + the kernel tables (tab_bytes, 0: tables in global memory)
-size_t rows_reg_lds(size_t tab_bytes) { return 4 * kPadRow * sizeof(double) + 144 * sizeof(double2) + tab_bytes; }
-// two workgroups per CU: 2 x (68 KB of exchange buffers + 2.25 KB of twiddles + tables) <= 160 KB
+// largest kernel tables the register row pass copies into LDS (three 16-byte chunks per thread, with room to spare)
 constexpr size_t kTabLdsReg = 9 * 1024 + 512;
-
-void launch_rows_reg(const Params & p, unsigned n_det, bool tab_lds, size_t tab_bytes, hipStream_t st) {
-    static bool attr_set = false;
-    if (!attr_set) {
-        const int most = (int)rows_reg_lds(kTabLdsReg);
-        auto set = [&](const void * fn) { TH_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, most)); };
-        set(reinterpret_cast<const void *>(&k_fft_rows_reg<true, false>));
-        set(reinterpret_cast<const void *>(&k_fft_rows_reg<true, true>));
-        set(reinterpret_cast<const void *>(&k_fft_rows_reg<false, false>));
-        set(reinterpret_cast<const void *>(&k_fft_rows_reg<false, true>));
-        attr_set = true;
-    }
-    const int n_pair = (1 << p.log_n1) / 2 - 1;                  // row pairs g = 1 .. N1 / 2 - 1
-    if (n_pair <= 0) return;
-    const dim3 grid((unsigned)((n_pair + 1) / 2), n_det);
-    const bool cplx = p.ang_coef != nullptr;
-    if (tab_lds && p.tab_blob != nullptr && tab_bytes <= kTabLdsReg) {
-        if (cplx) hipLaunchKernelGGL((k_fft_rows_reg<true, true>), grid, dim3(256), rows_reg_lds(tab_bytes), st, p);
-        else hipLaunchKernelGGL((k_fft_rows_reg<true, false>), grid, dim3(256), rows_reg_lds(tab_bytes), st, p);
-    } else {
-        if (cplx) hipLaunchKernelGGL((k_fft_rows_reg<false, true>), grid, dim3(256), rows_reg_lds(0), st, p);
-        else hipLaunchKernelGGL((k_fft_rows_reg<false, false>), grid, dim3(256), rows_reg_lds(0), st, p);
-    }
-}
 
 // k_fft_rows_reg16: one row pair per workgroup; LDS = two row buffers + twiddles + tables (<= 12 KB: three 16-byte chunks per thread)
 size_t rows_reg16_lds(size_t tab_bytes) { return 2 * kPadRow * sizeof(double) + 144 * sizeof(double2) + tab_bytes; }
@@ -909,8 +739,6 @@ void launch_rows_reg16(const Params & p, unsigned n_det, bool tab_lds, size_t ta
     if (!attr_set) {
         const int most = (int)rows_reg16_lds(kTabLdsReg);
         auto set = [&](const void * fn) { TH_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, most)); };
-        set(reinterpret_cast<const void *>(&k_fft_rows_reg16<true, false>));
-        set(reinterpret_cast<const void *>(&k_fft_rows_reg16<true, true>));
         set(reinterpret_cast<const void *>(&k_fft_rows_reg16<false, false>));
         set(reinterpret_cast<const void *>(&k_fft_rows_reg16<false, true>));
         set(reinterpret_cast<const void *>(&k_fft_rows_reg16<true, false, true>));
@@ -921,18 +749,11 @@ void launch_rows_reg16(const Params & p, unsigned n_det, bool tab_lds, size_t ta
     if (n_pair <= 0) return;
     const dim3 grid((unsigned)n_pair, n_det);
     const bool cplx = p.ang_coef != nullptr;
-    // (TOAST_HIP_FFT_HINTS=lds: the hints in LDS with the other tables, three workgroups per CU -- rounds 5-6a)
-    static const bool hints_global = [] {
-        const char * e = std::getenv("TOAST_HIP_FFT_HINTS");
-        return !(e != nullptr && std::string(e) == "lds");
-    }();
-    if (hints_global && tab_lds && p.tab_blob != nullptr && tab_bytes <= kTabLdsReg) {
+    if (tab_lds && p.tab_blob != nullptr && tab_bytes <= kTabLdsReg) {
+        // knots and cubics in LDS, the 16-bit hints in global memory (HG)
         const size_t lds = rows_reg16_lds((size_t)p.tab_copy_bytes);
         if (cplx) hipLaunchKernelGGL((k_fft_rows_reg16<true, true, true>), grid, dim3(256), lds, st, p);
         else hipLaunchKernelGGL((k_fft_rows_reg16<true, false, true>), grid, dim3(256), lds, st, p);
-    } else if (tab_lds && p.tab_blob != nullptr && tab_bytes <= kTabLdsReg) {
-        if (cplx) hipLaunchKernelGGL((k_fft_rows_reg16<true, true>), grid, dim3(256), rows_reg16_lds(tab_bytes), st, p);
-        else hipLaunchKernelGGL((k_fft_rows_reg16<true, false>), grid, dim3(256), rows_reg16_lds(tab_bytes), st, p);
     } else {
         if (cplx) hipLaunchKernelGGL((k_fft_rows_reg16<false, true>), grid, dim3(256), rows_reg16_lds(0), st, p);
         else hipLaunchKernelGGL((k_fft_rows_reg16<false, false>), grid, dim3(256), rows_reg16_lds(0), st, p);
@@ -953,13 +774,13 @@ void launch_rows_reg16_pole(const Params & p, unsigned n_det, hipStream_t st) {
                        rows_reg16_lds(0), st, p);
 }
 
-// column passes in registers: N2 = 2048, N1 = 512 / 1024 / 2048, aligned timestreams
-// (n_fft 2^21, N1 = 512, has a kernel too -- TOAST_HIP_FFT_COLS=reg9 -- but there the LDS-tile kernels already move
-// 128-byte pieces and pad their input in ONE memory round trip where pass 1 of this file needs three: 2.85 against 4.2 ms)
+// column passes in registers: N2 = 2048, N1 = min_log_n1 .. 2048, aligned timestreams.  Passes 1 and 3 at N1 = 1024 / 2048
+// (k_fft_cols_reg), pass 3 alone at N1 = 512 (k_fft_cols_inv16): there the LDS-tile kernel of pass 1 already moves
+// 128-byte pieces and pads its input in ONE memory round trip where a register kernel needed three (2.85 against 4.2 ms)
 bool cols_reg_supported(const Params & p, int min_log_n1) {
     return p.log_n2 == 11 && p.log_n1 >= min_log_n1 && p.log_n1 <= 11 && p.aligned;
 }
-int cols_reg_log_c(int log_n1) { return (log_n1 == 9 ? 12 : 13) - log_n1; }
+int cols_reg_log_c(int log_n1) { return 13 - log_n1; }      // columns per tile of k_fft_cols_reg (N1 = 1024 / 2048)
 
 // stage twiddles of the column transform of length 2^log_n1 in the kernel's LDS order (host; `out` gets the exponents
 // e of w_n^e, n = 2^log_n1); returns their number
@@ -994,20 +815,6 @@ static void launch_cols_reg_n(const Params & p, bool inv, unsigned n_det, hipStr
         attr_set = true;
     }
     const unsigned n_tiles = (unsigned)(2048 >> (LT - LOGN));
-    if constexpr (LOGN == 9) {
-        if (inv) {
-            const size_t lds16 = ((size_t)(1 << LT) + (size_t)(1 << (LT - 4))) * sizeof(double) +
-                                 (size_t)col_tw_count<LOGN>() * sizeof(double2);
-            static bool attr16 = false;
-            if (!attr16) {
-                TH_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_fft_cols_inv16<LOGN>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds16));
-                attr16 = true;
-            }
-            hipLaunchKernelGGL((k_fft_cols_inv16<LOGN>), dim3(n_tiles, n_det), dim3((1 << LT) / 16), lds16, st, p);
-            return;
-        }
-    }
     if (inv) {
         hipLaunchKernelGGL((k_fft_cols_reg<LOGN, true>), dim3(n_tiles, n_det), dim3(T), lds, st, p);
     } else if (p.fwd_seq != nullptr) {
@@ -1017,30 +824,34 @@ static void launch_cols_reg_n(const Params & p, bool inv, unsigned n_det, hipStr
     }
 }
 
+// pass 3 at N1 = 512
+static void launch_cols_inv16(const Params & p, unsigned n_det, hipStream_t st) {
+    constexpr int LOGN = 9;
+    constexpr int LT = ColPlan<LOGN>::LT;
+    const size_t lds16 = ((size_t)(1 << LT) + (size_t)(1 << (LT - 4))) * sizeof(double) +
+                         (size_t)col_tw_count<LOGN>() * sizeof(double2);
+    static bool attr16 = false;
+    if (!attr16) {
+        TH_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_fft_cols_inv16<LOGN>),
+                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds16));
+        attr16 = true;
+    }
+    const unsigned n_tiles = (unsigned)(2048 >> (LT - LOGN));
+    hipLaunchKernelGGL((k_fft_cols_inv16<LOGN>), dim3(n_tiles, n_det), dim3((1 << LT) / 16), lds16, st, p);
+}
+
+// the lengths of cols_reg_supported(p, 10) for pass 1 (inv = false), of cols_reg_supported(p, 9) for pass 3
 void launch_cols_reg(const Params & p, bool inv, unsigned n_det, hipStream_t st) {
-    if (p.log_n1 == 9) launch_cols_reg_n<9>(p, inv, n_det, st);
+    if (p.log_n2 != 11 || !p.aligned) fail_arg("fft: register column kernels need N2 = 2048 and aligned timestreams");
+    if (inv && p.log_n1 == 9) launch_cols_inv16(p, n_det, st);
     else if (p.log_n1 == 10) launch_cols_reg_n<10>(p, inv, n_det, st);
-    else launch_cols_reg_n<11>(p, inv, n_det, st);
+    else if (p.log_n1 == 11) launch_cols_reg_n<11>(p, inv, n_det, st);
+    else fail_arg("fft: no register column kernel for this length");
 }
 
 void pack_tables(const Params & p, char * blob, int64_t n_kern, hipStream_t st) {
     hipLaunchKernelGGL(k_pack_tables, dim3((unsigned)n_kern), dim3(256), 0, st, p, blob);
 }
 
-#if defined(TOAST_FFT_REG_CLOCK)
-void reg_ticks(unsigned long long * out, int reset) {
-    TH_HIP(hipDeviceSynchronize());
-    TH_HIP(hipMemcpyFromSymbol(out, HIP_SYMBOL(g_reg_ticks), 16 * sizeof(unsigned long long)));
-    if (reset) {
-        unsigned long long z[16] = {0};
-        TH_HIP(hipMemcpyToSymbol(HIP_SYMBOL(g_reg_ticks), z, sizeof(z)));
-    }
-}
-#endif
-
 }  // namespace fused_fft
 }  // namespace toast_hip
-
-#if defined(TOAST_FFT_REG_CLOCK)
-extern "C" void toast_hip_fft_reg_ticks(unsigned long long * out, int reset) { toast_hip::fused_fft::reg_ticks(out, reset); }
-#endif

@@ -37,29 +37,6 @@ def set_points(rows=0, cols_fwd=0, cols_inv=0):
     capi.lib().toast_hip_fft_points(C.c_int(int(rows)), C.c_int(int(cols_fwd)), C.c_int(int(cols_inv)))
 
 
-def set_rows_mode(mode="reg"):
-    """Row pass of the fused kernels: "reg" (default: tile in registers, 16 points per lane = a row in two waves, three
-    workgroups per CU; fft_reg.hip), "reg32" (32 points per lane, one row per wave), "pair" (row pair in one 64 KB LDS tile)
-    or "split" (one row per 32 KB LDS tile; experiment)."""
-    capi.lib().toast_hip_fft_rows_split(C.c_int({"pair": 0, "lds": 0, "split": 1, "reg": 2, "reg32": 3}[mode]))
-
-
-def set_cols_mode(mode="reg"):
-    """Column passes of the fused kernels: "reg" (default: tile in registers for n_fft 2^22 and 2^23), "reg9" (for 2^21
-    too) or "lds" (csrc/fft_fused.hip for every length)."""
-    capi.lib().toast_hip_fft_cols_reg(C.c_int({"lds": 0, "reg": 1, "reg9": 2}[mode]))
-
-
-def set_rows_split(split=True):
-    """Older spelling: the "split" row pass (True) or the default one (False)."""
-    set_rows_mode("split" if split else "reg")
-
-
-def set_rows_n2(n2=2048):
-    """Row length N2 of the four-step factorisation of the fused kernels: 2048 or 1024 (toast_hip_fft_rows_n2)."""
-    capi.lib().toast_hip_fft_rows_n2(C.c_int(int(n2)))
-
-
 def pipeline_bytes_per_sample(n_samp):
     """HBM bytes per timestream sample moved by the passes of the implementation in use."""
     fn = capi.lib().toast_hip_fft_pipeline_bytes
@@ -344,9 +321,9 @@ def convolve(raw, rate, flags=None, flag_mask=None, kernel_freq=None, kernels=No
 
     ``kernel_func`` may be a :class:`SinglePole`: the analytic time-constant kernel, evaluated on the device
     (reference fft.py:318-336 with the kernel function of ops/time_constant.py:155-168).  ``deconvolve=True`` then
-    divides by whatever the object describes, as the reference would.  Such a call always runs the default row passes
-    of the fused kernels: ``set_rows_mode`` / ``set_rows_n2`` / the row entry of ``set_points`` do not apply to it
-    (``select`` does).  Any other callable raises: the reference evaluates those on the host.
+    divides by whatever the object describes, as the reference would.  Such a call always runs the 8-point row pass
+    of the fused kernels: the row entry of ``set_points`` does not apply to it (``select`` does).  Any other callable
+    raises: the reference evaluates those on the host.
     """
     pole = None
     if kernel_func is not None:
