@@ -1,6 +1,11 @@
 """Shared by test_sim_noise_host.py and test_gpu_sim_noise.py: the fixture tests/golden/sim_noise.npz (the reference's
 own compiled random streams and PSD interpolation, tests/golden/make_golden_sim_noise.py), small observations with a
-noise model, and the periodogram check of a simulated spectrum."""
+noise model, and the periodogram check of a simulated spectrum.
+
+Shared by test_sim_noise_grid_host.py, test_gpu_sim_noise_grid.py and tests/golden/make_golden_sim_noise_grid.py: the
+grid of PSD tables, transform lengths and start samples below, the long double restatements of the interpolation and
+of a whole timestream, and the per-case bounds from tests/golden/sim_noise_grid.npz."""
+import functools
 import os
 
 import numpy as np
@@ -95,3 +100,193 @@ def spectrum_check(ts, interp_scale):
         out.append((k0, k1 - 1, float(np.mean(ratio[k0:k1])), 1.0 / np.sqrt((k1 - k0) * n_det)))
         k0 = k1
     return out
+
+
+# ------------------------------------------------------------------------------------------ grid and edges
+# PSD tables below, at and above the size the kernels keep in LDS (768 points), the two smallest tables, transform
+# lengths from 4 to 2^15 (below one block of the spectrum grid, the step from one block to two, three oversampling
+# factors, one crop chunk against two) and a start sample whose counter needs 43 bits.
+GRID_RATE = 37.0
+GRID_NBINNED = (2, 3, 72, 767, 768, 769, 2000)
+GRID_LENGTHS = ((1, 2), (2, 2), (3, 2), (511, 2), (512, 2), (1023, 1), (1024, 2), (1025, 3), (4095, 2), (4096, 1),
+                (4097, 4))                                   # (samples, oversample)
+GRID_FIRST = (0, (1 << 40) + 3)
+GRID_IDS = (2, 7, 1, 5)                                      # realization, telescope, component, obsindx
+GRID_DET = (3, 4294967295)                                   # stream indices of the two simulated streams
+TIE_LENGTH = (3000, 2)
+LONG_LENGTH = (1048577 + 4096, 2)                            # 258 crop chunks, fftlen 2^22
+LONG_PSD_ROW = 2
+LONG_IDS = (1, 3, 0, 8, 17, 5)                               # realization, telescope, component, obsindx, detindx, firstsamp
+
+
+def fft_length(samples, oversample):
+    fftlen = 2
+    while fftlen <= oversample * samples:
+        fftlen *= 2
+    return fftlen
+
+
+def red_psd(freq, zeros):
+    psd = 1e-4 * (1.0 + (0.1 / np.maximum(freq, 1e-6)) ** 1.5)
+    for z in zeros:
+        if 0 <= z < freq.size:
+            psd[z] = 0.0
+    return psd
+
+
+def grid_psds(n_binned):
+    """(freq [n_binned], psds [n][n_binned]): the fixture's grid with its four rows at 72 points; otherwise 0 and a
+    logarithmic grid up to rate / 2 with a white PSD and a red one with zero bins."""
+    if n_binned == 72:
+        return GOLD["psd_freq"], GOLD["psd_psds"]
+    if n_binned == 2:
+        freq = np.array([0.0, GRID_RATE / 2])
+    else:
+        freq = np.concatenate([[0.0], np.logspace(np.log10(1e-5), np.log10(GRID_RATE / 2), n_binned - 1)])
+        freq[-1] = GRID_RATE / 2
+    return freq, np.array([np.full(n_binned, 0.3), red_psd(freq, (0, 5, 40, n_binned - 3))])
+
+
+def tie_grid():
+    """(freq, psds, k): PSD frequencies that are transform bins k of the tie length exactly, so that
+    log10(freq + inc) on the host is bit for bit the x of bin k."""
+    fftlen = fft_length(*TIE_LENGTH)
+    inc = GRID_RATE / (fftlen - 1)
+    k = np.unique(np.concatenate([[0], np.round(np.logspace(0.0, np.log10(fftlen // 2 - 1), 60))])).astype(np.int64)
+    freq = np.concatenate([inc * k.astype(np.float64), [GRID_RATE / 2]])
+    return freq, np.array([np.full(freq.size, 0.3), red_psd(freq, (0, 7))]), k
+
+
+def grid_bins(n_psd):
+    """The bins of a case the fixture keeps: the first 64, every 8th and the last."""
+    return np.unique(np.concatenate([np.arange(min(64, n_psd)), np.arange(0, n_psd, 8), [n_psd - 1]]))
+
+
+def grid_cases():
+    return [(nb, s, o) for nb in GRID_NBINNED for s, o in GRID_LENGTHS]
+
+
+def case_key(n_binned, samples, oversample):
+    return f"{n_binned}_{samples}_{oversample}"
+
+
+@functools.lru_cache(maxsize=None)
+def grid_gold():
+    return np.load(os.path.join(HERE, "golden", "sim_noise_grid.npz"), allow_pickle=False)
+
+
+def scale_bound(key):
+    """4 x the larger of the reference's distance to the long double evaluation on the fixture's grid and on this one."""
+    return 4.0 * max(float(GOLD["scale_ref_err"]), float(grid_gold()["scale_err_" + key]))
+
+
+def ts_bound(key):
+    """10 x the larger of the reference's distance to the long double stream on the fixture's cases and on this one."""
+    return 10.0 * max(float(GOLD["ts_ref_err"]), float(grid_gold()["ts_err_" + key]))
+
+
+def noise_keys(realization, telescope, component, obsindx, detindx):
+    return realization * 4294967296 + telescope * 65536 + component, obsindx * 4294967296 + detindx
+
+
+# ---- long double restatements
+def interp_longdouble(rate, samples, oversample, freq, psd):
+    """Interpolated amplitudes of one PSD, every step after the double inputs in long double (as the function of this
+    name in make_golden_sim_noise.py, which writes the fixture this module loads and so cannot import it)."""
+    L = np.longdouble
+    fftlen = fft_length(samples, oversample)
+    psdlen = fftlen // 2 + 1
+    norm = L(rate) * L(psdlen - 1)
+    inc = L(np.float64(rate) / np.float64(fftlen - 1))
+    f, p = np.asarray(freq).astype(L), np.asarray(psd).astype(L)
+    logfreq = np.log10(f + inc)
+    shift = L(np.float64(0.01) * np.min(psd[psd != 0]))
+    logpsd = np.log10(np.sqrt(p * norm) + shift)
+    x = np.log10(inc * np.arange(psdlen).astype(L) + inc)
+    ibin = np.clip(np.searchsorted(logfreq[1:], x, side="left"), 0, f.size - 2)
+    r = (x - logfreq[ibin]) / (logfreq[ibin + 1] - logfreq[ibin])
+    out = L(10) ** (logpsd[ibin] + r * (logpsd[ibin + 1] - logpsd[ibin])) - shift
+    out[0] = 0
+    return out
+
+
+def scale_distance(got, want):
+    """Largest distance of interpolated amplitudes to ``want`` relative to the largest amplitude of ``want``."""
+    L = np.longdouble
+    return float(np.max(np.abs(np.asarray(got).astype(L) - np.asarray(want).astype(L))) / np.max(want))
+
+
+def timestream_longdouble(gauss, scale, samples):
+    """(stream, rms): the unit Gaussians ``gauss`` [fftlen] times the amplitudes ``scale`` [fftlen / 2 + 1] as a
+    half-complex spectrum, its inverse transform, the middle ``samples`` less their mean -- all in long double -- and
+    the rms of the full transform, the measure of the stream's distances (the rms of the cropped and de-meaned stream
+    is 0 at one sample and arbitrarily small at two or three of a red spectrum)."""
+    import scipy.fft
+
+    L = np.longdouble
+    n = gauss.size
+    half = n // 2
+    g, s = gauss.astype(L), np.asarray(scale).astype(L)
+    spec = np.zeros(half + 1, dtype=np.clongdouble)
+    spec.real[0] = g[0] * s[0]
+    spec.real[1:half] = g[1:half] * s[1:half]
+    spec.imag[1:half] = g[n - 1:half:-1] * s[1:half]
+    spec.real[half] = g[half] * s[half]
+    full = scipy.fft.irfft(spec, n)
+    assert full.dtype == L
+    off = (n - samples) // 2
+    x = full[off:off + samples]
+    return x - np.sum(x) / L(samples), float(np.sqrt(np.mean(full**2)))
+
+
+def host_gaussians(key1, key2, counter2, n):
+    """The library's host Gaussians: bit for bit the reference's (test_sim_noise_host.py)."""
+    from toast_amd import rng
+
+    return rng.random(n, key=(key1, key2), counter=(0, counter2), sampler="gaussian")
+
+
+@functools.lru_cache(maxsize=None)
+def grid_scale_longdouble(n_binned, samples, oversample):
+    """Long double amplitudes of every PSD of a grid case [n][n_psd]; computed once per process."""
+    freq, psds = grid_psds(n_binned)
+    out = np.array([interp_longdouble(GRID_RATE, samples, oversample, freq, p) for p in psds])
+    out.setflags(write=False)
+    return out
+
+
+def grid_stream_rows(n_binned):
+    """The PSD rows of the two simulated streams of a grid case: the last two."""
+    return (2, 3) if n_binned == 72 else (0, 1)
+
+
+def grid_streams_longdouble(n_binned, samples, oversample, firstsamp, gaussians=host_gaussians):
+    """(streams [2][samples] long double, rms [2]) of a grid case from ``gaussians(key1, key2, counter2, n)``."""
+    fftlen = fft_length(samples, oversample)
+    scale = grid_scale_longdouble(n_binned, samples, oversample)
+    out, rms = [], []
+    for det, row in zip(GRID_DET, grid_stream_rows(n_binned)):
+        key1, key2 = noise_keys(*GRID_IDS, det)
+        ts, r = timestream_longdouble(gaussians(key1, key2, firstsamp * oversample, fftlen), scale[row], samples)
+        out.append(ts)
+        rms.append(r)
+    return np.array(out), np.array(rms)
+
+
+def ts_distance(got, want, rms):
+    """Largest distance of streams [n][samples] to the long double ones relative to the full transforms' rms [n]."""
+    d = np.max(np.abs(np.atleast_2d(got).astype(np.longdouble) - np.atleast_2d(want)), axis=1)
+    return float(np.max(d / np.atleast_1d(rms)))
+
+
+@functools.lru_cache(maxsize=None)
+def long_stream_longdouble():
+    """(stream, rms) of the long case from the host Gaussians; computed once per process."""
+    samples, oversample = LONG_LENGTH
+    rz, tel, comp, obs, det, first = LONG_IDS
+    scale = interp_longdouble(GRID_RATE, samples, oversample, GOLD["psd_freq"], GOLD["psd_psds"][LONG_PSD_ROW])
+    key1, key2 = noise_keys(rz, tel, comp, obs, det)
+    ts, rms = timestream_longdouble(host_gaussians(key1, key2, first * oversample, fft_length(samples, oversample)),
+                                    scale, samples)
+    ts.setflags(write=False)
+    return ts, rms
