@@ -11,12 +11,12 @@ import sys as _sys
 
 import numpy as np
 
-from ..accel import accel_device_ptr, make_resident
+from ..accel import accel_device_ptr
 from ..data import defaults
 from ..pixels import PixelData
 from ..traits import Bool, Float, Instance, Int, Unicode
 from .arithmetic import Combine
-from .mapmaker_ops import Copy, CovarianceAndHits, Delete, ScanMask
+from .mapmaker_ops import Copy, CovarianceAndHits, Delete, ScanMask, device_det_flags, device_shared_flags
 from .mapmaker_solve import SolverLHS, SolverRHS, solve
 from .operator import Operator
 from .pipeline import Pipeline, uncached_detector_sets
@@ -639,14 +639,8 @@ class MapMaker(Operator):
             return
         sf = ob.detdata[solver_flags]
         n_samp = ob.n_local_samples
-        f_ptr, f_n, f_idx = 0, 0, np.zeros(len(dets), np.int32)
-        if binning.det_flags is not None:
-            src = make_resident(ob.detdata[binning.det_flags], binning.det_flags)
-            f_ptr, f_n, f_idx = accel_device_ptr(src.buffer), n_samp, src.indices(dets)
-        s_ptr, s_n = 0, 0
-        if binning.shared_flags is not None:
-            shared = make_resident(ob.shared[binning.shared_flags], binning.shared_flags)
-            s_ptr, s_n = accel_device_ptr(shared.data), n_samp
+        f_idx, f_ptr, f_n = device_det_flags(ob, binning.det_flags, dets, resident=True)
+        s_ptr, s_n = device_shared_flags(ob, binning.shared_flags, resident=True)
         view = binning.pixel_pointing.view
         capi.dev.combine_flags(accel_device_ptr(sf.buffer), sf.indices(dets), f_ptr, f_n, f_idx,
                                binning.det_flag_mask, s_ptr, s_n, binning.shared_flag_mask, n_samp,

@@ -18,6 +18,31 @@ from .pipeline import Pipeline, uncached_detector_sets
 _IMPLS = [ImplementationType.DEFAULT, ImplementationType.COMPILED]
 
 
+def device_g2l(data, key, dist):
+    """``dist.global_submap_to_local`` as a SharedData kept in ``data`` under ``key``, resident on the device."""
+    key = "_g2l_" + key
+    if key not in data:
+        data[key] = SharedData(dist.global_submap_to_local, "g2l")
+    return make_resident(data[key], "g2l")
+
+
+def device_det_flags(ob, key, dets, resident=False):
+    """(rows, device pointer, row length) of the detector flags ``key`` of ``dets``; without flags (zeros, 0, 0).
+    ``resident``: make them resident here -- otherwise whoever staged the caller's inputs (the Pipeline) has."""
+    if key is None:
+        return np.zeros(len(dets), np.int32), 0, 0
+    fd = make_resident(ob.detdata[key], key) if resident else ob.detdata[key]
+    return fd.indices(dets), accel_device_ptr(fd.buffer), ob.n_local_samples
+
+
+def device_shared_flags(ob, key, resident=False):
+    """(device pointer, length) of the shared flags ``key``, (0, 0) without; ``resident`` as for the detector flags."""
+    if key is None:
+        return 0, 0
+    sf = make_resident(ob.shared[key], key) if resident else ob.shared[key]
+    return accel_device_ptr(sf.data), ob.n_local_samples
+
+
 class ScanMap(Operator):
     """Scan a map into detector timestreams: ``tod (+|-)= sum_k w_k map[pix, k]``."""
 
@@ -131,10 +156,7 @@ class ScanMask(Operator):
 
                 for obj, nm in ((pd, self.pixels), (fd, self.det_flags), (mask_data, self.mask_key)):
                     make_resident(obj, nm)
-                gkey = "_g2l_" + str(id(mask_dist))
-                if gkey not in data:
-                    data[gkey] = SharedData(mask_dist.global_submap_to_local, "g2l")
-                g2l = make_resident(data[gkey], "g2l")
+                g2l = device_g2l(data, str(id(mask_dist)), mask_dist)
                 capi.dev.scan_mask(accel_device_ptr(g2l.data), accel_device_ptr(mask_data.buffer),
                                    mask_dist.n_pix_submap, self.mask_bits, self.det_flags_value, pd.indices(dets),
                                    accel_device_ptr(pd.buffer), fd.indices(dets), accel_device_ptr(fd.buffer),
@@ -342,20 +364,11 @@ class BuildNoiseWeighted(_MapBuilder):
         tmpl, amps = clean
         iob = data.obs.index(ob)
         make_resident(amps, f"{tmpl.name}_amplitudes")
-        if "_g2l_" + self.pixel_dist not in data:
-            data["_g2l_" + self.pixel_dist] = SharedData(dist.global_submap_to_local, "g2l")
-        g2l = make_resident(data["_g2l_" + self.pixel_dist], "g2l")
+        g2l = device_g2l(data, self.pixel_dist, dist)
         n_samp = ob.n_local_samples
         pd, wd, sd = ob.detdata[self.pixels], ob.detdata[self.weights], ob.detdata[self.det_data]
-        if self.det_flags is not None:
-            fd = ob.detdata[self.det_flags]
-            f_ptr, f_ns = accel_device_ptr(fd.buffer), n_samp
-        else:
-            f_ptr, f_ns = 0, 0
-        if self.shared_flags is not None:
-            s_ptr, s_n = accel_device_ptr(ob.shared[self.shared_flags].data), n_samp
-        else:
-            s_ptr, s_n = 0, 0
+        _, f_ptr, f_ns = device_det_flags(ob, self.det_flags, dets)
+        s_ptr, s_n = device_shared_flags(ob, self.shared_flags)
         capi.dev.offset_clean_accumulate(
             tmpl._step_length(tmpl.step_time, tmpl._obs_rate[iob]), tmpl.det_amp_offsets(iob, dets), tmpl._obs_views[iob],
             accel_device_ptr(amps.buffer), accel_device_ptr(amps.local_flags), accel_device_ptr(g2l.data),
@@ -409,10 +422,7 @@ class BuildNoiseWeightedOnTheFly(BuildNoiseWeighted):
             data[self.zmap] = PixelData(dist, np.float64, n_value=nnz)
             zmap = data[self.zmap]
         accel_place(zmap, self.zmap, True, zero_new=not zmap.accel_exists() and zmap.host_is_zero())
-        gkey = "_g2l_" + self.pixel_dist
-        if gkey not in data:
-            data[gkey] = SharedData(dist.global_submap_to_local, "g2l")
-        g2l = make_resident(data[gkey], "g2l")
+        g2l = device_g2l(data, self.pixel_dist, dist)
         view = self.pixel_pointing.view
         for ob in data.obs:
             dets = ob.select_local_detectors(selection=detectors, flagmask=self.det_mask)
@@ -429,9 +439,8 @@ class BuildNoiseWeightedOnTheFly(BuildNoiseWeighted):
             pt = otf_descriptor(ob, dets, self.pixel_pointing, self.stokes_weights, compact=compact)
             n_samp = ob.n_local_samples
             dd = make_resident(ob.detdata[self.det_data], self.det_data)
-            flag_indx, flag_data, shared = self._flag_args(ob, dets, True)
-            f_ptr, f_n = (accel_device_ptr(flag_data), n_samp) if self.det_flags is not None else (0, 0)
-            s_ptr, s_n = (accel_device_ptr(shared), n_samp) if self.shared_flags is not None else (0, 0)
+            flag_indx, f_ptr, f_n = device_det_flags(ob, self.det_flags, dets, resident=True)
+            s_ptr, s_n = device_shared_flags(ob, self.shared_flags, resident=True)
             clean = getattr(self, "_clean", None)
             if clean is not None:
                 # zmap += A^T N^-1 (d - M a): the template subtraction inside the accumulate kernel (MapMaker's fused
@@ -590,22 +599,14 @@ class BuildInverseCovariance(_MapBuilder):
         Returns whether ONE kernel did all three."""
         from .. import capi
 
-        if "_g2l_" + self.pixel_dist not in data:
-            data["_g2l_" + self.pixel_dist] = SharedData(dist.global_submap_to_local, "g2l")
-        g2l = make_resident(data["_g2l_" + self.pixel_dist], "g2l")
+        g2l = device_g2l(data, self.pixel_dist, dist)
         n_samp = ob.n_local_samples
         pd, wd, sd = ob.detdata[self.pixels], ob.detdata[self.weights], ob.detdata[self.signal]
         if sd.dtype != np.float64:
             raise RuntimeError(f"BuildInverseCovariance: signal '{self.signal}' must be float64")
         nnz = 1 if len(wd.detector_shape) == 1 else wd.detector_shape[1]
-        if self.det_flags is not None:
-            f_ptr, f_ns = accel_device_ptr(ob.detdata[self.det_flags].buffer), n_samp
-        else:
-            f_ptr, f_ns = 0, 0
-        if self.shared_flags is not None:
-            s_ptr, s_n = accel_device_ptr(ob.shared[self.shared_flags].data), n_samp
-        else:
-            s_ptr, s_n = 0, 0
+        _, f_ptr, f_ns = device_det_flags(ob, self.det_flags, dets)
+        s_ptr, s_n = device_shared_flags(ob, self.shared_flags)
         return capi.dev.build_cov_hits_signal(
             accel_device_ptr(g2l.data), accel_device_ptr(invcov.buffer), accel_device_ptr(hits.buffer),
             accel_device_ptr(zmap.buffer), dist.n_pix_submap, nnz, pd.indices(dets), accel_device_ptr(pd.buffer),

@@ -9,13 +9,17 @@ src/toast/ops/mapmaker_solve.py:27-229 (SolverRHS), :232-521 (SolverLHS), :524-7
 
 import numpy as np
 
-from ..accel import make_resident
+from .. import capi
+from ..accel import accel_data_create, accel_data_delete, accel_device_ptr, accel_enabled, make_resident, native
 from ..data import defaults
-from ..templates import AmplitudesMap
+from ..pixels import PixelData
+from ..templates import AmplitudesMap, Offset
 from ..traits import Bool, ImplementationType, Instance, Int, List, Unicode
-from .mapmaker_ops import Copy, Delete, NoiseWeight, ScanMap
+from .mapmaker_ops import Copy, Delete, NoiseWeight, ScanMap, device_det_flags, device_g2l, device_shared_flags
 from .operator import Operator
+from .packed_pointing import FusedContext, ObsPass, PackCache
 from .pipeline import Pipeline, uncached_detector_sets
+from .pointing import compact_pixel_cache, otf_descriptor, otf_supported
 
 
 class TemplateMatrix(Operator):
@@ -166,6 +170,151 @@ class TemplateMatrix(Operator):
         return all(t.supports_accel() for t in self.templates)
 
 
+def _sequence_pipe(binning, det_data, units, first, last):
+    """The tail of both sides as the reference's operators on the timestream ``det_data``: ``first``, [the pointing when
+    it is not cached,] subtract the scanned binned map, noise-weight, ``last``."""
+    pixels, weights = binning.pixel_pointing, binning.stokes_weights
+    scan_map = ScanMap(pixels=pixels.pixels, weights=weights.weights, view=pixels.view, map_key=binning.binned,
+                       det_data=det_data, det_data_units=units, det_mask=binning.det_mask,
+                       det_flag_mask=binning.det_flag_mask, subtract=True)
+    noise_weight = NoiseWeight(noise_model=binning.noise_model, det_data=det_data, det_mask=binning.det_mask,
+                               det_flag_mask=binning.det_flag_mask, view=pixels.view)
+    if binning.full_pointing:
+        return Pipeline(detector_sets=["ALL"], operators=[first, scan_map, noise_weight, last])
+    return Pipeline(detector_sets=uncached_detector_sets(),
+                    operators=[first, pixels, weights, scan_map, noise_weight, last])
+
+
+def collect_stable(collect, error):
+    """``collect()`` gathers raw device pointers.  An allocation made meanwhile can fail and trigger the eviction handler
+    (Data.accel_evict), which may free a buffer whose pointer was already taken.  Every create / delete bumps the memory
+    manager's generation, so: collect again until one whole pass ran without any (the second pass normally finds
+    everything resident and allocates nothing)."""
+    for _attempt in range(4):
+        gen0 = capi.accel_generation()
+        out = collect()
+        if capi.accel_generation() == gen0:
+            return out
+    raise RuntimeError(error)
+
+
+def can_fuse(binning, template_matrix):
+    """Whether the fused offset kernels can stand in for the operator sequence of this binning and these templates."""
+    if not accel_enabled():
+        return False
+    if capi.get_deterministic():
+        # debug mode: only build_noise_weighted has an order-deterministic form (deterministic.hip)
+        return False
+    if not binning.full_pointing:
+        # uncached pointing: only through the on-the-fly kernels
+        if not (getattr(binning, "on_the_fly", False)
+                and otf_supported(binning.pixel_pointing, binning.stokes_weights)):
+            return False
+    tmpls = [t for t in template_matrix.templates if t.enabled]
+    if len(tmpls) != 1 or not isinstance(tmpls[0], Offset):
+        return False
+    if tmpls[0].use_noise_prior and binning.pixel_pointing.view is not None:
+        # with a noise prior the baselines ignore the view (offset.py:135-140); the fused
+        # kernels take the baseline boundaries from the pointing view
+        return False
+    if binning.stokes_weights.mode not in ("I", "IQU"):
+        return False
+    return True
+
+
+def fused_prepare(binning, tm, out, data, detectors, cache=None, in_solve=False):
+    """Everything of the fused sweeps that is not a kernel launch: residency of the operands, device pointers,
+    per-observation index arrays.  ``out``: the Data key of the output amplitudes; ``cache``: the PackCache that may hold
+    packed copies of the pointing (``in_solve``: a solve is running, the only time it does).  Returns the FusedContext."""
+    pixels_op, weights_op = binning.pixel_pointing, binning.stokes_weights
+    tmpl = [t for t in tm.templates if t.enabled][0]
+    amps_in = data[tm.amplitudes][tmpl.name]
+    amps_out = data[out][tmpl.name]
+    # full_pointing: cached pointing, resident on the device (computed once, reused by every
+    # iteration); otherwise the kernels evaluate the pointing on the fly from the boresight
+    pixels_op.detector_pointing.det_mask = binning.det_mask
+    on_the_fly = not binning.full_pointing
+    if not on_the_fly:
+        cached = True
+        for ob in data.obs:
+            dets = ob.select_local_detectors(detectors, flagmask=binning.det_mask)
+            for key in (pixels_op.pixels, weights_op.weights):
+                if key not in ob.detdata or not set(dets) <= set(ob.detdata[key].detectors):
+                    cached = False
+        if cached:
+            # do not drag the detector quaternions (4x the pixel volume) to the device again
+            for ob in data.obs:
+                make_resident(ob.detdata[pixels_op.pixels], pixels_op.pixels)
+                make_resident(ob.detdata[weights_op.weights], weights_op.weights)
+        else:
+            pixels_op.apply(data, detectors=detectors, use_accel=True)
+            weights_op.apply(data, detectors=detectors, use_accel=True)
+    dist = data[binning.pixel_dist]
+    nnz = len(weights_op.mode)
+    if binning.binned not in data:
+        data[binning.binned] = PixelData(dist, np.float64, n_value=nnz)
+    zmap = data[binning.binned]
+    if not zmap.accel_exists():
+        zmap.accel_create(binning.binned, zero_out=True)
+    cov = make_resident(data[binning.covariance], binning.covariance)
+    g2l = device_g2l(data, binning.pixel_dist, dist)
+    make_resident(amps_in, f"{tmpl.name}_in")
+    if not amps_out.accel_exists():
+        amps_out.accel_create(f"{tmpl.name}_out", zero_out=True)
+    world = dist._world()
+    ctx = FusedContext(
+        on_the_fly=on_the_fly, nnz=nnz, nps=dist.n_pix_submap, n_local=dist.n_local_submap, zmap=zmap, amps_in=amps_in,
+        amps_out=amps_out, zmap_ptr=accel_device_ptr(zmap.buffer), zmap_bytes=zmap.buffer.nbytes,
+        cov_ptr=accel_device_ptr(cov.buffer), g2l_ptr=accel_device_ptr(g2l.data), in_ptr=accel_device_ptr(amps_in.buffer),
+        in_flags_ptr=accel_device_ptr(amps_in.local_flags), out_ptr=accel_device_ptr(amps_out.buffer),
+        out_bytes=amps_out.buffer.nbytes, det_flag_mask=binning.det_flag_mask, shared_flag_mask=binning.shared_flag_mask,
+        tmpl_flag_mask=tmpl.det_flag_mask, passes=[],
+        # several processes, one GPU each: sum over processes and covariance in one owner-computes pass on the stream
+        owner_computes=bool(world is not None and binning.sync_type == "alltoallv" and world.device_comm()
+                            and dist.replicated))
+    if tmpl.use_noise_prior and tmpl._prior is not None:
+        tmpl._prior.to_device()
+        ctx.prior = tmpl._prior
+    for iob, ob in enumerate(data.obs):
+        dets = [d for d in ob.select_local_detectors(detectors, flagmask=binning.det_mask)
+                if d in tmpl._obs_dets[iob]]
+        if len(dets) == 0:
+            continue
+        noise = ob[binning.noise_model]
+        n_samp = ob.n_local_samples
+        f_idx, f_ptr, f_ns = device_det_flags(ob, binning.det_flags, dets, resident=True)
+        s_ptr, s_n = device_shared_flags(ob, binning.shared_flags, resident=True)
+        pf_idx, pf_ptr, pf_n = None, 0, 0
+        if tmpl.det_flags is not None:
+            pflags = tmpl._solver_flags(iob, ob, True)
+            pf_idx, pf_ptr, pf_n = ob.detdata[tmpl.det_flags].indices(dets), accel_device_ptr(pflags), n_samp
+        ps = ObsPass(iob=iob, dets=dets, step=tmpl._step_length(tmpl.step_time, tmpl._obs_rate[iob]),
+                     ao=tmpl.det_amp_offsets(iob, dets), nav=tmpl._obs_views[iob], n_samp=n_samp,
+                     ivl=ob.intervals[pixels_op.view].data,
+                     detw=np.array([noise.detector_weight(d) for d in dets], dtype=np.float64),
+                     f_idx=f_idx, f_ptr=f_ptr, f_ns=f_ns, s_ptr=s_ptr, s_n=s_n, pf_idx=pf_idx, pf_ptr=pf_ptr, pf_n=pf_n)
+        if on_the_fly:
+            compact = None
+            if getattr(binning, "compact_cache", False):
+                compact = compact_pixel_cache(ob, dets, pixels_op, weights_op, dist, ctx.g2l_ptr)
+            ps.pt = otf_descriptor(ob, dets, pixels_op, weights_op, compact=compact)
+        else:
+            pd, wd = ob.detdata[pixels_op.pixels], ob.detdata[weights_op.weights]
+            ps.pi, ps.pp = pd.indices(dets), accel_device_ptr(pd.buffer)
+            ps.wi, ps.wp = wd.indices(dets), accel_device_ptr(wd.buffer)
+        ctx.passes.append(ps)
+    # (last: the packed copies are read from the arrays whose pointers were just collected)
+    if cache is not None and not on_the_fly:
+        for ps in ctx.passes:
+            ps.pk = cache.cached(ctx, ps, in_solve)
+    elif cache is not None and getattr(binning, "packed_cache", False) and not getattr(binning, "compact_cache", False):
+        for ps in ctx.passes:
+            ob = data.obs[ps.iob]
+            ps.pk = cache.on_the_fly(ctx, ps, in_solve, (id(ob), pixels_op.nside, pixels_op.nest),
+                                     lambda dets, ob=ob: otf_descriptor(ob, dets, pixels_op, weights_op), dist.n_submap)
+    return ctx
+
+
 class SolverRHS(Operator):
     """Right-hand side ``b = M^T N^-1 Z d`` (mapmaker_solve.py:27-229)."""
 
@@ -179,30 +328,22 @@ class SolverRHS(Operator):
                             "weight / project "
                             "(not a reference trait; False = the reference operator sequence)")
 
-    def _fused_lhs(self, data):
-        """The SolverLHS whose launch context the fused tail borrows, or None when the sequence has to run."""
-        if not self.fused:
-            return None
-        lhs = SolverLHS(name=f"{self.name}_ctx", binning=self.binning, template_matrix=self.template_matrix,
-                        out=self.template_matrix.amplitudes, fused=True, packed_pointing=False)
-        if not lhs._can_fuse(data):
-            return None
+    def _can_fuse(self, data):
+        """Whether the fused tail runs, or the sequence has to."""
+        if not (self.fused and can_fuse(self.binning, self.template_matrix)):
+            return False
         tmpl = [t for t in self.template_matrix.templates if t.enabled][0]
         if tmpl.use_noise_prior:
-            return None     # (the prior's baselines ignore the view; keep the reference sequence there)
+            return False     # (the prior's baselines ignore the view; keep the reference sequence there)
         for ob in data.obs:
             if self.det_data in ob.detdata and ob.detdata[self.det_data].dtype != np.float64:
-                return None
-        return lhs
+                return False
+        return True
 
-    def _exec_fused(self, data, detectors, lhs):
+    def _exec_fused(self, data, detectors):
         """b = M^T N^-1 (d - A C A^T N^-1 d): the binning pass, then ONE pass over the cached pointing that reads d
         (toast_hip_offset_scan_project_signal_dev) -- no copy of the timestreams, no scan_map / noise_weight /
-        project_signal passes over it."""
-        from .. import capi
-        from ..accel import accel_device_ptr
-        from ..templates import AmplitudesMap
-
+        project_signal passes over it.  It sweeps the arrays as they are: no packed cache."""
         tm = self.template_matrix
         tm.transpose = True
         tm.det_data = self.det_data
@@ -214,39 +355,22 @@ class SolverRHS(Operator):
         if tm.amplitudes not in data:
             data[tm.amplitudes] = AmplitudesMap()
             data[tm.amplitudes][tmpl.name] = tmpl.zeros()
-        # The context holds raw device pointers: collect until one whole pass made no allocation (an allocation that
-        # fails evicts lazily retained buffers, possibly one whose pointer was already taken; see SolverLHS).
-        for _attempt in range(4):
-            gen0 = capi.accel_generation()
+
+        def collect():
             # the binned map of the pass above is an INPUT here (the left-hand side only uses that buffer as scratch)
             make_resident(data[self.binning.binned], self.binning.binned)
             for ob in data.obs:
                 if self.det_data in ob.detdata:
                     make_resident(ob.detdata[self.det_data], self.det_data)
-            ctx = lhs._fused_prepare(data, detectors)
-            if capi.accel_generation() == gen0:
-                break
-        else:
-            raise RuntimeError("SolverRHS: device buffers keep being evicted while the right-hand side is prepared "
-                               "(device memory too small for its working set)")
-        D = capi.dev
+            return fused_prepare(self.binning, tm, tm.amplitudes, data, detectors)
+
+        ctx = collect_stable(collect, "SolverRHS: device buffers keep being evicted while the right-hand side is prepared "
+                                      "(device memory too small for its working set)")
         # (like TemplateMatrix(transpose): amplitudes that already exist are added to, not reset)
-        for ps in ctx["passes"]:
-            ob = data.obs[ps["iob"]]
-            dd = ob.detdata[self.det_data]
-            if ctx["on_the_fly"]:
-                D.otf_offset_scan_project_signal(ps["pt"], ps["step"], ps["ao"], ps["nav"], dd.indices(ps["dets"]),
-                                                 accel_device_ptr(dd.buffer), ctx["out_ptr"], ctx["in_flags_ptr"],
-                                                 ctx["g2l_ptr"], ctx["zmap_ptr"], ctx["nps"], ps["pf_idx"],
-                                                 ps["pf_ptr"], ps["pf_n"], ctx["tmpl_flag_mask"], ps["detw"],
-                                                 ps["n_samp"], ps["ivl"])
-                continue
-            D.offset_scan_project_signal(ps["step"], ps["ao"], ps["nav"], dd.indices(ps["dets"]),
-                                         accel_device_ptr(dd.buffer), ctx["out_ptr"], ctx["in_flags_ptr"],
-                                         ctx["g2l_ptr"], ctx["zmap_ptr"], ctx["nps"], ctx["nnz"], ps["pi"], ps["pp"],
-                                         ps["wi"], ps["wp"], ps["pf_idx"], ps["pf_ptr"], ctx["tmpl_flag_mask"],
-                                         ps["detw"], ps["n_samp"], ps["ivl"])
-        ctx["amps_out"].accel_used(True)
+        for ps in ctx.passes:
+            dd = data.obs[ps.iob].detdata[self.det_data]
+            ctx.scan_project_signal(ps, dd.indices(ps.dets), accel_device_ptr(dd.buffer))
+        ctx.amps_out.accel_used(True)
         tm._finalize(data)
 
     def _exec(self, data, detectors=None, **kwargs):
@@ -256,30 +380,15 @@ class SolverRHS(Operator):
         self.binning.det_data = self.det_data
         self.binning.det_data_units = self.det_data_units
         self.binning.apply(data, detectors=detectors)
-        lhs = self._fused_lhs(data)
-        if lhs is not None:
-            self._exec_fused(data, detectors, lhs)
+        if self._can_fuse(data):
+            self._exec_fused(data, detectors)
             return
         det_temp = "temp_RHS"
-        pixels = self.binning.pixel_pointing
-        weights = self.binning.stokes_weights
-        copy_det = Copy(detdata=[(self.det_data, det_temp)])
-        scan_map = ScanMap(pixels=pixels.pixels, weights=weights.weights, view=pixels.view,
-                           map_key=self.binning.binned, det_data=det_temp, det_data_units=self.det_data_units,
-                           det_mask=self.binning.det_mask, det_flag_mask=self.binning.det_flag_mask, subtract=True)
-        noise_weight = NoiseWeight(noise_model=self.binning.noise_model, det_data=det_temp,
-                                   det_mask=self.binning.det_mask, det_flag_mask=self.binning.det_flag_mask,
-                                   view=pixels.view)
         self.template_matrix.transpose = True
         self.template_matrix.det_data = det_temp
         self.template_matrix.det_data_units = self.det_data_units
-        if self.binning.full_pointing:
-            ops = [copy_det, scan_map, noise_weight, self.template_matrix]
-            proj_pipe = Pipeline(detector_sets=["ALL"], operators=ops)
-        else:
-            ops = [copy_det, pixels, weights, scan_map, noise_weight, self.template_matrix]
-            proj_pipe = Pipeline(detector_sets=uncached_detector_sets(), operators=ops)
-        proj_pipe.apply(data, detectors=detectors)
+        _sequence_pipe(self.binning, det_temp, self.det_data_units, Copy(detdata=[(self.det_data, det_temp)]),
+                       self.template_matrix).apply(data, detectors=detectors)
         Delete(detdata=[det_temp]).apply(data)
 
     def _finalize(self, data, **kwargs):
@@ -313,33 +422,7 @@ class SolverLHS(Operator):
 
     # -- fused path ---------------------------------------------------------------------------
     def _can_fuse(self, data):
-        from ..accel import accel_enabled
-        from ..templates import Offset
-
-        if not (self.fused and accel_enabled()):
-            return False
-        from .. import capi
-
-        if capi.get_deterministic():
-            # debug mode: only build_noise_weighted has an order-deterministic form (deterministic.hip)
-            return False
-        if not self.binning.full_pointing:
-            # uncached pointing: only through the on-the-fly kernels
-            from .pointing import otf_supported
-
-            if not (getattr(self.binning, "on_the_fly", False)
-                    and otf_supported(self.binning.pixel_pointing, self.binning.stokes_weights)):
-                return False
-        tmpls = [t for t in self.template_matrix.templates if t.enabled]
-        if len(tmpls) != 1 or not isinstance(tmpls[0], Offset):
-            return False
-        if tmpls[0].use_noise_prior and self.binning.pixel_pointing.view is not None:
-            # with a noise prior the baselines ignore the view (offset.py:135-140); the fused
-            # kernels take the baseline boundaries from the pointing view
-            return False
-        if self.binning.stokes_weights.mode not in ("I", "IQU"):
-            return False
-        return True
+        return bool(self.fused and can_fuse(self.binning, self.template_matrix))
 
     def __del__(self):
         try:
@@ -349,395 +432,39 @@ class SolverLHS(Operator):
 
     def release_packed(self):
         """Give the packed pointing cache back (and forget the recorded launches that point into it)."""
-        packed = self.__dict__.pop("_packed", None)
-        if packed:
-            from .. import capi
-
+        cache = self.__dict__.pop("_packed", None)
+        if cache is not None and cache.entries:
             self.__dict__.pop("_fused_plan", None)
-            for _key, pk in packed.values():
-                self._free_pack(pk)
+            cache.release()
 
-    @staticmethod
-    def _room_for_pack(nbytes):
-        """The packed cache is an extra: it is built only while at least a fifth of the device stays free afterwards (a
-        data set of many observations keeps the on-the-fly / unpacked sweeps for those that do not fit)."""
-        from .. import capi
-
-        free, total = capi.accel_mem_info()
-        return free - nbytes >= total // 5
-
-    @staticmethod
-    def _free_pack(pk):
-        from .. import capi
-
-        for ptr, nbytes in pk["blocks"]:
-            capi.device_release(ptr, nbytes)     # (kept by the manager for the next solve's copy of the same size)
-
-    def _pack_pass(self, c, ps):
-        """The packed copy of one observation's cached pointing (toast_hip_offset_pack_pointing_dev), or None when it
-        cannot be had: switched off, rows of an odd length, an intensity weight that varies along a row, no memory."""
-        import os
-
-        from .. import capi
-
-        if not self.packed_pointing or os.environ.get("TOAST_HIP_PACKED_POINTING", "1") == "0":
+    def _pack_cache(self):
+        """The packed pointing cache of this operator; None when the trait switches it off."""
+        if not self.packed_pointing:
             return None
-        if not getattr(self, "keep_on_device", False):
-            # The pack is a SNAPSHOT of pixels, weights and flags, keyed by their device addresses: it lives inside a
-            # solve (solve() sets keep_on_device and gives the pack back in its finally block).  A stand-alone apply()
-            # sweeps the live arrays -- an in-place edit followed by accel_update_device keeps the address.
-            return None
-        n_det, n_samp = len(ps["dets"]), int(ps["n_samp"])
-        if c["nnz"] != 3 or n_samp % 2 != 0 or n_det == 0:
-            return None
-        # One packed copy per observation for the whole solve: the launch plan is rebuilt when the amplitude vectors
-        # change (starting guess, then the proposal), the pointing behind it is the same -- same arrays at the same device
-        # addresses, same flags and masks, same views.
-        ident = (tuple(ps["dets"]), n_samp, c["g2l_ptr"], c["nps"], ps["pp"], tuple(int(i) for i in ps["pi"]), ps["wp"],
-                 tuple(int(i) for i in ps["wi"]), ps["f_ptr"], ps["f_ns"], c["det_flag_mask"], ps["s_ptr"], ps["s_n"],
-                 c["shared_flag_mask"], ps["pf_ptr"], ps["pf_n"], c["tmpl_flag_mask"],
-                 np.ascontiguousarray(ps["ivl"]).tobytes())
-        packed = self.__dict__.setdefault("_packed", {})
-        have = packed.get(ps["iob"])
-        if have is not None:
-            if have[0] == ident:
-                return have[1]
-            del packed[ps["iob"]]
-            self._free_pack(have[1])
-        if not self._room_for_pack(20 * n_det * n_samp):
-            return None
-        mine = []
-        try:
-            for nbytes in (4 * n_det * n_samp, 16 * n_det * n_samp, 8 * n_det):
-                nbytes = max(nbytes, 16)
-                mine.append((capi.device_malloc(nbytes, -2), nbytes))
-        except RuntimeError:
-            self._free_pack(dict(blocks=mine))
-            return None
-        key_ptr, qu_ptr, cal_ptr = (m[0] for m in mine)
-        # the pair weight sums are written by the same sweep (toast_hip_offset_pack_pointing_onepass_dev): their block
-        # is taken first and given back when the pairs turn out not to qualify
-        corr_ptr, corr_bytes = 0, max(8 * ((n_det + 1) // 2) * n_samp, 16)
-        if os.environ.get("TOAST_HIP_PACKED_PAIR_WEIGHTS", "1") != "0" and os.environ.get("TOAST_HIP_PACK_ONEPASS", "1") != "0":
-            try:
-                corr_ptr = capi.device_malloc(corr_bytes, -2)
-            except RuntimeError:
-                corr_ptr = 0
-        tried_onepass = bool(corr_ptr)
-        if corr_ptr:
-            ok, pair, pair_weights = capi.dev.offset_pack_pointing_onepass(
-                c["g2l_ptr"], c["nps"], ps["pi"], ps["pp"], ps["wi"], ps["wp"], ps["f_idx"], ps["f_ptr"], ps["f_ns"],
-                c["det_flag_mask"], ps["s_ptr"], ps["s_n"], c["shared_flag_mask"], ps["pf_idx"], ps["pf_ptr"], ps["pf_n"],
-                c["tmpl_flag_mask"], n_samp, ps["ivl"], key_ptr, qu_ptr, cal_ptr, corr_ptr)
-            if ok and pair_weights:
-                mine.append((corr_ptr, corr_bytes))
-            else:
-                capi.device_release(corr_ptr, corr_bytes)
-                corr_ptr = 0
-        else:
-            ok, pair = capi.dev.offset_pack_pointing(
-                c["g2l_ptr"], c["nps"], ps["pi"], ps["pp"], ps["wi"], ps["wp"], ps["f_idx"], ps["f_ptr"], ps["f_ns"],
-                c["det_flag_mask"], ps["s_ptr"], ps["s_n"], c["shared_flag_mask"], ps["pf_idx"], ps["pf_ptr"], ps["pf_n"],
-                c["tmpl_flag_mask"], n_samp, ps["ivl"], key_ptr, qu_ptr, cal_ptr)
-        if not ok:
-            self._free_pack(dict(blocks=mine))
-            return None
-        pk = dict(key=key_ptr, qu=qu_ptr, cal=cal_ptr, pair=pair, corr=corr_ptr, blocks=mine)
-        if not tried_onepass:
-            self._pack_pair_weights(pk, n_det, n_samp, ps["ivl"])
-        packed[ps["iob"]] = (ident, pk)
-        return pk
-
-    @staticmethod
-    def _pack_pair_weights(pk, n_det, n_samp, ivl):
-        """With pair words: the partner's Q / U weights as float sums q_a + q_b, u_a + u_b when that is exact for every
-        sample in view (orthogonal pairs of equal calibration and efficiency; toast_hip_offset_pack_pair_weights_dev) --
-        14 instead of 18 B per detector-sample in both sweeps.  Anything else leaves the pack as it is."""
-        import os
-
-        from .. import capi
-
-        if not pk["pair"] or os.environ.get("TOAST_HIP_PACKED_PAIR_WEIGHTS", "1") == "0":
-            return
-        nbytes = max(8 * ((n_det + 1) // 2) * n_samp, 16)
-        try:
-            ptr = capi.device_malloc(nbytes, -2)
-        except RuntimeError:
-            return
-        if capi.dev.offset_pack_pair_weights(pk["qu"], ptr, n_det, n_samp, ivl):
-            pk["corr"] = ptr
-            pk["blocks"] = list(pk["blocks"]) + [(ptr, nbytes)]
-        else:
-            capi.device_release(ptr, nbytes)
-
-    def _pack_pass_otf(self, c, ps, ob, pixels_op, weights_op, n_submap):
-        """The packed cache of an observation whose pointing is NOT cached (full_pointing=False, packed_cache=True):
-        pixels and weights of a batch of detectors are expanded from the boresight into a bounded temporary
-        (toast_hip_otf_pixels_healpix_dev / _stokes_weights_dev), packed into the batch's rows, and the temporary goes to
-        the next batch; co-pointing pairs are merged at the end.  None when it cannot be had (see _pack_pass)."""
-        import os
-
-        from .. import capi
-        from .pointing import otf_descriptor
-
-        if os.environ.get("TOAST_HIP_PACKED_POINTING", "1") == "0" or not getattr(self, "keep_on_device", False):
-            return None            # (outside a solve: see _pack_pass)
-        dets = ps["dets"]
-        n_det, n_samp = len(dets), int(ps["n_samp"])
-        if c["nnz"] != 3 or n_samp % 2 != 0 or n_det == 0:
-            return None
-        ident = ("otf", tuple(dets), n_samp, c["g2l_ptr"], c["nps"], id(ob), pixels_op.nside, pixels_op.nest,
-                 ps["f_ptr"], ps["f_ns"], c["det_flag_mask"], ps["s_ptr"], ps["s_n"], c["shared_flag_mask"],
-                 ps["pf_ptr"], ps["pf_n"], c["tmpl_flag_mask"], np.ascontiguousarray(ps["ivl"]).tobytes())
-        packed = self.__dict__.setdefault("_packed", {})
-        have = packed.get(ps["iob"])
-        if have is not None:
-            if have[0] == ident:
-                return have[1]
-            del packed[ps["iob"]]
-            self._free_pack(have[1])
-        D = capi.dev
-        batch = max(2, int((4 << 30) // (32 * n_samp)) // 2 * 2)       # <= 4 GB of expanded pointing at a time, whole pairs
-        batch = min(batch, n_det + (n_det & 1))
-        if not self._room_for_pack(20 * n_det * n_samp + 32 * batch * n_samp):
-            return None
-        mine, temps = [], []
-        try:
-            for nbytes in (4 * n_det * n_samp, 16 * n_det * n_samp, 8 * n_det):
-                nbytes = max(nbytes, 16)
-                mine.append((capi.device_malloc(nbytes, -2), nbytes))
-            for nbytes in (8 * batch * n_samp, 24 * batch * n_samp, max(int(n_submap), 16)):
-                temps.append((capi.device_malloc(nbytes, -2), nbytes))
-        except RuntimeError:
-            self._free_pack(dict(blocks=mine + temps))
-            return None
-        (key_ptr, _), (qu_ptr, _), (cal_ptr, _) = mine
-        (pix_ptr, _), (w_ptr, _), (hsub_ptr, _) = temps
-        # the pair words and the pair weight sums straight from each batch's expanded pointing (one sweep per batch,
-        # toast_hip_offset_pack_pointing_onepass_dev; batches are whole pairs) -- or, when a batch's pairs do not share their
-        # pixels, everything again the old way: plain words per batch, then pair check / merge / weights over all rows
-        corr_ptr, corr_bytes = 0, max(8 * ((n_det + 1) // 2) * n_samp, 16)
-        if (os.environ.get("TOAST_HIP_PACKED_PAIR_WEIGHTS", "1") != "0" and os.environ.get("TOAST_HIP_PACK_ONEPASS", "1") != "0"
-                and self._room_for_pack(20 * n_det * n_samp + 32 * batch * n_samp + corr_bytes)):
-            try:
-                corr_ptr = capi.device_malloc(corr_bytes, -2)
-            except RuntimeError:
-                corr_ptr = 0
-
-        def sweep(onepass):
-            """-> (ok, every batch in pair words, every batch's sums usable)"""
-            pairs, sums = True, True
-            for b0 in range(0, n_det, batch):
-                bd = dets[b0:b0 + batch]
-                rows = np.arange(len(bd), dtype=np.int32)
-                pt = otf_descriptor(ob, bd, pixels_op, weights_op)
-                D.otf_pixels_healpix(pt, rows, pix_ptr, n_samp, ps["ivl"], hsub_ptr, n_submap, c["nps"])
-                D.otf_stokes_weights(pt, rows, w_ptr, n_samp, ps["ivl"])
-                pf_idx = None if ps["pf_idx"] is None else ps["pf_idx"][b0:b0 + batch]
-                args = (c["g2l_ptr"], c["nps"], rows, pix_ptr, rows, w_ptr, ps["f_idx"][b0:b0 + batch], ps["f_ptr"], ps["f_ns"],
-                        c["det_flag_mask"], ps["s_ptr"], ps["s_n"], c["shared_flag_mask"], pf_idx, ps["pf_ptr"], ps["pf_n"],
-                        c["tmpl_flag_mask"], n_samp, ps["ivl"], key_ptr + 4 * b0 * n_samp, qu_ptr + 16 * b0 * n_samp,
-                        cal_ptr + 8 * b0)
-                if onepass:
-                    good, pair_b, sums_b = D.offset_pack_pointing_onepass(*args, corr_ptr + 8 * (b0 // 2) * n_samp)
-                    pairs, sums = pairs and pair_b, sums and sums_b
-                    if good and not pair_b:
-                        return True, False, False
-                else:
-                    good, _ = D.offset_pack_pointing(*args, pair_words=False)
-                if not good:
-                    return False, False, False
-            return True, pairs, sums
-
-        ok, tried_onepass = True, False
-        try:
-            pair, sums = False, False
-            if corr_ptr:
-                tried_onepass = True
-                ok, pair, sums = sweep(True)
-            if ok and not pair:
-                tried_onepass = False
-                ok, _, _ = sweep(False)
-                pair = bool(ok and D.offset_pack_pairs(key_ptr, n_det, n_samp, ps["ivl"]))
-        finally:
-            self._free_pack(dict(blocks=temps))
-        if corr_ptr and not (ok and tried_onepass and sums):
-            capi.device_release(corr_ptr, corr_bytes)
-            corr_ptr = 0
-        if not ok:
-            self._free_pack(dict(blocks=mine))
-            return None
-        if corr_ptr:
-            mine.append((corr_ptr, corr_bytes))
-        pk = dict(key=key_ptr, qu=qu_ptr, cal=cal_ptr, pair=pair, corr=corr_ptr, blocks=mine)
-        if not tried_onepass:
-            self._pack_pair_weights(pk, n_det, n_samp, ps["ivl"])
-        packed[ps["iob"]] = (ident, pk)
-        return pk
-
-    def _fused_prepare(self, data, detectors):
-        """Everything of the fused left-hand side that is not a kernel launch: residency of the
-        operands, device pointers, per-observation index arrays.  Returns the launch context."""
-        from ..accel import accel_device_ptr
-        from ..pixels import PixelData
-        from .pointing import compact_pixel_cache, otf_descriptor
-
-        binning, tm = self.binning, self.template_matrix
-        pixels_op, weights_op = binning.pixel_pointing, binning.stokes_weights
-        tmpl = [t for t in tm.templates if t.enabled][0]
-        amps_in = data[tm.amplitudes][tmpl.name]
-        amps_out = data[self.out][tmpl.name]
-        # full_pointing: cached pointing, resident on the device (computed once, reused by every
-        # iteration); otherwise the kernels evaluate the pointing on the fly from the boresight
-        pixels_op.detector_pointing.det_mask = binning.det_mask
-        on_the_fly = not binning.full_pointing
-        if not on_the_fly:
-            cached = True
-            for ob in data.obs:
-                dets = ob.select_local_detectors(detectors, flagmask=binning.det_mask)
-                for key in (pixels_op.pixels, weights_op.weights):
-                    if key not in ob.detdata or not set(dets) <= set(ob.detdata[key].detectors):
-                        cached = False
-            if cached:
-                # do not drag the detector quaternions (4x the pixel volume) to the device again
-                for ob in data.obs:
-                    make_resident(ob.detdata[pixels_op.pixels], pixels_op.pixels)
-                    make_resident(ob.detdata[weights_op.weights], weights_op.weights)
-            else:
-                pixels_op.apply(data, detectors=detectors, use_accel=True)
-                weights_op.apply(data, detectors=detectors, use_accel=True)
-        dist = data[binning.pixel_dist]
-        nnz = len(weights_op.mode)
-        if binning.binned not in data:
-            data[binning.binned] = PixelData(dist, np.float64, n_value=nnz)
-        zmap = data[binning.binned]
-        if not zmap.accel_exists():
-            zmap.accel_create(binning.binned, zero_out=True)
-        cov = make_resident(data[binning.covariance], binning.covariance)
-        if "_g2l_" + binning.pixel_dist not in data:
-            from ..data import SharedData
-
-            data["_g2l_" + binning.pixel_dist] = SharedData(dist.global_submap_to_local, "g2l")
-        g2l = make_resident(data["_g2l_" + binning.pixel_dist], "g2l")
-        make_resident(amps_in, f"{tmpl.name}_in")
-        if not amps_out.accel_exists():
-            amps_out.accel_create(f"{tmpl.name}_out", zero_out=True)
-        ctx = dict(on_the_fly=on_the_fly, nnz=nnz, nps=dist.n_pix_submap, n_local=dist.n_local_submap,
-                   zmap=zmap, amps_in=amps_in, amps_out=amps_out, zmap_ptr=accel_device_ptr(zmap.buffer),
-                   zmap_bytes=zmap.buffer.nbytes, cov_ptr=accel_device_ptr(cov.buffer), g2l_ptr=accel_device_ptr(g2l.data),
-                   in_ptr=accel_device_ptr(amps_in.buffer), in_flags_ptr=accel_device_ptr(amps_in.local_flags),
-                   out_ptr=accel_device_ptr(amps_out.buffer), out_bytes=amps_out.buffer.nbytes,
-                   det_flag_mask=binning.det_flag_mask, shared_flag_mask=binning.shared_flag_mask,
-                   tmpl_flag_mask=tmpl.det_flag_mask, passes=[], prior=None)
-        world = dist._world()
-        # several processes, one GPU each: sum over processes and covariance in one owner-computes pass on the stream
-        ctx["owner_computes"] = bool(world is not None and binning.sync_type == "alltoallv" and world.device_comm()
-                                     and dist.replicated)
-        if tmpl.use_noise_prior and tmpl._prior is not None:
-            tmpl._prior.to_device()
-            ctx["prior"] = tmpl._prior
-        for iob, ob in enumerate(data.obs):
-            dets = [d for d in ob.select_local_detectors(detectors, flagmask=binning.det_mask)
-                    if d in tmpl._obs_dets[iob]]
-            if len(dets) == 0:
-                continue
-            noise = ob[binning.noise_model]
-            n_samp = ob.n_local_samples
-            ps = dict(iob=iob, dets=dets, step=tmpl._step_length(tmpl.step_time, tmpl._obs_rate[iob]),
-                      ao=tmpl.det_amp_offsets(iob, dets),
-                      nav=tmpl._obs_views[iob], n_samp=n_samp, ivl=ob.intervals[pixels_op.view].data,
-                      detw=np.array([noise.detector_weight(d) for d in dets], dtype=np.float64))
-            if binning.det_flags is not None:
-                fd = make_resident(ob.detdata[binning.det_flags], binning.det_flags)
-                ps.update(f_idx=fd.indices(dets), f_ptr=accel_device_ptr(fd.buffer), f_ns=n_samp)
-            else:
-                ps.update(f_idx=np.zeros(len(dets), np.int32), f_ptr=0, f_ns=0)
-            if binning.shared_flags is not None:
-                sf = make_resident(ob.shared[binning.shared_flags], binning.shared_flags)
-                ps.update(s_ptr=accel_device_ptr(sf.data), s_n=n_samp)
-            else:
-                ps.update(s_ptr=0, s_n=0)
-            if tmpl.det_flags is not None:
-                pflags = tmpl._solver_flags(iob, ob, True)
-                ps.update(pf_idx=ob.detdata[tmpl.det_flags].indices(dets), pf_ptr=accel_device_ptr(pflags), pf_n=n_samp)
-            else:
-                ps.update(pf_idx=None, pf_ptr=0, pf_n=0)
-            if on_the_fly:
-                compact = None
-                if getattr(binning, "compact_cache", False):
-                    compact = compact_pixel_cache(ob, dets, pixels_op, weights_op, dist, ctx["g2l_ptr"])
-                ps["pt"] = otf_descriptor(ob, dets, pixels_op, weights_op, compact=compact)
-            else:
-                pd, wd = ob.detdata[pixels_op.pixels], ob.detdata[weights_op.weights]
-                ps.update(pi=pd.indices(dets), pp=accel_device_ptr(pd.buffer), wi=wd.indices(dets),
-                          wp=accel_device_ptr(wd.buffer))
-            ctx["passes"].append(ps)
-        # (last: the packed copies are read from the arrays whose pointers were just collected)
-        if not on_the_fly:
-            for ps in ctx["passes"]:
-                ps["pk"] = self._pack_pass(ctx, ps)
-        elif (getattr(binning, "packed_cache", False) and self.packed_pointing
-              and not getattr(binning, "compact_cache", False)):
-            for ps in ctx["passes"]:
-                ps["pk"] = self._pack_pass_otf(ctx, ps, data.obs[ps["iob"]], pixels_op, weights_op, dist.n_submap)
-        return ctx
+        return self.__dict__.setdefault("_packed", PackCache())
 
     @staticmethod
     def _fused_first_half(c):
         """zmap = 0;  a_out = 0;  zmap += A^T N^-1 M a   (launches only, ``capi.dev``)"""
-        from .. import capi
-
-        D = capi.dev
-        D.memset(c["zmap_ptr"], 0, c["zmap_bytes"])
-        D.memset(c["out_ptr"], 0, c["out_bytes"])
-        if c["prior"] is not None:
+        capi.dev.memset(c.zmap_ptr, 0, c.zmap_bytes)
+        capi.dev.memset(c.out_ptr, 0, c.out_bytes)
+        if c.prior is not None:
             # a_out = C_a^-1 a: the noise prior term of the left-hand side (mapmaker_solve.py:409-411)
-            c["prior"].add_prior(c["amps_in"], c["amps_out"])
-        for ps in c["passes"]:
-            if ps.get("pk") is not None:
-                pk = ps["pk"]
-                D.offset_accumulate_packed(ps["step"], ps["ao"], ps["nav"], c["in_ptr"], c["in_flags_ptr"], c["zmap_ptr"],
-                                           pk["key"], pk["qu"], pk["cal"], ps["detw"], ps["n_samp"], ps["ivl"],
-                                           pair_words=pk["pair"], pair_corr=pk.get("corr", 0))
-            elif c["on_the_fly"]:
-                D.otf_offset_accumulate(ps["pt"], ps["step"], ps["ao"], ps["nav"], c["in_ptr"], c["in_flags_ptr"],
-                                        c["g2l_ptr"], c["zmap_ptr"], c["nps"], ps["f_idx"], ps["f_ptr"], ps["f_ns"],
-                                        ps["detw"], c["det_flag_mask"], ps["n_samp"], ps["ivl"], ps["s_ptr"],
-                                        ps["s_n"], c["shared_flag_mask"])
-            else:
-                D.offset_accumulate(ps["step"], ps["ao"], ps["nav"], c["in_ptr"], c["in_flags_ptr"], c["g2l_ptr"],
-                                    c["zmap_ptr"], c["nps"], c["nnz"], ps["pi"], ps["pp"], ps["wi"], ps["wp"],
-                                    ps["f_idx"], ps["f_ptr"], ps["f_ns"], ps["detw"], c["det_flag_mask"],
-                                    ps["n_samp"], ps["ivl"], ps["s_ptr"], ps["s_n"], c["shared_flag_mask"])
+            c.prior.add_prior(c.amps_in, c.amps_out)
+        for ps in c.passes:
+            c.accumulate(ps)
 
     @staticmethod
     def _fused_second_half(c):
         """zmap = C zmap;  a_out += M^T N^-1 (M a - A zmap)"""
-        from .. import capi
-
-        D = capi.dev
-        if c.get("owner_computes"):
+        if c.owner_computes:
             # zmap = C . (sum over processes of zmap) in one owner-computes pass on this stream: RCCL reduce-scatter,
             # covariance on the owned pixel shard, all-gather (toast_hip_comm_map_reduce_apply_dev)
-            D.comm_map_reduce_apply(c["n_local"] * c["nps"], c["nnz"], c["cov_ptr"], c["zmap_ptr"], reduce=True)
+            capi.dev.comm_map_reduce_apply(c.n_local * c.nps, c.nnz, c.cov_ptr, c.zmap_ptr, reduce=True)
         else:
-            D.cov_apply_diag(c["n_local"], c["nps"], c["nnz"], c["cov_ptr"], c["zmap_ptr"])
-        for ps in c["passes"]:
-            if ps.get("pk") is not None:
-                pk = ps["pk"]
-                D.offset_scan_project_packed(ps["step"], ps["ao"], ps["nav"], c["in_ptr"], c["out_ptr"], c["in_flags_ptr"],
-                                             c["zmap_ptr"], pk["key"], pk["qu"], pk["cal"], ps["detw"], ps["n_samp"],
-                                             ps["ivl"], pair_words=pk["pair"], pair_corr=pk.get("corr", 0))
-            elif c["on_the_fly"]:
-                D.otf_offset_scan_project(ps["pt"], ps["step"], ps["ao"], ps["nav"], c["in_ptr"], c["out_ptr"],
-                                          c["in_flags_ptr"], c["g2l_ptr"], c["zmap_ptr"], c["nps"], ps["pf_idx"],
-                                          ps["pf_ptr"], ps["pf_n"], c["tmpl_flag_mask"], ps["detw"], ps["n_samp"],
-                                          ps["ivl"])
-            else:
-                D.offset_scan_project(ps["step"], ps["ao"], ps["nav"], c["in_ptr"], c["out_ptr"], c["in_flags_ptr"],
-                                      c["g2l_ptr"], c["zmap_ptr"], c["nps"], c["nnz"], ps["pi"], ps["pp"], ps["wi"],
-                                      ps["wp"], ps["pf_idx"], ps["pf_ptr"], c["tmpl_flag_mask"], ps["detw"],
-                                      ps["n_samp"], ps["ivl"])
+            capi.dev.cov_apply_diag(c.n_local, c.nps, c.nnz, c.cov_ptr, c.zmap_ptr)
+        for ps in c.passes:
+            c.scan_project(ps)
 
     def _exec_fused(self, data, detectors):
         """a' = M^T N^-1 (M a - A C A^T N^-1 M a) with two passes over the pointing and no
@@ -748,9 +475,6 @@ class SolverLHS(Operator):
         with their converted arguments) and replayed while the operands and the memory manager's
         generation are unchanged: the host then spends ~0.1 ms per iteration instead of
         re-deriving ~100 arguments, and the GPU does not idle between iterations."""
-        from .. import capi
-        from ..accel import native
-
         binning, tm = self.binning, self.template_matrix
         tmpl = [t for t in tm.templates if t.enabled][0]
         tm.det_data = self.det_temp
@@ -768,19 +492,11 @@ class SolverLHS(Operator):
                amps_in.accel_in_use())
         plan = self.__dict__.get("_fused_plan")
         if plan is None or plan["key"] != key or plan["generation"] != capi.accel_generation():
-            # The context holds raw device pointers.  An allocation made while they are being collected
-            # can fail and trigger the eviction handler (Data.accel_evict), which may free a buffer whose
-            # pointer is already in the context.  Every create / delete bumps the manager's generation, so:
-            # collect again until one whole pass ran without any (the second pass normally finds
-            # everything resident and allocates nothing).
-            for _attempt in range(4):
-                gen0 = capi.accel_generation()
-                ctx = self._fused_prepare(data, detectors)
-                if capi.accel_generation() == gen0:
-                    break
-            else:
-                raise RuntimeError("SolverLHS: device buffers keep being evicted while the fused left-hand "
-                                   "side is prepared (device memory too small for its working set)")
+            ctx = collect_stable(
+                lambda: fused_prepare(binning, tm, self.out, data, detectors, cache=self._pack_cache(),
+                                      in_solve=getattr(self, "keep_on_device", False)),
+                "SolverLHS: device buffers keep being evicted while the fused left-hand side is prepared "
+                "(device memory too small for its working set)")
             with capi.capture() as first:
                 self._fused_first_half(ctx)
             with capi.capture() as second:
@@ -788,19 +504,15 @@ class SolverLHS(Operator):
             key = key[:4] + (id(data.get(binning.binned)),) + key[5:-1] + (True,)
             plan = dict(key=key, generation=capi.accel_generation(), ctx=ctx, first=first, second=second)
             self._fused_plan = plan
-            # which sweeps the plan holds, one entry per observation: "packed" (the solver's packed pointing cache),
-            # "fused" (the cached pixels / weights as they are), "fused-otf" (pointing evaluated in the kernels)
-            self.last_route = tuple("packed" if ps.get("pk") is not None else ("fused-otf" if ctx["on_the_fly"] else "fused")
-                                    for ps in ctx["passes"])
-            # bytes per detector-sample and sweep of each packed observation: 20, 18 (pair words) or 14 (+ pair weights)
-            self.last_pack_bytes = tuple((14 if ps["pk"].get("corr") else (18 if ps["pk"]["pair"] else 20))
-                                         if ps.get("pk") is not None else None for ps in ctx["passes"])
+            # which sweeps the plan holds and the bytes per detector-sample of a packed one, one entry per observation
+            self.last_route = tuple(ps.route for ps in ctx.passes)
+            self.last_pack_bytes = tuple(None if ps.pk is None else ps.pk.bytes_per_sample for ps in ctx.passes)
         ctx = plan["ctx"]
-        zmap = ctx["zmap"]
+        zmap = ctx.zmap
         zmap.accel_used(True)
         amps_out.accel_used(True)
         plan["first"].replay()
-        if not ctx.get("owner_computes"):
+        if not ctx.owner_computes:
             zmap.sync_allreduce()      # (device-resident: an RCCL all-reduce on the same stream; no-op for one process)
         plan["second"].replay()
         if not getattr(self, "keep_on_device", False):
@@ -826,8 +538,6 @@ class SolverLHS(Operator):
             return
         self.last_route = ("sequence",)
         self._zero_temp(data)
-        pixels = self.binning.pixel_pointing
-        weights = self.binning.stokes_weights
         self.template_matrix.transpose = False
         self.template_matrix.det_data = self.det_temp
         self.template_matrix.det_data_units = self.det_data_units
@@ -839,23 +549,12 @@ class SolverLHS(Operator):
         if self.out in data:
             data[self.out].reset()
         self.template_matrix.add_prior(data[self.template_matrix.amplitudes], data[self.out])
-        scan_map = ScanMap(pixels=pixels.pixels, weights=weights.weights, view=pixels.view,
-                           map_key=self.binning.binned, det_data=self.det_temp, det_data_units=self.det_data_units,
-                           det_mask=self.binning.det_mask, det_flag_mask=self.binning.det_flag_mask, subtract=True)
-        noise_weight = NoiseWeight(noise_model=self.binning.noise_model, det_data=self.det_temp,
-                                   det_mask=self.binning.det_mask, det_flag_mask=self.binning.det_flag_mask,
-                                   view=pixels.view)
         template_transpose = self.template_matrix.duplicate()
         template_transpose.amplitudes = self.out
         template_transpose.transpose = True
         self._zero_temp(data)
-        if self.binning.full_pointing:
-            ops = [self.template_matrix, scan_map, noise_weight, template_transpose]
-            proj_pipe = Pipeline(detector_sets=["ALL"], operators=ops)
-        else:
-            ops = [self.template_matrix, pixels, weights, scan_map, noise_weight, template_transpose]
-            proj_pipe = Pipeline(detector_sets=uncached_detector_sets(), operators=ops)
-        proj_pipe.apply(data, detectors=detectors)
+        _sequence_pipe(self.binning, self.det_temp, self.det_data_units, self.template_matrix,
+                       template_transpose).apply(data, detectors=detectors)
 
     def _finalize(self, data, **kwargs):
         return
@@ -892,9 +591,6 @@ def _pcg_device_scalars(data, detectors, lhs_op, result, residual, precond, prop
     iteration k + 1 while the device works on iteration k and reads the status one iteration late; an iteration
     enqueued after the end is a no-op for the solution (alpha = 0)."""
     import time as _time
-
-    from .. import capi
-    from ..accel import accel_data_create, accel_data_delete, accel_device_ptr
 
     D = capi.dev
     state_host = np.zeros(D.pcg_state_bytes(n_iter_max), dtype=np.uint8)   # host key of the device-side state block
