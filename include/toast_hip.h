@@ -606,7 +606,8 @@ int toast_hip_template_offset_project_signal_dev(
  *   offset_accumulate :   zmap += A^T N^-1 (M a)
  *   offset_scan_project : a_out += M^T [ det_w (M a - A map) ]  over samples with clear flags
  * amp_offsets[d] = first amplitude of detector d (Offset._det_start).  flag_index / d_flag_data
- * may be NULL (no sample flags). */
+ * may be NULL (no sample flags); flag rows that are all negative mean the same, a mix of negative and
+ * non-negative rows is an argument error. */
 int toast_hip_template_offset_add_to_signal_multi_dev(
     int64_t step_length, const int64_t * amp_offsets /*host*/, const int64_t * n_amp_views /*host*/,
     const double * d_amplitudes, const uint8_t * d_amplitude_flags, const int32_t * data_index /*host*/,

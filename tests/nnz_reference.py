@@ -1,7 +1,8 @@
 """Extended-precision statements of the map-domain operations for any number of Stokes components
 (nnz = 1 "I", 2 "QU", 3 "IQU", 4), with rounding bounds that are derived and not chosen.  Shared by
-tests/test_nnz_reference_host.py (the CPU oracle must stay inside the bounds) and tests/test_gpu_nnz.py (every launch
-variant of the HIP kernels must).  Nothing here calls the code under test.
+tests/test_nnz_reference_host.py (the CPU oracle must stay inside the bounds), tests/test_gpu_nnz.py (every launch
+variant of the HIP kernels must) and tests/test_gpu_offset_steps.py (the offset-template kernels at every baseline
+length).  Nothing here calls the code under test.
 
 Every function returns the exact value (``np.longdouble``, unit roundoff 2^-64: its own rounding is 2^-11 of a double's
 and is ignored), the sum of the magnitudes of what was added up and, for scatter sums, the number of terms.
@@ -18,7 +19,27 @@ the library is built with -ffp-contract=off, so every product and sum is rounded
   M = |d| |scale| sum |w_k m_k|.  With the zero switch d is 0 (also for a sample without a pixel: it is zeroed).
 * offset_scan_project: a term is fl(fl(a - sum_k w_k m_k) dw): gamma(nnz + 2) (|a| + sum |w_k m_k|) |dw|; n of them are
   added to what the amplitude held, n additions: gamma(n + nnz + 2) S.
-* hits are integers: exact."""
+* hits are integers: exact.
+
+The offset-template statements at any baseline length (tests/test_gpu_offset_steps.py):
+
+* offset_add_to_signal: a sample of an unflagged amplitude is fl(d + a), ONE IEEE addition, and the correctly rounded sum
+  is what a float64 addition returns: the statement is exact and the comparison is bit equality, everywhere -- samples of
+  flagged amplitudes, samples outside the views and rows outside data_index hold what they held.
+* offset_project_signal: the terms are the raw samples d_s (read, not computed: no rounding of their own); n of them are
+  added, in any order, onto what the amplitude held: n additions, |got - exact| <= gamma(n) S with
+  S = |initial| + sum |d_s| -- ``extra = 0``.  Flagged samples contribute an exact + 0.0 and are not terms.
+* offset_clean_accumulate: a term is fl(fl(fl(d - a~) s) w_k) with a~ the amplitude or, flagged, 0 (the kernel's 0.0 + a is
+  exact): fl(d - a~) = (d - a~)(1 + e1) errs RELATIVE to the exact difference, the two products add e2, e3:
+  |term - (d - a~) s w_k| <= gamma(3) |(d - a~) s w_k|.  With the n additions: gamma(n + 3) S,
+  S = |initial| + sum |(d - a~) s w_k| -- ``extra = 3``, one more than offset_accumulate.
+* the packed sweeps (packed_pointing.hip) read the I weight from ``cal`` (checked equal to weights[..., 0] in every sample
+  when the cache is written) and Q / U from ``qu`` (copies): the same operands, products and order as the kernels over the
+  original arrays, fl(fl(a s) w_k) and fl(fl(a - sum_k fl(w_k m_k)) dw); the pair forms add the two detectors' terms of a
+  sample before the run sum, which is one of the n additions.  ``extra = 2`` and ``extra = nnz + 2 = 5`` as above.
+* flagged-sample counts are sums of 1.0 far below 2^53: exact integers.
+* offset_variance: rint, one subtraction of integers (exact), one division, one comparison; one product and one division
+  for the variance: the same IEEE operations in NumPy double -- bit equality."""
 import numpy as np
 
 import cases
@@ -41,6 +62,25 @@ CASES = {
     "no_flags": dict(with_det_flags=False, with_shared_flags=False),
 }
 
+#: baseline lengths at which the offset kernels change path: runs of 1, 2, one DPP row (16), half a wave (32), a wave (64),
+#: two samples per lane times a wave (128: the packed sweeps' uniform amplitude look-up), a workgroup trip (256), a chunk
+#: (1024), one amplitude per view and a step no view reaches; each with its neighbours (divisors that are and are not
+#: powers of two)
+STEPS = (1, 2, 3, 15, 16, 17, 31, 32, 33, 63, 64, 65, 127, 128, 129, 255, 256, 257, 1023, 1024, 1025, 2500, 10**6)
+
+#: view cases of the offset-template grid: make_case arguments and, where given, the views [first, last) that replace
+#: the case's own.  long_odd_view: odd first sample, odd length, three chunks (steps 1023 / 1024 / 1025 put a baseline
+#: boundary before, on and after the chunk boundary at sample 3 + 1024); even_views: even first samples and even lengths,
+#: the middle one longer than a chunk -- with an even step no lane of the two-samples-per-lane kernels sees a boundary
+#: between its samples.
+VIEW_CASES = {
+    "long_odd_view": (dict(n_det=5, n_samp=2600, nside=64), ((3, 2598),)),
+    "odd_dets_odd_starts": (CASES["odd_dets_odd_starts"], None),
+    "odd_n_samp": (CASES["odd_n_samp"], None),
+    "short_intervals": (CASES["short_intervals"], None),
+    "even_views": (dict(n_det=4, n_samp=3000, nside=64), ((0, 1000), (1002, 2050), (2052, 3000))),
+}
+
 #: (should_zero, should_subtract, should_scale) of scan_map
 SCAN_MODES = {"zero": (True, False, False), "add": (False, False, False), "subtract": (False, True, False),
               "multiply": (False, False, True)}
@@ -55,11 +95,23 @@ def gamma(m):
 _POINTING = {}
 
 
+def intervals(views, rate=10.0):
+    """Views [first, last) as an interval array."""
+    ivl = np.zeros(len(views), dtype=cases.interval_dtype)
+    for k, (first, last) in enumerate(views):
+        ivl[k]["first"], ivl[k]["last"] = first, last
+        ivl[k]["start"], ivl[k]["stop"] = first / rate, last / rate
+    return ivl
+
+
 def pointing(oracle, name):
     """(case, pointing) of CASES[name]: pixels, IQU weights, global2local and the number of local submaps from the CPU
     oracle's pointing chain.  Computed once per session; callers must not write into it."""
     if name not in _POINTING:
-        c = cases.make_case(**CASES[name])
+        kwargs, views = VIEW_CASES[name] if name in VIEW_CASES else (CASES[name], None)
+        c = cases.make_case(**kwargs)
+        if views is not None:
+            c["intervals"] = intervals(views, c["rate"])
         ch = cases.run_chain(oracle, c)
         pt = dict(pixels=ch["pixels"], weights=ch["weights"], g2l=ch["g2l"], n_local=ch["zmap"].shape[0])
         for a in list(pt.values()) + [v for v in c.values() if isinstance(v, np.ndarray)]:
@@ -117,14 +169,15 @@ def _local(c, pt, p):
     return hit, np.where(hit, lsm * nps + p % nps, 0)
 
 
-def amplitude_index(c, step, n_amp_views):
+def amplitude_index(c, step, n_amp_views, shift=0):
     """Per sample the index of its baseline inside one detector's amplitudes (template_offset: the views follow each
-    other, each with n_amp_views[v] steps of ``step`` samples); -1 outside the views."""
+    other, each with n_amp_views[v] steps of ``step`` samples); -1 outside the views.  ``shift`` moves every baseline
+    boundary by that many samples: a wrong statement, for the tests that show that the bounds can fail."""
     out = np.full(c["n_samp"], -1, dtype=np.int64)
     run = 0
     for iv, n in zip(c["intervals"], n_amp_views):
         first, last = int(iv["first"]), int(iv["last"])
-        out[first:last] = run + (np.arange(first, last) - first) // step
+        out[first:last] = run + (np.arange(first, last) - first + shift) // step
         run += int(n)
     return out
 
@@ -173,9 +226,10 @@ class Scatter:
         return excess(got[self.idx], self.total, gamma(self.n + extra)[:, None] * self.mag)
 
 
-def _scatter(c, pt, initial, det_mask, shared_mask, values):
+def _scatter(c, pt, initial, det_mask, shared_mask, values, skip_non_local=False):
     """initial + the sum over the unflagged, pixelled samples inside the views of values(d, s) [len(s), n_value], per
-    local pixel."""
+    local pixel.  ``skip_non_local``: samples whose submap is not local contribute nothing (the offset kernels skip
+    them); otherwise there must be none."""
     samples = view_samples(c)
     elements, terms = [], []
     for d in range(c["n_det"]):
@@ -183,7 +237,10 @@ def _scatter(c, pt, initial, det_mask, shared_mask, values):
         good = (p >= 0) & _unflagged(c, d, samples, det_mask, shared_mask)
         s, p = samples[good], p[good]
         hit, loc = _local(c, pt, p)
-        assert hit.all(), "the scatter kernels need every hit submap to be local"
+        if skip_non_local:
+            s, loc = s[hit], loc[hit]
+        else:
+            assert hit.all(), "the scatter kernels need every hit submap to be local"
         elements.append(loc)
         terms.append(values(d, s))
     return Scatter(initial, elements, terms)
@@ -210,7 +267,7 @@ def inverse_covariance(c, pt, weights, nnz, cov0, det_mask=1, shared_mask=1):
 
 
 def offset_accumulate(c, pt, weights, nnz, zmap0, step, n_amp_views, amp_offsets, amps, amp_flags, det_mask=1,
-                      shared_mask=1):
+                      shared_mask=1, skip_non_local=False):
     """zmap0 + A^T N^-1 M a: build_noise_weighted of the timestream of unflagged baseline amplitudes -> Scatter."""
     aidx = amplitude_index(c, step, n_amp_views)
 
@@ -219,7 +276,79 @@ def offset_accumulate(c, pt, weights, nnz, zmap0, step, n_amp_views, amp_offsets
         t = np.where(amp_flags[a] == 0, amps[a], 0.0).astype(LD) * LD(c["det_scale"][d])
         return t[:, None] * _wrow(c, weights, d, s, nnz)
 
+    return _scatter(c, pt, np.reshape(zmap0, (-1, nnz)), det_mask, shared_mask, values, skip_non_local)
+
+
+def offset_clean_accumulate(c, pt, weights, nnz, zmap0, step, n_amp_views, amp_offsets, amps, amp_flags, signal, det_mask=1,
+                            shared_mask=1):
+    """zmap0 + A^T N^-1 (d - M a): build_noise_weighted of the signal (rows by data_index) minus the timestream of
+    unflagged baseline amplitudes -> Scatter (``extra = 3``)."""
+    aidx = amplitude_index(c, step, n_amp_views)
+
+    def values(d, s):
+        a = amp_offsets[d] + aidx[s]
+        t = signal[c["data_index"][d]][s].astype(LD) - np.where(amp_flags[a] == 0, amps[a], 0.0).astype(LD)
+        return (t * LD(c["det_scale"][d]))[:, None] * _wrow(c, weights, d, s, nnz)
+
     return _scatter(c, pt, np.reshape(zmap0, (-1, nnz)), det_mask, shared_mask, values)
+
+
+def offset_add_to_signal(c, step, n_amp_views, amp_offsets, amps, amp_flags, tod, shift=0):
+    """tod + M a: every sample inside the views whose amplitude is unflagged gets the amplitude added (rows by
+    data_index) -> the expected buffer, exact: a float64 addition IS the exact sum rounded once.  Bit equality."""
+    want = np.array(tod, dtype=np.float64)
+    aidx = amplitude_index(c, step, n_amp_views, shift)
+    s = view_samples(c)
+    for d in range(c["n_det"]):
+        row = c["data_index"][d]
+        a = amp_offsets[d] + aidx[s]
+        on = amp_flags[a] == 0
+        want[row, s[on]] = tod[row, s[on]] + amps[a[on]]
+    return want
+
+
+def offset_project_signal(c, step, n_amp_views, amp_offsets, amps0, amp_flags, flag_mask, use_flags, tod=None, shift=0):
+    """amps0 + M^T d: per unflagged amplitude the sum of its samples (rows by data_index; ``use_flags``: of those whose
+    detector flag, rows by flag_index, has no bit of ``flag_mask``) -> Scatter (``extra = 0``)."""
+    tod = c["tod"] if tod is None else tod
+    aidx = amplitude_index(c, step, n_amp_views, shift)
+    samples = view_samples(c)
+    elements, terms = [], []
+    for d in range(c["n_det"]):
+        a = amp_offsets[d] + aidx[samples]
+        keep = amp_flags[a] == 0
+        if use_flags:
+            keep &= (c["det_flags"][c["flag_index"][d], samples] & flag_mask) == 0
+        elements.append(a[keep])
+        terms.append(tod[c["data_index"][d]][samples[keep]].astype(LD)[:, None])
+    return Scatter(np.reshape(amps0, (-1, 1)), elements, terms)
+
+
+def offset_count_flagged(c, step, n_amp_views, amp_offsets, flag_mask, n_amp, det_flags=None):
+    """Per amplitude the number of samples whose detector flag (rows by flag_index) has a bit of ``flag_mask`` -> int64
+    [n_amp], exact."""
+    det_flags = c["det_flags"] if det_flags is None else det_flags
+    aidx = amplitude_index(c, step, n_amp_views)
+    s = view_samples(c)
+    out = np.zeros(n_amp, dtype=np.int64)
+    for d in range(c["n_det"]):
+        bad = (det_flags[c["flag_index"][d], s] & flag_mask) != 0
+        np.add.at(out, amp_offsets[d] + aidx[s][bad], 1)
+    return out
+
+
+def offset_variance(n_bad, amp_len, det_weight, good_fraction):
+    """(flags uint8, variances) [n_det, n_len] of the Offset template's set-up from the flagged-sample counts ``n_bad``
+    [n_det, n_len], the baseline lengths ``amp_len`` [n_len] and the detector weights: an amplitude is cut (flag 1,
+    variance 0) when n_good / max(len, 1) <= good_fraction with n_good = len - rint(n_bad), the weight is not positive
+    or the baseline is empty; else its variance is 1 / (weight x n_good).  The kernel's IEEE operations, in double."""
+    length = np.asarray(amp_len, dtype=np.int64)[None, :]
+    w = np.asarray(det_weight, dtype=np.float64)[:, None]
+    n_good = length.astype(np.float64) - np.rint(np.asarray(n_bad, dtype=np.float64))
+    with np.errstate(divide="ignore", invalid="ignore"):
+        cut = (n_good / np.maximum(length, 1).astype(np.float64) <= good_fraction) | (w <= 0.0) | (length == 0)
+        var = np.where(cut, 0.0, 1.0 / (w * n_good))
+    return cut.astype(np.uint8), var
 
 
 def offset_scan_project(c, pt, weights, nnz, mapdata, step, n_amp_views, amp_offsets, amps, amp_flags, out0, det_weights,

@@ -201,46 +201,46 @@ def fused_setup(torch, hip, c, pt, nnz, otf):
     return s, pt, wts.cpu().numpy()
 
 
-def fused_accumulate(hip, s, c, nnz, otf, lay, d_amps, d_afl, d_z):
+def fused_accumulate(hip, s, c, nnz, otf, lay, d_amps, d_afl, d_z, step=STEP):
     n_amp_views, amp_offsets, _ = lay
     n_samp = c["n_samp"]
     if otf:
-        hip.dev.otf_offset_accumulate(s["pt"], STEP, amp_offsets, n_amp_views, d_amps.data_ptr(), d_afl.data_ptr(),
+        hip.dev.otf_offset_accumulate(s["pt"], step, amp_offsets, n_amp_views, d_amps.data_ptr(), d_afl.data_ptr(),
                                       s["g2l"].data_ptr(), d_z.data_ptr(), c["n_pix_submap"], c["flag_index"],
                                       s["dfl"].data_ptr(), s["n_flag"], c["det_scale"], 1, n_samp, c["intervals"],
                                       s["sfl"].data_ptr(), c["shared_flags"].size, 1)
     else:
-        hip.dev.offset_accumulate(STEP, amp_offsets, n_amp_views, d_amps.data_ptr(), d_afl.data_ptr(), s["g2l"].data_ptr(),
+        hip.dev.offset_accumulate(step, amp_offsets, n_amp_views, d_amps.data_ptr(), d_afl.data_ptr(), s["g2l"].data_ptr(),
                                   d_z.data_ptr(), c["n_pix_submap"], nnz, c["pixel_index"], s["pix"].data_ptr(),
                                   c["weight_index"], s["wts"].data_ptr(), c["flag_index"], s["dfl"].data_ptr(), s["n_flag"],
                                   c["det_scale"], 1, n_samp, c["intervals"], s["sfl"].data_ptr(), c["shared_flags"].size, 1)
 
 
-def fused_scan_project(hip, s, c, nnz, otf, lay, d_amps, d_afl, d_out, d_map):
+def fused_scan_project(hip, s, c, nnz, otf, lay, d_amps, d_afl, d_out, d_map, step=STEP):
     n_amp_views, amp_offsets, _ = lay
     n_samp = c["n_samp"]
     if otf:
-        hip.dev.otf_offset_scan_project(s["pt"], STEP, amp_offsets, n_amp_views, d_amps.data_ptr(), d_out.data_ptr(),
+        hip.dev.otf_offset_scan_project(s["pt"], step, amp_offsets, n_amp_views, d_amps.data_ptr(), d_out.data_ptr(),
                                         d_afl.data_ptr(), s["g2l"].data_ptr(), d_map.data_ptr(), c["n_pix_submap"],
                                         c["flag_index"], s["dfl"].data_ptr(), s["n_flag"], 4, c["det_scale"], n_samp,
                                         c["intervals"])
     else:
-        hip.dev.offset_scan_project(STEP, amp_offsets, n_amp_views, d_amps.data_ptr(), d_out.data_ptr(), d_afl.data_ptr(),
+        hip.dev.offset_scan_project(step, amp_offsets, n_amp_views, d_amps.data_ptr(), d_out.data_ptr(), d_afl.data_ptr(),
                                     s["g2l"].data_ptr(), d_map.data_ptr(), c["n_pix_submap"], nnz, c["pixel_index"],
                                     s["pix"].data_ptr(), c["weight_index"], s["wts"].data_ptr(), c["flag_index"],
                                     s["dfl"].data_ptr(), 4, c["det_scale"], n_samp, c["intervals"])
 
 
-def fused_scan_project_signal(hip, s, c, nnz, otf, lay, d_sig, d_afl, d_out, d_map):
+def fused_scan_project_signal(hip, s, c, nnz, otf, lay, d_sig, d_afl, d_out, d_map, step=STEP):
     n_amp_views, amp_offsets, _ = lay
     n_samp = c["n_samp"]
     if otf:
-        hip.dev.otf_offset_scan_project_signal(s["pt"], STEP, amp_offsets, n_amp_views, c["data_index"], d_sig.data_ptr(),
+        hip.dev.otf_offset_scan_project_signal(s["pt"], step, amp_offsets, n_amp_views, c["data_index"], d_sig.data_ptr(),
                                                d_out.data_ptr(), d_afl.data_ptr(), s["g2l"].data_ptr(), d_map.data_ptr(),
                                                c["n_pix_submap"], c["flag_index"], s["dfl"].data_ptr(), s["n_flag"], 4,
                                                c["det_scale"], n_samp, c["intervals"])
     else:
-        hip.dev.offset_scan_project_signal(STEP, amp_offsets, n_amp_views, c["data_index"], d_sig.data_ptr(), d_out.data_ptr(),
+        hip.dev.offset_scan_project_signal(step, amp_offsets, n_amp_views, c["data_index"], d_sig.data_ptr(), d_out.data_ptr(),
                                            d_afl.data_ptr(), s["g2l"].data_ptr(), d_map.data_ptr(), c["n_pix_submap"], nnz,
                                            c["pixel_index"], s["pix"].data_ptr(), c["weight_index"], s["wts"].data_ptr(),
                                            c["flag_index"], s["dfl"].data_ptr(), 4, c["det_scale"], n_samp, c["intervals"])

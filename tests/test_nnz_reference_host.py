@@ -133,3 +133,73 @@ def test_oracle_operator_sequence_is_inside_the_fused_bounds(oracle, name, nnz):
         oracle.template_offset_project_signal(int(c["data_index"][d]), tod, int(c["flag_index"][d]), c["det_flags"], 4, step,
                                               int(amp_offsets[d]), n_amp_views, out, aflags, c["intervals"])
     assert ref.excess(out, extra=nnz + 2) <= 1.0
+
+
+# ------------------------------------------------------------------------------------------ offset template, every step
+def _offset_inputs(c, step, seed=8):
+    n_amp_views, amp_offsets, n_amp = R.offset_layout(c, step)
+    rng = np.random.default_rng(seed)
+    amps = rng.standard_normal(n_amp)
+    aflags = (rng.random(n_amp) < 0.05).astype(np.uint8)
+    return n_amp_views, amp_offsets, n_amp, amps, aflags
+
+
+def _longest_view(c):
+    return max(int(v["last"]) - int(v["first"]) for v in c["intervals"])
+
+
+@pytest.mark.parametrize("name", ["long_odd_view", "short_intervals"])
+def test_oracle_offset_add_to_signal_equals_the_reference_at_every_step(oracle, name):
+    """Bit equality at every baseline length, and the statement with every baseline boundary moved by one sample differs
+    from the oracle wherever a view holds a boundary at all (step shorter than the view): the comparison can fail."""
+    c, _ = R.pointing(oracle, name)
+    for step in R.STEPS:
+        n_amp_views, amp_offsets, n_amp, amps, aflags = _offset_inputs(c, step)
+        tod = c["tod"].copy()
+        for d in range(c["n_det"]):
+            oracle.template_offset_add_to_signal(step, int(amp_offsets[d]), n_amp_views, amps, aflags,
+                                                 int(c["data_index"][d]), tod, c["intervals"])
+        want = R.offset_add_to_signal(c, step, n_amp_views, amp_offsets, amps, aflags, c["tod"])
+        assert np.array_equal(tod, want), step
+        assert not np.array_equal(tod, c["tod"]), step
+        if step < _longest_view(c):
+            wrong = R.offset_add_to_signal(c, step, n_amp_views, amp_offsets, amps, aflags, c["tod"], shift=1)
+            assert not np.array_equal(tod, wrong), step
+
+
+@pytest.mark.parametrize("fidx", ["no_flags", "flags"])
+@pytest.mark.parametrize("name", ["long_odd_view", "short_intervals"])
+def test_oracle_offset_project_signal_is_inside_the_bound_at_every_step(oracle, name, fidx):
+    """gamma(n) S per amplitude at every baseline length, amplitudes that receive nothing keep their bits, and the
+    statement with the boundaries moved by one sample is outside the bound for every step shorter than the view."""
+    c, _ = R.pointing(oracle, name)
+    use_flags = fidx == "flags"
+    for step in R.STEPS:
+        n_amp_views, amp_offsets, n_amp, amps0, aflags = _offset_inputs(c, step)
+        out = amps0.copy()
+        for d in range(c["n_det"]):
+            oracle.template_offset_project_signal(int(c["data_index"][d]), c["tod"], int(c["flag_index"][d]) if use_flags else -1,
+                                                  c["det_flags"], 4, step, int(amp_offsets[d]), n_amp_views, out, aflags,
+                                                  c["intervals"])
+        ref = R.offset_project_signal(c, step, n_amp_views, amp_offsets, amps0, aflags, 4, use_flags)
+        assert ref.n.sum() > 0
+        worst = ref.excess(out, extra=0)
+        assert worst <= 1.0, (step, worst)
+        if step < _longest_view(c):
+            wrong = R.offset_project_signal(c, step, n_amp_views, amp_offsets, amps0, aflags, 4, use_flags, shift=1)
+            assert wrong.excess(out, extra=0) > 1.0, step
+
+
+def test_offset_count_and_variance_references_on_a_worked_example():
+    """The two exact statements by hand: 7 samples in baselines of 3 (lengths 3, 3, 1), flags with the mask bit mixed with
+    others; and the cut at exactly good_fraction."""
+    c = dict(n_samp=9, n_det=1, intervals=R.intervals(((1, 8),)), flag_index=np.array([0], dtype=np.int32),
+             det_flags=np.array([[1, 1, 0, 2, 3, 1, 0, 1, 1]], dtype=np.uint8))
+    n_amp_views, amp_offsets, n_amp = R.offset_layout(c, 3, amp_offset=2, spare=1)
+    assert list(n_amp_views) == [3] and n_amp == 6
+    counts = R.offset_count_flagged(c, 3, n_amp_views, amp_offsets, 1, n_amp)
+    assert list(counts) == [0, 0, 1, 2, 1, 0]
+    flags, var = R.offset_variance(np.array([[1.0, 2.0000000000000004, 0.0, 0.0]]), [4, 4, 0, 1], [0.5], 0.5)
+    assert flags.tolist() == [[0, 1, 1, 0]]
+    assert var.tolist() == [[1.0 / (0.5 * 3.0), 0.0, 0.0, 2.0]]
+    assert R.offset_variance(np.zeros((1, 1)), [5], [-1.0], 0.0)[0].tolist() == [[1]]

@@ -2679,6 +2679,13 @@ int toast_hip_template_offset_project_signal_multi_dev(
     return guarded([&] {
         if (n_det <= 0) return;
         if (step_length <= 0) fail_arg("step_length must be positive");
+        if (flag_index != nullptr && d_flag_data != nullptr) {
+            // the first entry decides whether flags are used at all: a negative row among non-negative ones would be
+            // read before the flag buffer
+            bool negative = false, row = false;
+            for (int64_t i = 0; i < n_det; ++i) (flag_index[i] < 0 ? negative : row) = true;
+            if (negative && row) fail_arg("offset_project_signal: flag_index mixes negative and non-negative rows");
+        }
         const auto chunks = make_chunks(intervals, n_view, n_samp);
         if (chunks.empty()) return;
         const OffsetViews ov = offset_views(intervals, n_amp_views, n_view);
