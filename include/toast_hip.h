@@ -993,6 +993,31 @@ int toast_hip_subharmonic_precond_build_dev(
     int64_t n_view, double * d_gram, int64_t * d_ngood, void * stream);
 int toast_hip_subharmonic_apply_precond_dev(int64_t norder, int64_t n_block, const double * d_precond,
                                             const double * d_amp_in, double * d_amp_out, void * stream);
+/* GainTemplate (src/toast/templates/gaintemplate.py): the SubHarmonic basis times a per-detector signal estimate.
+ * Arguments as in the toast_hip_subharmonic_*_dev entries, plus the estimate (d_estimate [rows][n_samp], est_index =
+ * the detector's row in it).  norder <= toast_hip_subharmonic_max_terms().
+ *   add_to_signal   signal[d][i] += est[d][i] * (sum_k T_k(r_i) a_k), the sum over ascending k from zero, one rounding
+ *                   per product and per add [gaintemplate.py:182-197; no flags]
+ *   project_signal  a_k += sum_i (est_i signal_i) T_k(r_i) over the samples with (flags & mask) == 0 (every sample when
+ *                   d_det_flags is NULL): the flags ARE applied and the amplitudes ACCUMULATE, the opposite of the
+ *                   SubHarmonic entry [gaintemplate.py:199-220].  Fixed-order reduction, no atomics; the amplitudes of
+ *                   an empty view are left alone.
+ *   precond_build   d_gram[d][v][r][c] = det_weights[d] * sum_i (T_r est_i)(T_c est_i) over ALL samples of the view, no
+ *                   flags, symmetric [gaintemplate.py:159-170; the inverse (:171) is the caller's].  The product with
+ *                   the inverse is toast_hip_subharmonic_apply_precond_dev [gaintemplate.py:226-238]. */
+int toast_hip_gain_add_to_signal_dev(
+    int64_t norder, const int64_t * amp_offsets /*host*/, const double * d_amplitudes, const int32_t * data_index /*host*/,
+    double * d_det_data, const int32_t * est_index /*host*/, const double * d_estimate, int64_t n_det, int64_t n_samp,
+    const toast_hip_interval * intervals /*host*/, int64_t n_view, void * stream);
+int toast_hip_gain_project_signal_dev(
+    int64_t norder, const int64_t * amp_offsets /*host*/, double * d_amplitudes, const int32_t * data_index /*host*/,
+    const double * d_det_data, const int32_t * est_index /*host*/, const double * d_estimate,
+    const int32_t * flag_index /*host*/, const uint8_t * d_det_flags, uint8_t det_flag_mask, int64_t n_det, int64_t n_samp,
+    const toast_hip_interval * intervals /*host*/, int64_t n_view, void * stream);
+int toast_hip_gain_precond_build_dev(
+    int64_t norder, const int32_t * est_index /*host*/, const double * d_estimate, const double * det_weights /*host*/,
+    int64_t n_det, int64_t n_samp, const toast_hip_interval * intervals /*host*/, int64_t n_view, double * d_gram,
+    void * stream);
 int toast_hip_periodic_index_dev(
     const double * d_key, const uint8_t * d_flags, uint8_t flag_mask, int64_t n_row, int64_t n_samp, double obs_min,
     double incr, int64_t nbins, const toast_hip_interval * intervals /*host*/, int64_t n_view, int32_t * d_index,

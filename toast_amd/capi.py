@@ -1512,6 +1512,45 @@ class _Dev:
         _check(lib().toast_hip_subharmonic_apply_precond_dev(_i64(norder), _i64(n_block), _p(d_precond), _p(d_amp_in),
                                                              _p(d_amp_out), _p(stream)))
 
+    # ---- GainTemplate kernels (csrc/template_basis.hip): the SubHarmonic arguments plus the estimate and its rows
+    def gain_add_to_signal(self, norder, amp_offsets, d_amplitudes, data_index, d_det_data, est_index, d_estimate, n_samp,
+                           intervals, stream=0):
+        ao = self._small(amp_offsets, np.int64)
+        di = self._small(data_index, np.int32)
+        ei = self._small(est_index, np.int32)
+        iv = self._small(intervals, interval_dtype)
+        if ao.size != di.size or ei.size != di.size:
+            raise RuntimeError("gain_add_to_signal: one amplitude offset and one estimate row per detector row")
+        _check(lib().toast_hip_gain_add_to_signal_dev(
+            _i64(norder), _p(ao), _p(d_amplitudes), _p(di), _p(d_det_data), _p(ei), _p(d_estimate), _i64(di.size),
+            _i64(n_samp), _p(iv), _i64(iv.size), _p(stream)))
+
+    def gain_project_signal(self, norder, amp_offsets, d_amplitudes, data_index, d_det_data, est_index, d_estimate,
+                            flag_index, d_det_flags, det_flag_mask, n_samp, intervals, stream=0):
+        ao = self._small(amp_offsets, np.int64)
+        di = self._small(data_index, np.int32)
+        ei = self._small(est_index, np.int32)
+        fi = None if flag_index is None else self._small(flag_index, np.int32)
+        iv = self._small(intervals, interval_dtype)
+        if ao.size != di.size or ei.size != di.size:
+            raise RuntimeError("gain_project_signal: one amplitude offset and one estimate row per detector row")
+        if fi is not None and fi.size != di.size:
+            raise RuntimeError("gain_project_signal: one flag row per detector row")
+        _check(lib().toast_hip_gain_project_signal_dev(
+            _i64(norder), _p(ao), _p(d_amplitudes), _p(di), _p(d_det_data), _p(ei), _p(d_estimate), _p(fi),
+            _p(d_det_flags), _u8(det_flag_mask), _i64(di.size), _i64(n_samp), _p(iv), _i64(iv.size), _p(stream)))
+
+    def gain_precond_build(self, norder, est_index, d_estimate, det_weights, n_samp, intervals, d_gram, stream=0):
+        """``d_gram`` float64 [n_det][n_view][norder][norder]."""
+        w = self._small(det_weights, np.float64)
+        ei = self._small(est_index, np.int32)
+        iv = self._small(intervals, interval_dtype)
+        if ei.size != w.size:
+            raise RuntimeError("gain_precond_build: one estimate row per detector weight")
+        _check(lib().toast_hip_gain_precond_build_dev(
+            _i64(norder), _p(ei), _p(d_estimate), _p(w), _i64(w.size), _i64(n_samp), _p(iv), _i64(iv.size), _p(d_gram),
+            _p(stream)))
+
     def periodic_index(self, d_key, d_flags, flag_mask, n_row, n_samp, obs_min, incr, nbins, intervals, d_index, stream=0):
         """``d_index`` int32 [n_row][n_samp]: the bin of every sample in view whose key flags are clear, -1 elsewhere."""
         iv = self._small(intervals, interval_dtype)

@@ -17,6 +17,15 @@
 //                     the amplitude (or writes the weighted Gram matrix).  No atomics anywhere: order-deterministic.
 //   k_subh_precond    out[block] = P[block] in[block], one thread per output amplitude.
 //
+// GainTemplate (src/toast/templates/gaintemplate.py:56-238) -- the same basis times a per-detector signal estimate, a
+// second fp64 stream per sample with its own buffer and row list.  Same chunks, same two-pass reductions.
+//   k_gain_add        signal[d][i] += est[d][i] * sum_k T_k a_k: 24 B per detector-sample.
+//   k_gain_partial    pass 1 of a_k += sum_unflagged (est_i signal_i) T_k(r_i) (17 B per detector-sample; the flags ARE
+//                     applied and the amplitudes accumulate: the opposite of SubHarmonic, gaintemplate.py:199-220) and of
+//                     the Gram matrix sum_all (T_r est)(T_c est) (NO flags: the reference never uses its `good`, :159-170).
+//   k_gain_combine    adds the partials in chunk order ONTO the amplitude (or writes the weighted Gram matrix).
+//   The block product of the preconditioner is k_subh_precond.
+//
 // Periodic -- the bin of every sample is computed once per observation (k_periodic_index: int32((v - min) / incr) in
 // fp64, truncated, clamped to nbins - 1; -1 outside the views and where the key's own flags are set) and cached as an
 // int32 row: the three sweeps then read 4 B per sample, shared by all detectors when the key is a shared field.
@@ -242,6 +251,160 @@ __global__ __launch_bounds__(kThreads) void k_subh_precond(int n, int64_t n_amp,
         double acc = 0.0;
         for (int c = 0; c < n; ++c) acc += row[c] * x[c];
         amp_out[i] = acc;
+    }
+}
+
+// ------------------------------------------------------------------------------------ gain template
+// gaintemplate.py:182-197: the gain fluctuation sum_k T_k a_k (ascending k, from zero), times the estimate, onto the signal
+template <int N>
+__device__ __forceinline__ double gain_add(double s, double e, double r, const double (&amp)[N], int n) {
+    double t[N];
+    subh_terms<N>(r, t);
+    double g = 0.0;
+#pragma unroll
+    for (int k = 0; k < N; ++k) {
+        if (k < n) g += t[k] * amp[k];
+    }
+    return s + e * g;
+}
+
+// The signal moves as aligned pairs like k_subh_add.  The estimate row lies in another buffer with its own row index,
+// so its pairs may start 8 bytes off a 16-byte boundary: it is read as two adjacent 8-byte values with no alignment
+// promised.  gfx950 takes wide loads at 8-byte alignment, and the compiler merges the two into one global_load_dwordx4
+// (seen in the ISA: one dwordx4 load per stream and one dwordx4 store per pair); either way a wave covers one contiguous
+// range of the estimate.
+template <int N>
+__global__ __launch_bounds__(kThreads) void k_gain_add(double * __restrict__ signal, int64_t n_samp,
+                                                       const int32_t * __restrict__ sig_index,
+                                                       const double * __restrict__ estimate,
+                                                       const int32_t * __restrict__ est_index,
+                                                       const int64_t * __restrict__ amp_offsets,
+                                                       const double * __restrict__ amplitudes,
+                                                       const BasisJob * __restrict__ jobs,
+                                                       const BasisChunk * __restrict__ chunks, int n) {
+    const BasisChunk ch = chunks[blockIdx.x];
+    const BasisJob job = jobs[ch.job];
+    const int64_t d = blockIdx.y;
+    const double * __restrict__ arow = amplitudes + amp_offsets[d] + (int64_t)job.view * n;
+    double amp[N];
+#pragma unroll
+    for (int k = 0; k < N; ++k) amp[k] = (k < n) ? arow[k] : 0.0;
+    const int i0 = ch.chunk * kBasisChunk;
+    const int cnt = (i0 + kBasisChunk < job.len) ? kBasisChunk : job.len - i0;
+    double * __restrict__ sig = signal + (int64_t)sig_index[d] * n_samp + job.first + i0;
+    const double * __restrict__ est = estimate + (int64_t)est_index[d] * n_samp + job.first + i0;
+    const double step = linspace_step(job.len);
+    const int pad = (int)((reinterpret_cast<uintptr_t>(sig) >> 3) & 1);
+    const int n_pair = (pad + cnt + 1) >> 1;
+    for (int p = threadIdx.x; p < n_pair; p += kThreads) {
+        const int j = 2 * p - pad;
+        if (j >= 0 && j + 2 <= cnt) {
+            double2 v = *reinterpret_cast<const double2 *>(sig + j);
+            const double ex = est[j], ey = est[j + 1];
+            v.x = gain_add<N>(v.x, ex, linspace_r(i0 + j, job.len, step), amp, n);
+            v.y = gain_add<N>(v.y, ey, linspace_r(i0 + j + 1, job.len, step), amp, n);
+            *reinterpret_cast<double2 *>(sig + j) = v;
+        } else {
+            if (j >= 0 && j < cnt) sig[j] = gain_add<N>(sig[j], est[j], linspace_r(i0 + j, job.len, step), amp, n);
+            if (j + 1 >= 0 && j + 1 < cnt) {
+                sig[j + 1] = gain_add<N>(sig[j + 1], est[j + 1], linspace_r(i0 + j + 1, job.len, step), amp, n);
+            }
+        }
+    }
+}
+
+// GRAM = false: v[k] = sum (est_i signal_i) T_k(r_i) over the UNFLAGGED samples of the chunk (gaintemplate.py:199-220)
+// GRAM = true:  v = packed upper triangle of sum (T_r est_i)(T_c est_i) over ALL samples of the chunk: the reference
+//               computes `good` for its preconditioner and never uses it (gaintemplate.py:159-170)
+template <int N, bool GRAM>
+__global__ __launch_bounds__(kThreads) void k_gain_partial(const double * __restrict__ signal, int64_t n_samp,
+                                                           const int32_t * __restrict__ sig_index,
+                                                           const double * __restrict__ estimate,
+                                                           const int32_t * __restrict__ est_index,
+                                                           const uint8_t * __restrict__ det_flags,
+                                                           const int32_t * __restrict__ flag_index, uint8_t det_mask,
+                                                           const BasisJob * __restrict__ jobs,
+                                                           const BasisChunk * __restrict__ chunks, int64_t n_chunk,
+                                                           double * __restrict__ partial) {
+    constexpr int NV = GRAM ? N * (N + 1) / 2 : N;
+    __shared__ double wave_tot[4 * NV];
+    const BasisChunk ch = chunks[blockIdx.x];
+    const BasisJob job = jobs[ch.job];
+    const int64_t d = blockIdx.y;
+    const int i0 = ch.chunk * kBasisChunk;
+    const int i1 = (i0 + kBasisChunk < job.len) ? i0 + kBasisChunk : job.len;
+    const double step = linspace_step(job.len);
+    const double * __restrict__ est = estimate + (int64_t)est_index[d] * n_samp + job.first;
+    double v[NV];
+#pragma unroll
+    for (int k = 0; k < NV; ++k) v[k] = 0.0;
+    if constexpr (GRAM) {
+        for (int i = i0 + threadIdx.x; i < i1; i += kThreads) {
+            const double e = est[i];
+            double t[N];
+            subh_terms<N>(linspace_r(i, job.len, step), t);
+#pragma unroll
+            for (int k = 0; k < N; ++k) t[k] *= e;
+            int q = 0;
+#pragma unroll
+            for (int r = 0; r < N; ++r) {
+#pragma unroll
+                for (int c = r; c < N; ++c) v[q++] += t[r] * t[c];
+            }
+        }
+    } else {
+        const double * __restrict__ sig = signal + (int64_t)sig_index[d] * n_samp + job.first;
+        const uint8_t * __restrict__ fl =
+            (det_flags != nullptr) ? det_flags + (int64_t)flag_index[d] * n_samp + job.first : nullptr;
+        for (int i = i0 + threadIdx.x; i < i1; i += kThreads) {
+            if (fl != nullptr && (fl[i] & det_mask) != 0) continue;
+            const double w = est[i] * sig[i];
+            double t[N];
+            subh_terms<N>(linspace_r(i, job.len, step), t);
+#pragma unroll
+            for (int k = 0; k < N; ++k) v[k] += w * t[k];
+        }
+    }
+    block_totals<NV>(v, wave_tot, partial + ((int64_t)d * n_chunk + blockIdx.x) * NV);
+}
+
+// grid (views, detectors): thread k adds the partials of its value in chunk order.
+// GRAM = false: amplitudes[amp_offsets[d] + view * n + k] += total: onto the value already there (gaintemplate.py:220)
+// GRAM = true:  gram[(d * n_view + view)][r][c] = gram[..][c][r] = total * weight[d]
+template <int N, bool GRAM>
+__global__ __launch_bounds__(64) void k_gain_combine(const BasisJob * __restrict__ jobs, int64_t n_chunk,
+                                                     const double * __restrict__ partial, int n, int64_t n_view,
+                                                     const int64_t * __restrict__ amp_offsets,
+                                                     double * __restrict__ amplitudes,
+                                                     const double * __restrict__ weights, double * __restrict__ gram) {
+    constexpr int NV = GRAM ? N * (N + 1) / 2 : N;
+    const BasisJob job = jobs[blockIdx.x];
+    const int64_t d = blockIdx.y;
+    const double * __restrict__ p = partial + ((int64_t)d * n_chunk + job.chunk0) * NV;
+    for (int k = threadIdx.x; k < NV; k += 64) {
+        if constexpr (GRAM) {
+            double t = 0.0;
+            for (int c = 0; c < job.n_chunk; ++c) t += p[(int64_t)c * NV + k];
+            int r = 0, rem = k;
+            while (rem >= N - r) {
+                rem -= N - r;
+                ++r;
+            }
+            const int c = r + rem;
+            if (c < n) {
+                const int64_t blk = d * n_view + job.view;
+                const double g = t * weights[d];
+                gram[blk * n * n + r * n + c] = g;
+                gram[blk * n * n + c * n + r] = g;
+            }
+        } else {
+            if (k < n) {
+                double * __restrict__ a = amplitudes + amp_offsets[d] + (int64_t)job.view * n + k;
+                double t = *a;
+                for (int c = 0; c < job.n_chunk; ++c) t += p[(int64_t)c * NV + k];
+                *a = t;
+            }
+        }
     }
 }
 
@@ -639,6 +802,120 @@ int toast_hip_subharmonic_apply_precond_dev(int64_t norder, int64_t n_block, con
         if (d_amp_in == d_amp_out) fail_arg("subharmonic_apply_precond: input and output must be different vectors");
         hipLaunchKernelGGL(k_subh_precond, flat_grid(n_block * norder), dim3(kThreads), 0, as_stream(stream), (int)norder,
                            n_block * norder, d_precond, d_amp_in, d_amp_out);
+        check_launch();
+    });
+}
+
+int toast_hip_gain_add_to_signal_dev(int64_t norder, const int64_t * amp_offsets, const double * d_amplitudes,
+                                     const int32_t * data_index, double * d_det_data, const int32_t * est_index,
+                                     const double * d_estimate, int64_t n_det, int64_t n_samp,
+                                     const toast_hip_interval * intervals, int64_t n_view, void * stream) {
+    return guarded([&] {
+        if (n_det <= 0 || n_view <= 0 || n_samp <= 0) return;
+        subh_check(norder, "gain_add_to_signal");
+        if (n_det > 65535) fail_arg("gain_add_to_signal: at most 65535 detectors per call");
+        if (d_det_data == nullptr || d_estimate == nullptr || d_amplitudes == nullptr) fail_arg("gain_add_to_signal: signal, estimate and amplitudes are required");
+        if ((reinterpret_cast<uintptr_t>(d_det_data) & 7) != 0 || (reinterpret_cast<uintptr_t>(d_estimate) & 7) != 0) fail_arg("gain_add_to_signal: signal and estimate must be 8-byte aligned");
+        hipStream_t st = as_stream(stream);
+        const BasisPlan plan = basis_plan(intervals, n_view, n_samp, "gain_add_to_signal");
+        if (plan.chunks.empty()) return;
+        ParamBlock pb;
+        const size_t o_si = pb.push(data_index, sizeof(int32_t) * n_det);
+        const size_t o_ei = pb.push(est_index, sizeof(int32_t) * n_det);
+        const size_t o_ao = pb.push(amp_offsets, sizeof(int64_t) * n_det);
+        const size_t o_j = pb.push_vec(plan.jobs);
+        const size_t o_c = pb.push_vec(plan.chunks);
+        const char * dp = pb.commit(st);
+#define CALL(NN)                                                                                                          \
+    hipLaunchKernelGGL(k_gain_add<NN>, dim3((unsigned)plan.chunks.size(), (unsigned)n_det), dim3(kThreads), 0, st, d_det_data, \
+                       n_samp, (const int32_t *)(dp + o_si), d_estimate, (const int32_t *)(dp + o_ei),                      \
+                       (const int64_t *)(dp + o_ao), d_amplitudes, (const BasisJob *)(dp + o_j),                            \
+                       (const BasisChunk *)(dp + o_c), (int)norder)
+        SUBH_DISPATCH(norder, CALL);
+#undef CALL
+        check_launch();
+    });
+}
+
+int toast_hip_gain_project_signal_dev(int64_t norder, const int64_t * amp_offsets, double * d_amplitudes,
+                                      const int32_t * data_index, const double * d_det_data, const int32_t * est_index,
+                                      const double * d_estimate, const int32_t * flag_index, const uint8_t * d_det_flags,
+                                      uint8_t det_flag_mask, int64_t n_det, int64_t n_samp,
+                                      const toast_hip_interval * intervals, int64_t n_view, void * stream) {
+    return guarded([&] {
+        if (n_det <= 0 || n_view <= 0 || n_samp <= 0) return;
+        subh_check(norder, "gain_project_signal");
+        if (n_det > 65535) fail_arg("gain_project_signal: at most 65535 detectors per call");
+        if (d_det_data == nullptr || d_estimate == nullptr || d_amplitudes == nullptr) fail_arg("gain_project_signal: signal, estimate and amplitudes are required");
+        if (d_det_flags != nullptr && flag_index == nullptr) fail_arg("gain_project_signal: detector flags need their row indices");
+        hipStream_t st = as_stream(stream);
+        // (a view without samples has no job: nothing is added to its amplitudes)
+        const BasisPlan plan = basis_plan(intervals, n_view, n_samp, "gain_project_signal");
+        if (plan.chunks.empty()) return;
+        ParamBlock pb;
+        std::vector<int32_t> no_flags(n_det, 0);
+        const size_t o_si = pb.push(data_index, sizeof(int32_t) * n_det);
+        const size_t o_ei = pb.push(est_index, sizeof(int32_t) * n_det);
+        const size_t o_fi = pb.push(d_det_flags != nullptr ? flag_index : no_flags.data(), sizeof(int32_t) * n_det);
+        const size_t o_ao = pb.push(amp_offsets, sizeof(int64_t) * n_det);
+        const size_t o_j = pb.push_vec(plan.jobs);
+        const size_t o_c = pb.push_vec(plan.chunks);
+        const char * dp = pb.commit(st);
+        const int64_t n_chunk = (int64_t)plan.chunks.size();
+#define CALL(NN)                                                                                                              \
+    do {                                                                                                                      \
+        double * partial = static_cast<double *>(                                                                             \
+            Manager::get().scratch(Manager::kScratchTemplate, sizeof(double) * (size_t)(n_det * n_chunk * NN), st));          \
+        hipLaunchKernelGGL((k_gain_partial<NN, false>), dim3((unsigned)n_chunk, (unsigned)n_det), dim3(kThreads), 0, st,      \
+                           d_det_data, n_samp, (const int32_t *)(dp + o_si), d_estimate, (const int32_t *)(dp + o_ei),        \
+                           d_det_flags, (const int32_t *)(dp + o_fi), det_flag_mask, (const BasisJob *)(dp + o_j),            \
+                           (const BasisChunk *)(dp + o_c), n_chunk, partial);                                                 \
+        check_launch();                                                                                                       \
+        hipLaunchKernelGGL((k_gain_combine<NN, false>), dim3((unsigned)plan.jobs.size(), (unsigned)n_det), dim3(64), 0, st,   \
+                           (const BasisJob *)(dp + o_j), n_chunk, (const double *)partial, (int)norder, n_view,               \
+                           (const int64_t *)(dp + o_ao), d_amplitudes, (const double *)nullptr, (double *)nullptr);           \
+    } while (0)
+        SUBH_DISPATCH(norder, CALL);
+#undef CALL
+        check_launch();
+    });
+}
+
+int toast_hip_gain_precond_build_dev(int64_t norder, const int32_t * est_index, const double * d_estimate,
+                                     const double * det_weights, int64_t n_det, int64_t n_samp,
+                                     const toast_hip_interval * intervals, int64_t n_view, double * d_gram, void * stream) {
+    return guarded([&] {
+        if (n_det <= 0 || n_view <= 0 || n_samp <= 0) return;
+        subh_check(norder, "gain_precond_build");
+        if (n_det > 65535) fail_arg("gain_precond_build: at most 65535 detectors per call");
+        if (d_gram == nullptr || d_estimate == nullptr || det_weights == nullptr || est_index == nullptr) fail_arg("gain_precond_build: estimate, weights and output are required");
+        hipStream_t st = as_stream(stream);
+        TH_HIP(hipMemsetAsync(d_gram, 0, sizeof(double) * (size_t)(n_det * n_view * norder * norder), st));     // (an empty view has no job)
+        const BasisPlan plan = basis_plan(intervals, n_view, n_samp, "gain_precond_build");
+        if (plan.chunks.empty()) return;
+        ParamBlock pb;
+        const size_t o_ei = pb.push(est_index, sizeof(int32_t) * n_det);
+        const size_t o_w = pb.push(det_weights, sizeof(double) * n_det);
+        const size_t o_j = pb.push_vec(plan.jobs);
+        const size_t o_c = pb.push_vec(plan.chunks);
+        const char * dp = pb.commit(st);
+        const int64_t n_chunk = (int64_t)plan.chunks.size();
+#define CALL(NN)                                                                                                              \
+    do {                                                                                                                      \
+        constexpr int NV = NN * (NN + 1) / 2;                                                                                 \
+        double * partial = static_cast<double *>(                                                                             \
+            Manager::get().scratch(Manager::kScratchTemplate, sizeof(double) * (size_t)(n_det * n_chunk * NV), st));          \
+        hipLaunchKernelGGL((k_gain_partial<NN, true>), dim3((unsigned)n_chunk, (unsigned)n_det), dim3(kThreads), 0, st,       \
+                           (const double *)nullptr, n_samp, (const int32_t *)nullptr, d_estimate,                             \
+                           (const int32_t *)(dp + o_ei), (const uint8_t *)nullptr, (const int32_t *)nullptr, (uint8_t)0,      \
+                           (const BasisJob *)(dp + o_j), (const BasisChunk *)(dp + o_c), n_chunk, partial);                   \
+        check_launch();                                                                                                       \
+        hipLaunchKernelGGL((k_gain_combine<NN, true>), dim3((unsigned)plan.jobs.size(), (unsigned)n_det), dim3(64), 0, st,    \
+                           (const BasisJob *)(dp + o_j), n_chunk, (const double *)partial, (int)norder, n_view,               \
+                           (const int64_t *)nullptr, (double *)nullptr, (const double *)(dp + o_w), d_gram);                  \
+    } while (0)
+        SUBH_DISPATCH(norder, CALL);
+#undef CALL
         check_launch();
     });
 }

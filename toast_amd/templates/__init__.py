@@ -1,5 +1,6 @@
 """Template amplitudes and the destriping templates: Offset (baselines, below), SubHarmonic (templates/subharmonic.py),
-Periodic (templates/periodic.py) and Fourier2D (templates/fourier2d.py).
+Periodic (templates/periodic.py), Fourier2D (templates/fourier2d.py) and GainTemplate (templates/gaintemplate.py): every
+template class of the reference.
 
 Reference: src/toast/templates/amplitudes.py (Amplitudes, AmplitudesMap),
 src/toast/templates/template.py (Template), src/toast/templates/offset/offset.py (Offset,
@@ -910,5 +911,6 @@ def block_amp_offsets(cache, det_start, obs_dets, per_obs, iob, dets):
 
 
 from .fourier2d import Fourier2D  # noqa: E402
+from .gaintemplate import GainTemplate  # noqa: E402
 from .periodic import Periodic  # noqa: E402
 from .subharmonic import SubHarmonic  # noqa: E402

@@ -8,6 +8,9 @@ in one process:
 * toast_hip_noise_weight_dev over the same rows and views: 16 B per detector-sample read and written, the ceiling of
   the two add_to_signal sweeps; the 8 B (read-only) sweeps are set against half of its bytes at the same rate;
 * toast_hip_subharmonic_add_to_signal_dev / _project_signal_dev / _precond_build_dev, order 1, 3 and 8;
+* toast_hip_gain_add_to_signal_dev (24 B per detector-sample: signal read and written, estimate read),
+  _project_signal_dev (17 B: signal, estimate, one flag byte) and _precond_build_dev (8 B), order 1, 3 and 8, the
+  estimate's rows in another order than the signal's;
 * toast_hip_periodic_add_to_signal_dev and _project_signal_dev (LDS path, and global atomics forced), 100 azimuth bins
   on a shared key;
 * toast_hip_fourier2d_add_to_signal_dev / _project_signal_dev at order 1 and 3 with subharmonics (7 and 39 amplitudes per
@@ -92,6 +95,9 @@ def main(argv=None):
         return {"ms": round(ms, 4), "bytes": nbytes, "tb_s": round(nbytes / ms / 1e9, 3),
                 "rate_vs_ceiling": round(nbytes / ms / ceiling_rate, 3)}
 
+    # the estimate of the GainTemplate sweeps: its rows in another order than the signal's
+    est = 1.0 + 0.1 * torch.randn((n_det, n_samp), dtype=torch.float64, device="cuda", generator=gen)
+    eidx = idx[::-1].copy()
     for order in (1, 3, 8):
         norder = order + 1
         amps = 1.0e-3 * torch.randn(n_det * n_view * norder, dtype=torch.float64, device="cuda", generator=gen)
@@ -106,6 +112,16 @@ def main(argv=None):
                                                        gram.data_ptr(), ngood.data_ptr()))
         out[f"subharmonic_precond_build_order{order}"] = entry(ms, 1 * n_det * covered)
         assert int(ngood.min()) > 0
+        # GainTemplate: the same basis times a second fp64 stream, the estimate, in a buffer of its own
+        gamps = 1.0e-3 * torch.randn(n_det * n_view * norder, dtype=torch.float64, device="cuda", generator=gen)
+        ms = timed(lambda: D.gain_add_to_signal(norder, offs, gamps.data_ptr(), idx, sig.data_ptr(), eidx, est.data_ptr(),
+                                                n_samp, ivl))
+        out[f"gain_add_order{order}"] = entry(ms, 24 * n_det * covered)
+        ms = timed(lambda: D.gain_project_signal(norder, offs, gamps.data_ptr(), idx, sig.data_ptr(), eidx, est.data_ptr(),
+                                                 idx, dflags.data_ptr(), 1, n_samp, ivl))
+        out[f"gain_project_order{order}"] = entry(ms, 17 * n_det * covered)
+        ms = timed(lambda: D.gain_precond_build(norder, eidx, est.data_ptr(), np.ones(n_det), n_samp, ivl, gram.data_ptr()))
+        out[f"gain_precond_build_order{order}"] = entry(ms, 8 * n_det * covered)
     # a shared key swept back and forth like the azimuth of a constant-elevation scan
     key = torch.zeros(n_samp, dtype=torch.float64, device="cuda")
     for first, last in zip(starts, stops):

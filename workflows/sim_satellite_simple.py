@@ -9,10 +9,18 @@ configs[0] (4 detectors x 10 min @ 100 Hz, Nside 64) by default, configs[1] with
     python workflows/sim_satellite_simple.py [--ndet 4] [--minutes 10] [--rate 100] [--nside 64]
                                              [--destripe] [--sim-noise] [--estimate-noise] [--out map.npz]
                                              [--demodulate [--nskip N] [--hwp-rpm R]]
+                                             [--gain-drift ORDER [--noise-free]]
 
 ``--demodulate``: the HWP spins at ``--hwp-rpm`` (default 120, i.e. 2 Hz), a piecewise-constant input sky is scanned into
 the signal, and after the usual (modulated) map the data goes through Demodulate -> StokesWeightsDemod -> the same
 binning / ``--destripe`` map-maker; the residual of both maps against the input sky is printed.
+
+``--gain-drift ORDER``: the input sky is scanned into a detdata key of its own, the *signal estimate*; the signal is
+``estimate * (1 + L a_injected)`` -- a Legendre series of that order per detector, a few per cent -- plus the usual noise
+(none with ``--noise-free``), and the map-maker solves for [Offset, GainTemplate].  Injected and recovered amplitudes are
+printed.  The mean of the order-0 terms over the detectors is degenerate with the map -- a common gain is a brighter sky
+-- so order 0 is reported relative to that mean.  A drift can only be told from the sky where pixels are seen again at
+another time: this run spins once a minute instead of once in ten.
 """
 import argparse
 import os
@@ -26,7 +34,9 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from toast_amd import ops  # noqa: E402
 from toast_amd.data import defaults  # noqa: E402
 from toast_amd.sim import create_satellite_data  # noqa: E402
-from toast_amd.templates import Offset  # noqa: E402
+from toast_amd.templates import GainTemplate, Offset  # noqa: E402
+
+GAIN_ESTIMATE = "gain_estimate"
 
 
 def input_sky(nside):
@@ -36,8 +46,8 @@ def input_sky(nside):
     return np.stack([1.0 + 0.1 * np.sin(0.7 * coarse), 0.05 * np.cos(0.4 * coarse), 0.03 * np.sin(0.9 * coarse + 1.0)], axis=1)
 
 
-def scan_input_sky(data, nside):
-    """Add the input sky to the signal through the pointing the map-maker will use; returns the sky."""
+def scan_input_sky(data, nside, det_data=defaults.det_data):
+    """Add the input sky to ``det_data`` through the pointing the map-maker will use; returns the sky."""
     from toast_amd.accel import ensure_assigned
 
     ensure_assigned()                   # the host-level pointing calls below are staged through the device
@@ -50,7 +60,7 @@ def scan_input_sky(data, nside):
     for ob in data.obs:
         pix, w = ob.detdata[pixels.pixels].data, ob.detdata[weights.weights].data
         seen = pix >= 0
-        ob.detdata[defaults.det_data].data[seen] += np.sum(w[seen] * sky[pix[seen]], axis=1)
+        ob.detdata[det_data].data[seen] += np.sum(w[seen] * sky[pix[seen]], axis=1)
     ops.Delete(detdata=[pixels.pixels, weights.weights, det_pointing.quats]).apply(data)
     return sky
 
@@ -63,6 +73,38 @@ def residual(m, good, sky, dist):
     ok = good.reshape(-1) & np.any(flat != 0, axis=1) & (pix < sky.shape[0])
     return "map - input sky rms  I %.4g  Q %.4g  U %.4g  over %d pixels" % (
         *np.sqrt(np.mean((flat[ok] - sky[pix[ok]]) ** 2, axis=0)), int(np.count_nonzero(ok)))
+
+
+def inject_gain_drift(data, args):
+    """Scan the input sky into the estimate, add ``estimate * (1 + drift)`` to the signal; returns the injected amplitudes
+    [n_det][order + 1] (one observation)."""
+    from toast_amd.templates.subharmonic import legendre_basis
+
+    for ob in data.obs:
+        ob.detdata.create(GAIN_ESTIMATE, dtype=np.float64)
+    scan_input_sky(data, args.nside, det_data=GAIN_ESTIMATE)
+    rng = np.random.default_rng(2)
+    injected = 0.03 * rng.standard_normal((args.ndet, args.gain_drift + 1))
+    for ob in data.obs:
+        basis = legendre_basis(args.gain_drift + 1, ob.n_local_samples)
+        ob.detdata[defaults.det_data].data[:] += ob.detdata[GAIN_ESTIMATE].data * (1.0 + injected @ basis)
+    return injected
+
+
+def report_gain_drift(data, mapper, injected):
+    """Print injected against recovered amplitudes; order 0 relative to its mean over the detectors."""
+    recovered = data["mapmaker_solve_amplitudes"]["gain"].local.reshape(injected.shape).copy()
+    data["gain_drift_injected"], data["gain_drift_recovered"] = injected, recovered
+    data["gain_drift_history"] = np.array(mapper.history)
+    diff = recovered - injected
+    print(f"gain drift: mean over the detectors of recovered - injected order 0 = {diff[:, 0].mean():+.6f} (degenerate with "
+          f"the map: a common gain is a brighter sky; order 0 below is relative to that mean)")
+    diff[:, 0] -= diff[:, 0].mean()
+    for d in range(injected.shape[0]):
+        print(f"gain drift, detector {d}: injected " + " ".join(f"{x:+.6f}" for x in injected[d]) + "   recovered " +
+              " ".join(f"{x:+.6f}" for x in injected[d] + diff[d]))
+    print(f"gain drift: largest error {np.abs(diff).max():.3e}, rms of the injected amplitudes "
+          f"{np.sqrt(np.mean(injected ** 2)):.3e}")
 
 
 def demodulate_and_map(data, args, sky):
@@ -112,23 +154,34 @@ def main(argv=None):
                          "pseudo-detectors; prints both maps' residual against the input sky")
     ap.add_argument("--nskip", type=int, default=3, help="decimation factor of --demodulate")
     ap.add_argument("--hwp-rpm", type=float, default=None, help="HWP rotation rate (9, or 120 with --demodulate)")
+    ap.add_argument("--gain-drift", type=int, default=None, metavar="ORDER",
+                    help="inject a Legendre gain drift of this order per detector on a scanned input sky and solve for "
+                         "[Offset, GainTemplate]; prints injected against recovered amplitudes")
+    ap.add_argument("--noise-free", action="store_true", help="with --gain-drift: no detector noise")
     ap.add_argument("--out", default=None)
     args = ap.parse_args(argv)
+    gain = args.gain_drift is not None
+    if gain and (args.demodulate or args.gain_drift < 0):
+        ap.error("--gain-drift takes an order >= 0 and does not combine with --demodulate")
+    if args.noise_free and not gain:
+        ap.error("--noise-free belongs to --gain-drift")
 
     n_samp = int(args.minutes * 60 * args.rate)
     t0 = time.time()
-    data = create_satellite_data(n_det=args.ndet, n_samp=n_samp, rate=args.rate, spin_period_s=600.0,
+    data = create_satellite_data(n_det=args.ndet, n_samp=n_samp, rate=args.rate, spin_period_s=60.0 if gain else 600.0,
                                  spin_angle_deg=30.0, prec_period_s=3000.0, prec_angle_deg=65.0, net=1.0,
                                  hwp_rpm=args.hwp_rpm if args.hwp_rpm is not None else (120.0 if args.demodulate else 9.0))
     rng = np.random.default_rng(1)
     for ob in data.obs:
         sig = ob.detdata[defaults.det_data].data
-        sig[:] = 0.0 if args.sim_noise else rng.standard_normal(sig.shape)
+        sig[:] = 0.0 if (args.sim_noise or args.noise_free) else rng.standard_normal(sig.shape)
         if args.destripe:
             sig += (rng.standard_normal((sig.shape[0], 1)) * 5.0)  # one offset per detector
     sky = None
     if args.demodulate:
         sky = scan_input_sky(data, args.nside)
+    if gain:
+        injected = inject_gain_drift(data, args)
     if args.sim_noise:
         from toast_amd.accel import accel_enabled
 
@@ -156,8 +209,14 @@ def main(argv=None):
     if args.destripe:
         templates = ops.TemplateMatrix(templates=[Offset(step_time=60.0, noise_model=defaults.noise_model,
                                                          name="baselines")])
-    mapper = ops.MapMaker(name="mapmaker", det_data=defaults.det_data, binning=binner, template_matrix=templates,
-                          iter_max=50, convergence=1e-12)
+    solver = dict(iter_max=50, convergence=1e-12)
+    if gain:
+        templates = ops.TemplateMatrix(templates=[
+            Offset(step_time=60.0, noise_model=defaults.noise_model, name="baselines"),
+            GainTemplate(order=args.gain_drift, template_name=GAIN_ESTIMATE, noise_model=defaults.noise_model, name="gain")])
+        # (the amplitudes are compared with what was injected: solved to rounding, no stall test on the way, and kept)
+        solver = dict(iter_min=100, iter_max=300, convergence=1e-24, keep_solver_products=True)
+    mapper = ops.MapMaker(name="mapmaker", det_data=defaults.det_data, binning=binner, template_matrix=templates, **solver)
     mapper.apply(data)
     dt = time.time() - t0
     hits = data["mapmaker_hits"].data
@@ -167,6 +226,8 @@ def main(argv=None):
           f"local submaps {data['pixel_dist'].n_local_submap}  hit pixels {np.count_nonzero(good)}  "
           f"total hits {int(hits.sum())}  PCG iterations {len(mapper.history)}  wall {dt:.2f} s")
     print("map rms  I %.6g  Q %.6g  U %.6g" % tuple(np.sqrt(np.mean(m[good] ** 2, axis=0))))
+    if gain:
+        report_gain_drift(data, mapper, injected)
     if args.demodulate:
         print("modulated run:   " + residual(m, good, sky, data["pixel_dist"]))
         demodulate_and_map(data, args, sky)
