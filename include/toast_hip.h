@@ -1406,6 +1406,91 @@ int toast_hip_stokes_weights_demod_dev(int64_t n_entry, int64_t n_samp, int64_t 
 int toast_hip_demod_timing(int on, double * phase_ms);
 
 /* ------------------------------------------------------------------------------------
+ * Observing a simulated atmosphere (csrc/atm_observe.hip)
+ * [ref: src/libtoast/src/toast_atm_observe.cpp, src/toast/ops/sim_tod_atm_observe.py].
+ *
+ * The geometry of one simulated slab, the arguments of toast::atm_sim_observe between tod and the three arrays
+ * [ref: toast_atm_observe.cpp:252-284] as one block.  The volume is the compressed index (nn entries: the element of
+ * every cell of the nx x ny x nz box, anything outside [0, nelem) where the cell was not simulated) and the
+ * realization (nelem values).  full_index is not read by the observation. */
+typedef struct toast_hip_atm_geometry {
+    double T0;
+    double azmin, azmax, elmin, elmax, tmin, tmax;
+    double rmin, rmax, fixed_r;
+    double zatm, zmax;
+    double wx, wy, wz;
+    double xstep, ystep, zstep;
+    double xstart, delta_x, ystart, delta_y, zstart, delta_z;
+    double maxdist;
+    int64_t nn, nx, ny, nz;
+    int64_t xstride, ystride, zstride;
+    int64_t nelem;
+} toast_hip_atm_geometry;
+/* toast::atm_sim_observe [ref: toast_atm_observe.cpp:246-488] for n_row rows of n_samp samples in one launch:
+ *     tod[row][i] += T0 xstep sum_steps interp(x, y, z) (1 - z / zatm)
+ * along the line of sight of (az[row][i], el[row][i]) at times[row][i] (time_stride 0: one row of times for all rows;
+ * the strides count doubles).  The steps: r from 1.5 xstep, advanced by repeated r += xstep while r < rmin, or the single
+ * r = fixed_r > 0; the loop ends at r > rmax or r sin(elmax) >= zmax [ref: :359-375]; the point is rotated to the scan
+ * frame by el0 and moved by wind (t - tmin) [ref: :379-394]; interp is toast::atm_sim_interp [ref: :28-244] with its
+ * truncation to ix, iy, iz and its association of the seven lerps.
+ * A sample whose az is not in [azmin, azmax] as given or minus 2 pi, or whose el is not in [elmin, elmax], is skipped
+ * (tod untouched) [ref: :323-343].  Every check of the reference build without NO_ATM_CHECKS is made before the load it
+ * guards -- point outside the box [ref: :397], fractional step outside [0, 1] [ref: :78], ix > nx - 2 and the like
+ * [ref: :98], full index outside [0, nn) [ref: :127], compressed index outside [0, nelem) [ref: :165] --; a failed check
+ * sets the sample's sum to 0 and ends its ray, the sample still receives += 0.  There is no unchecked variant.
+ * *status = 1 when any sample was skipped or failed, else 0 (a device word, read back once per call: the call
+ * synchronises).  d_index: int32 entries with index32 != 0 (nelem < 2^31), else int64.  cell_cache != 0 keeps the
+ * reference's one-cell cache (last_ind / last_nodes) in registers; it starts EMPTY for every ray, the reference's
+ * starts as cell (0, 0, 0) with zero values [ref: :315-316].  Any n_samp >= 1.  No atomics on tod: its bits do not
+ * depend on the batch.  rmin, rmax and xstep must put at most 2^24 steps on a ray. */
+int toast_hip_atm_observe_dev(const toast_hip_atm_geometry * geom, const void * d_index, int index32,
+                              const double * d_realization, int cell_cache, int64_t n_row, int64_t n_samp,
+                              const double * d_times, int64_t time_stride, const double * d_az, const double * d_el,
+                              int64_t angle_stride, double * d_tod, int64_t tod_stride, int * status, void * stream);
+/* The same for one row of host arrays, staged on the device for the call (the reference binding's shape). */
+int toast_hip_atm_observe(const toast_hip_atm_geometry * geom, const int64_t * compressed_index, const double * realization,
+                          int64_t n_samp, const double * times, const double * az, const double * el, double * tod,
+                          int * status);
+/* What ObserveAtmosphere asks of a detector before it observes [ref: sim_tod_atm_observe.py:240-255, :287-294]:
+ * d_good[e][i] = 1 where (det_flags[flag_row[e]][i] & det_flag_mask) | (shared_flags[i] & shared_flag_mask) is 0 (either
+ * flag array may be NULL), and ranges[e][8] (host) = first good sample, last good sample (-1, -1: none), min and max of
+ * el, az of the first good sample, min and max of az - that az wrapped to [-pi, pi), 0 -- with az = 2 pi - phi,
+ * el = pi / 2 - theta of qa_to_angles [ref: src/libtoast/src/toast_math_qarray.cpp:1166-1188] of row quat_row[e] of
+ * d_quats [row][stride][4].  n_samp samples of every row are looked at -- a view of an observation: the row arrays of
+ * this and the following entries (quaternions, flags, weights, detector data) have `stride` samples per row and are
+ * handed in at the view's first sample; d_good, d_atm and the times have n_samp per row.  The call synchronises. */
+int toast_hip_atm_good_ranges_dev(int64_t n_row, int64_t n_samp, int64_t stride, const int32_t * quat_row, const double * d_quats,
+                                  int64_t n_quat_rows, const int32_t * flag_row, const uint8_t * d_det_flags,
+                                  int64_t n_flag_rows, uint8_t det_flag_mask, const uint8_t * d_shared_flags,
+                                  uint8_t shared_flag_mask, uint8_t * d_good, double * ranges, void * stream);
+/* toast_hip_atm_observe_dev with az, el from the quaternions as above, for the samples with d_good[e][i] != 0 only,
+ * accumulating into the scratch rows d_atm [n_row][n_samp]; d_times is one row for all [ref: sim_tod_atm_observe.py:341].
+ * status (host, [n_row]) receives one status per row: the reference observes detector by detector. */
+int toast_hip_atm_observe_quats_dev(const toast_hip_atm_geometry * geom, const void * d_index, int index32,
+                                    const double * d_realization, int cell_cache, int64_t n_row, int64_t n_samp,
+                                    int64_t stride, const double * d_times, const int32_t * quat_row, const double * d_quats,
+                                    int64_t n_quat_rows, const uint8_t * d_good, double * d_atm, int * status,
+                                    void * stream);
+/* After a slab whose status was not 0 [ref: sim_tod_atm_observe.py:379-399]: det_flags[flag_row[e]][i] |= det_flag_mask
+ * where enable[e] != 0 (the slab's status of that detector), d_good[e][i] and |d_atm[e][i]| < 1e-30; n_bad[e] (host)
+ * counts them.  The rows of flag_row are distinct.  The call
+ * synchronises. */
+int toast_hip_atm_flag_failed_dev(int64_t n_row, int64_t n_samp, int64_t stride, const uint8_t * d_good, const double * d_atm,
+                                  const int32_t * flag_row, const int32_t * enable, uint8_t * d_det_flags,
+                                  int64_t n_flag_rows, uint8_t det_flag_mask, int64_t * n_bad, void * stream);
+/* The rest of the per-detector chain, in the reference's order [ref: sim_tod_atm_observe.py:424-483], for the good samples:
+ *     atm = d_atm[e][i] * gain_absorption[e];  atm *= w_I + w_Q * pfrac;  atm += loading[e] / sin(el);
+ *     det_data[data_row[e]][i] += scale * atm
+ * w_I, w_Q: components comp_i, comp_q of row weight_row[e] of d_weights [row][n_samp][nnz] (a component < 0: 0;
+ * d_weights NULL: 1 and 0); loading NULL: no loading term.  gain_absorption and loading are host arrays. */
+int toast_hip_atm_finish_dev(int64_t n_row, int64_t n_samp, int64_t stride, const uint8_t * d_good, const double * d_atm,
+                             const double * gain_absorption, const double * loading, const int32_t * quat_row,
+                             const double * d_quats, int64_t n_quat_rows, const int32_t * weight_row,
+                             const double * d_weights, int64_t n_weight_rows, int64_t nnz, int64_t comp_i, int64_t comp_q,
+                             double pfrac, double scale, const int32_t * data_row, double * d_det_data,
+                             int64_t n_data_rows, void * stream);
+
+/* ------------------------------------------------------------------------------------
  * Deterministic debug mode (TOAST_HIP_DETERMINISTIC=1 in the environment, or this switch).
  * The production A^T kernels add run-reduced partial sums with fp64 atomics, so zmap / the
  * inverse covariance differ from run to run in the last bits.  With the mode on,

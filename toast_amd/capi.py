@@ -697,6 +697,29 @@ class OtfPointing(C.Structure):
 _RNG_HOST = {"uint64": np.uint64, "uniform_01": np.float64, "uniform_11": np.float64, "normal": np.float64}
 
 
+class AtmGeometry(C.Structure):
+    """toast_hip_atm_geometry: the geometry of one simulated atmosphere slab."""
+
+    _fields_ = [(name, C.c_double) for name in (
+        "T0", "azmin", "azmax", "elmin", "elmax", "tmin", "tmax", "rmin", "rmax", "fixed_r", "zatm", "zmax", "wx", "wy",
+        "wz", "xstep", "ystep", "zstep", "xstart", "delta_x", "ystart", "delta_y", "zstart", "delta_z", "maxdist")] + [
+        (name, C.c_int64) for name in ("nn", "nx", "ny", "nz", "xstride", "ystride", "zstride", "nelem")]
+
+
+def atm_observe(geom, compressed_index, realization, times, az, el, tod):
+    """toast::atm_sim_observe on host arrays, staged on the device for the call (toast_hip_atm_observe); returns the
+    status."""
+    ci = _buf(compressed_index, "compressed_index", np.int64, 1, (geom.nn,))
+    re = _buf(realization, "realization", np.float64, 1, (geom.nelem,))
+    t = _buf(times, "times", np.float64, 1)
+    n = t.size
+    a, e, d = _buf(az, "az", np.float64, 1, (n,)), _buf(el, "el", np.float64, 1, (n,)), _buf(tod, "tod", np.float64, 1, (n,))
+    status = C.c_int(0)
+    _check(real_lib().toast_hip_atm_observe(C.byref(geom), _p(ci), _p(re), _i64(n), _p(t), _p(a), _p(e), _p(d),
+                                            C.byref(status)))
+    return int(status.value)
+
+
 def _u64(x):
     x = int(x)
     if x < 0 or x >= 1 << 64:
@@ -2015,6 +2038,73 @@ class _Dev:
         ms = (C.c_double * 4)()
         _check(real_lib().toast_hip_demod_timing(C.c_int(1 if on else 0), ms))
         return tuple(float(x) for x in ms)
+
+    # ---- observing a simulated atmosphere (csrc/atm_observe.hip)
+    def atm_observe(self, geom, d_index, index32, d_realization, n_row, n_samp, d_times, time_stride, d_az, d_el,
+                    angle_stride, d_tod, tod_stride, cell_cache=False, stream=0):
+        """``tod[row] += `` the line-of-sight integral of every (times, az, el) sample of ``n_row`` rows through the
+        volume (``geom``: AtmGeometry); returns the status (1: a sample was skipped or failed).
+        toast_hip_atm_observe_dev."""
+        status = C.c_int(0)
+        _check(real_lib().toast_hip_atm_observe_dev(
+            C.byref(geom), _p(d_index), C.c_int(1 if index32 else 0), _p(d_realization), C.c_int(1 if cell_cache else 0),
+            _i64(n_row), _i64(n_samp), _p(d_times), _i64(time_stride), _p(d_az), _p(d_el), _i64(angle_stride), _p(d_tod),
+            _i64(tod_stride), C.byref(status), _p(stream)))
+        return int(status.value)
+
+    def atm_good_ranges(self, n_samp, stride, quat_row, d_quats, n_quat_rows, flag_row, d_det_flags, n_flag_rows, det_flag_mask,
+                        d_shared_flags, shared_flag_mask, d_good, stream=0):
+        """The good-sample mask of every entry into ``d_good`` and its (first, last, el min, el max, az first, min and max
+        of the wrapped az offset, 0) as an array [n_row][8].  toast_hip_atm_good_ranges_dev."""
+        rq = self._small(quat_row, np.int32)
+        rf = None if flag_row is None else self._small(flag_row, np.int32)
+        ranges = np.zeros((rq.size, 8), dtype=np.float64)
+        _check(real_lib().toast_hip_atm_good_ranges_dev(
+            _i64(rq.size), _i64(n_samp), _i64(stride), _p(rq), _p(d_quats), _i64(n_quat_rows), _p(rf), _p(d_det_flags or None),
+            _i64(n_flag_rows), C.c_uint8(int(det_flag_mask) & 255), _p(d_shared_flags or None),
+            C.c_uint8(int(shared_flag_mask) & 255), _p(d_good), _p(ranges), _p(stream)))
+        return ranges
+
+    def atm_observe_quats(self, geom, d_index, index32, d_realization, n_samp, stride, d_times, quat_row, d_quats,
+                          n_quat_rows, d_good, d_atm, cell_cache=False, stream=0):
+        """``atm_observe`` with az / el from the detector quaternions, good samples only, into the scratch rows
+        ``d_atm``; returns the status of every row.  toast_hip_atm_observe_quats_dev."""
+        rq = self._small(quat_row, np.int32)
+        status = np.zeros(rq.size, dtype=np.int32)
+        _check(real_lib().toast_hip_atm_observe_quats_dev(
+            C.byref(geom), _p(d_index), C.c_int(1 if index32 else 0), _p(d_realization), C.c_int(1 if cell_cache else 0),
+            _i64(rq.size), _i64(n_samp), _i64(stride), _p(d_times), _p(rq), _p(d_quats), _i64(n_quat_rows), _p(d_good),
+            _p(d_atm), _p(status), _p(stream)))
+        return status
+
+    def atm_flag_failed(self, n_samp, stride, d_good, d_atm, flag_row, enable, d_det_flags, n_flag_rows, det_flag_mask,
+                        stream=0):
+        """Raise ``det_flag_mask`` on the good samples whose accumulated atmosphere is still (almost) zero; returns
+        their number per entry; entries with ``enable`` 0 are left alone.  toast_hip_atm_flag_failed_dev."""
+        rf, en = self._small(flag_row, np.int32), self._small(enable, np.int32)
+        if en.size != rf.size:
+            raise RuntimeError("atm_flag_failed: one switch per entry")
+        n_bad = np.zeros(rf.size, dtype=np.int64)
+        _check(real_lib().toast_hip_atm_flag_failed_dev(
+            _i64(rf.size), _i64(n_samp), _i64(stride), _p(d_good), _p(d_atm), _p(rf), _p(en), _p(d_det_flags),
+            _i64(n_flag_rows), C.c_uint8(int(det_flag_mask) & 255), _p(n_bad), _p(stream)))
+        return n_bad
+
+    def atm_finish(self, n_samp, stride, d_good, d_atm, gain_absorption, loading, quat_row, d_quats, n_quat_rows, weight_row,
+                   d_weights, n_weight_rows, nnz, comp_i, comp_q, pfrac, scale, data_row, d_det_data, n_data_rows,
+                   stream=0):
+        """Calibrate, polarize, load and accumulate the scratch rows into the detector data.
+        toast_hip_atm_finish_dev."""
+        ga = self._small(gain_absorption, np.float64)
+        ld = None if loading is None else self._small(loading, np.float64)
+        rq, rd = self._small(quat_row, np.int32), self._small(data_row, np.int32)
+        rw = None if weight_row is None else self._small(weight_row, np.int32)
+        if rq.size != ga.size or rd.size != ga.size or (ld is not None and ld.size != ga.size):
+            raise RuntimeError("atm_finish: one value and one row of each array per entry")
+        _check(lib().toast_hip_atm_finish_dev(
+            _i64(ga.size), _i64(n_samp), _i64(stride), _p(d_good), _p(d_atm), _p(ga), _p(ld), _p(rq), _p(d_quats), _i64(n_quat_rows),
+            _p(rw), _p(d_weights or None), _i64(n_weight_rows), _i64(nnz), _i64(comp_i), _i64(comp_q),
+            C.c_double(float(pfrac)), C.c_double(float(scale)), _p(rd), _p(d_det_data), _i64(n_data_rows), _p(stream)))
 
     def test_math(self, op, n, d_a, d_b, d_out, stream=0):
         _check(lib().toast_hip_test_math_dev(C.c_int(op), _i64(n), _p(d_a), _p(d_b), _p(d_out), _p(stream)))

@@ -1127,4 +1127,39 @@ PYBIND11_MODULE(_libtoast_hip, m) {
                                                  n_weight_rows, single_precision ? 1 : 0, nullptr));
     }, py::arg("n_samp"), py::arg("values"), py::arg("out_row"), py::arg("d_weights"), py::arg("n_weight_rows"),
        py::arg("single_precision"));
+
+    // ---- observing a simulated atmosphere (csrc/atm_observe.hip) under the name, argument order and size checks of
+    // toast._libtoast (src/toast/_libtoast/atm.cpp:208-334); the arrays are staged on the device for the call
+    m.def("atm_sim_observe", [](py::buffer times, py::buffer az, py::buffer el, py::buffer tod, double T0, double azmin,
+                                double azmax, double elmin, double elmax, double tmin, double tmax, double rmin, double rmax,
+                                double fixed_r, double zatm, double zmax, double wx, double wy, double wz, double xstep,
+                                double ystep, double zstep, double xstart, double delta_x, double ystart, double delta_y,
+                                double zstart, double delta_z, double maxdist, int64_t nx, int64_t ny, int64_t nz,
+                                int64_t xstride, int64_t ystride, int64_t zstride, py::buffer compressed_index,
+                                py::buffer full_index, py::buffer realization) {
+        Shape st, sa, se, sd, sc, sf, sr;
+        const double * rt = extract<double>(times, "times", 1, st, {-1});
+        const double * ra = extract<double>(az, "az", 1, sa, {-1});
+        const double * re = extract<double>(el, "el", 1, se, {-1});
+        double * rd = extract<double>(tod, "tod", 1, sd, {-1});
+        const int64_t * rc = extract<int64_t>(compressed_index, "compressed_index", 1, sc, {-1});
+        (void)extract<int64_t>(full_index, "full_index", 1, sf, {-1});
+        const double * rr = extract<double>(realization, "realization", 1, sr, {-1});
+        if (sa[0] != st[0] || se[0] != st[0] || sd[0] != st[0]) {
+            throw std::runtime_error("time domain buffer sizes are not consistent.");
+        }
+        if (sf[0] != sr[0]) throw std::runtime_error("full_index and realization sizes are not consistent.");
+        toast_hip_atm_geometry g{T0, azmin, azmax, elmin, elmax, tmin, tmax, rmin, rmax, fixed_r, zatm, zmax, wx, wy, wz,
+                                 xstep, ystep, zstep, xstart, delta_x, ystart, delta_y, zstart, delta_z, maxdist,
+                                 sc[0], nx, ny, nz, xstride, ystride, zstride, sr[0]};
+        int status = 0;
+        check(toast_hip_atm_observe(&g, rc, rr, st[0], rt, ra, re, rd, &status));
+        return status;
+    }, py::arg("times"), py::arg("az"), py::arg("el"), py::arg("tod"), py::arg("T0"), py::arg("azmin"), py::arg("azmax"),
+       py::arg("elmin"), py::arg("elmax"), py::arg("tmin"), py::arg("tmax"), py::arg("rmin"), py::arg("rmax"),
+       py::arg("fixed_r"), py::arg("zatm"), py::arg("zmax"), py::arg("wx"), py::arg("wy"), py::arg("wz"), py::arg("xstep"),
+       py::arg("ystep"), py::arg("zstep"), py::arg("xstart"), py::arg("delta_x"), py::arg("ystart"), py::arg("delta_y"),
+       py::arg("zstart"), py::arg("delta_z"), py::arg("maxdist"), py::arg("nx"), py::arg("ny"), py::arg("nz"),
+       py::arg("xstride"), py::arg("ystride"), py::arg("zstride"), py::arg("compressed_index"), py::arg("full_index"),
+       py::arg("realization"));
 }

@@ -48,6 +48,7 @@ defaults = types.SimpleNamespace(
     pixels="pixels",
     weights="weights",
     quats="quats",
+    quats_azel="quats_azel",
     noise_model="noise_model",
     shared_mask_invalid=1,
     shared_mask_processing=2,

@@ -2,8 +2,9 @@
 """The structure of BASELINE configs[4] on one GPU's share of the detectors: constant-elevation
 scans (sweeps as intervals, flagged turnarounds), a ground-synchronous signal injected into the
 timestreams, `GroundFilter` (ground-template subtraction), then `MapMaker` at Nside 2048 with
-baseline offsets, everything through the reference's Operator names.  The atmosphere simulation of
-configs[4] is upstream of this path and is not part of it.
+baseline offsets, everything through the reference's Operator names.  `--atmosphere` observes one or
+two STAND-IN atmosphere slabs into the signal with `ObserveAtmosphere` before the filters; generating
+the atmosphere as configs[4] does (GenerateAtmosphere, CHOLMOD) is not part of this path.
 
     python workflows/ground_filter_mapmaker.py [--ndet 256] [--minutes 60] [--rate 200] [--nside 2048]
                                                [--iter 10] [--split] [--filter-order 5] [--trend-order 5]
@@ -11,6 +12,7 @@ configs[4] is upstream of this path and is not part of
                                                [--common-mode] [--save-map FILE]
                                                [--subharmonic ORDER] [--periodic-az BINS] [--fourier2d ORDER]
                                                [--time-constant MS [--time-constant-sigma S]]
+                                               [--atmosphere {1,2}]
 """
 import argparse
 import os
@@ -26,6 +28,41 @@ from toast_amd.accel import native  # noqa: E402
 from toast_amd.data import defaults  # noqa: E402
 from toast_amd.sim import create_ground_data  # noqa: E402
 from toast_amd.templates import Fourier2D, Offset, Periodic, SubHarmonic  # noqa: E402
+
+
+def observe_standin_atmosphere(data, n_slab):
+    """Detector az / el quaternions from the boresight's azimuth and elevation (PointingDetectorSimple on the device),
+    ``n_slab`` stand-in slabs along the line of sight (toast_amd.atm.standin_slab) for one wind interval that spans the
+    observation, then ObserveAtmosphere into the signal."""
+    from toast_amd.atm import azel_to_quat, standin_slab
+
+    edges = np.linspace(0.0, 2000.0, n_slab + 1)
+    sims = {}
+    for ob in data.obs:
+        az, el = ob.shared[defaults.azimuth].data, ob.shared[defaults.elevation].data
+        times = ob.shared[defaults.times].data
+        ob.shared.create(defaults.boresight_azel, azel_to_quat(az, el))
+        ob.intervals.create("wind", [(0, ob.n_local_samples)])
+        half = 0.55 * ob.telescope.focalplane.field_of_view
+        el_lo, el_hi = max(float(el.min()) - half, 0.0), min(float(el.max()) + half, np.pi / 2)
+        az_pad = half / np.cos(el_hi) + 0.01
+        sims[ob.session.name] = [[
+            standin_slab(float(az.min()) - az_pad, float(az.max()) + az_pad, el_lo, el_hi, float(times[0]) - 1.0,
+                         float(times[-1]) + 1.0, rmin=edges[k], rmax=edges[k + 1], seed=100 + k)
+            for k in range(n_slab)]]
+        ob["atm_absorption"] = {d: 1.0 for d in ob.local_detectors}
+    data["atm_sim"] = sims
+    ops.PointingDetectorSimple(boresight=defaults.boresight_azel, quats=defaults.quats_azel, hwp_angle=None,
+                               shared_flags=None, name="pointing_azel").apply(data, use_accel=True)
+    ops.ObserveAtmosphere(absorption="atm_absorption", name="observe_atmosphere").apply(data, use_accel=True)
+    for slabs in sims.values():
+        for sim in slabs[0]:
+            sim.close()
+    for ob in data.obs:
+        del ob.detdata[defaults.quats_azel]
+        if ob.shared[defaults.boresight_azel].accel_exists():
+            ob.shared[defaults.boresight_azel].accel_delete()
+        del ob.shared[defaults.boresight_azel]
 
 
 def main(argv=None):
@@ -73,6 +110,10 @@ def main(argv=None):
                          "ops.TimeConstant(deconvolve=True) before the filters; prints the residual (off by default)")
     ap.add_argument("--time-constant-sigma", type=float, default=0.0, metavar="S",
                     help="with --time-constant: relative Gaussian spread of the time constants across the focal plane")
+    ap.add_argument("--atmosphere", type=int, default=0, choices=(0, 1, 2), metavar="SLABS",
+                    help="observe SLABS (1 or 2) atmosphere slabs into the signal with ops.ObserveAtmosphere before the "
+                         "filters.  The slabs are a STAND-IN, not the reference's generator: a box around the scan cone, "
+                         "cells kept by a cone predicate, a smooth random field from a filtered FFT (off by default)")
     ap.add_argument("--save-map", default=None, metavar="FILE", help="save the binned map as a .npy file")
     args = ap.parse_args(argv)
     n_samp = int(args.minutes * 60 * args.rate)
@@ -117,6 +158,11 @@ def main(argv=None):
         ops.SimNoise(noise_model=defaults.noise_model).apply(data, use_accel=True)
         lap("SimNoise")
         sig = ob.detdata[defaults.det_data].data
+    if args.atmosphere:
+        observe_standin_atmosphere(data, args.atmosphere)
+        lap(f"ObserveAtmosphere ({args.atmosphere} stand-in slab{'s' * (args.atmosphere > 1)}; upload)")
+        sig = ob.detdata[defaults.det_data].data
+        print(f"atmosphere: rms of detector 0 after observing {float(np.std(sig[0])):.2f}")
     if args.time_constant is not None:
         n_keep = min(8, sig.shape[0])
         untouched = np.array(sig[:n_keep])
