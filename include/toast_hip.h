@@ -1491,6 +1491,31 @@ int toast_hip_atm_finish_dev(int64_t n_row, int64_t n_samp, int64_t stride, cons
                              int64_t n_data_rows, void * stream);
 
 /* ------------------------------------------------------------------------------------
+ * sim_dipole: the CMB dipole seen by every detector, accumulated into the detector data straight from the boresight
+ * (csrc/sim_dipole.hip) [ref: src/toast/dipole.py:26-97, src/toast/ops/sim_tod_dipole.py:128-217].  For every sample s
+ * inside an interval and every detector d:
+ *     q   = (shared_flags[s] & mask ? [0,0,0,1] : boresight[s]) * focalplane[d]          (quat_mult's term order)
+ *     dir = the z axis rotated by q / |q|                                                 (qa.rotate)
+ *     v   = solar, velocity[s], or their relativistic sum [dipole.py:54-68] -- whichever of the two pointers are given;
+ *           speed = |v|, v /= speed, beta = speed * 1e3 / c
+ *     dip = cmb * (sqrt(1 - beta^2) / (1 - beta v.dir) - 1)                               freq_hz == 0
+ *           cmb * (bt + fcor bt^2), bt = beta v.dir, fcor = (x / 2)(e^x + 1) / (e^x - 1), x = h freq / (k cmb)   otherwise
+ *     det_data[data_index[d]][s] += scale * dip                                           (scale signed: -scale subtracts)
+ *   focalplane f64[n_det,4] (host); boresight f64[n_samp,4]; data_index i32[n_det] (host, distinct rows < n_data_rows);
+ *   det_data f64[n_data_rows,n_samp]; shared_flags u8[n_flags] (used iff not NULL, n_flags == n_samp and mask != 0);
+ *   velocity f64[n_samp,3] in km/s or NULL; solar f64[3] in km/s (host) or NULL.  Both NULL is an error, reported before
+ *   anything is launched.  Samples outside the intervals and rows not named in data_index are not touched.
+ * A zero speed (a zero velocity row without a solar velocity) divides by zero, as in the reference: NaN.
+ * toast_hip_sim_dipole_det_tile(): the detectors that share one lane's per-sample work (tests straddle it).
+ * ---------------------------------------------------------------------------------- */
+int toast_hip_sim_dipole_dev(
+    const double * focalplane /*host*/, const double * d_boresight, const int32_t * data_index /*host*/, int64_t n_det,
+    double * d_det_data, int64_t n_data_rows, int64_t n_samp, const toast_hip_interval * intervals /*host*/, int64_t n_view,
+    const uint8_t * d_shared_flags, int64_t n_flags, uint8_t shared_flag_mask, const double * d_velocity,
+    const double * solar /*host*/, double cmb_kelvin, double freq_hz, double scale, void * stream);
+int toast_hip_sim_dipole_det_tile(void);
+
+/* ------------------------------------------------------------------------------------
  * Deterministic debug mode (TOAST_HIP_DETERMINISTIC=1 in the environment, or this switch).
  * The production A^T kernels add run-reduced partial sums with fp64 atomics, so zmap / the
  * inverse covariance differ from run to run in the last bits.  With the mode on,

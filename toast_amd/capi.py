@@ -2106,6 +2106,28 @@ class _Dev:
             _p(rw), _p(d_weights or None), _i64(n_weight_rows), _i64(nnz), _i64(comp_i), _i64(comp_q),
             C.c_double(float(pfrac)), C.c_double(float(scale)), _p(rd), _p(d_det_data), _i64(n_data_rows), _p(stream)))
 
+    # ---- CMB dipole timestreams (csrc/sim_dipole.hip)
+    def sim_dipole(self, focalplane, d_boresight, data_index, d_det_data, n_data_rows, n_samp, intervals, d_shared_flags=0,
+                   n_flags=0, mask=0, d_velocity=0, solar=None, cmb=2.72548, freq=0.0, scale=1.0, stream=0):
+        """``det_data[data_index[d], s] += scale * dipole`` for every sample of ``intervals``; ``d_velocity`` (device,
+        [n_samp, 3] km/s) and ``solar`` ([3] km/s) select the orbital, solar or total dipole.  toast_hip_sim_dipole_dev."""
+        fp = self._small(focalplane, np.float64)
+        di = self._small(data_index, np.int32)
+        iv = self._small(intervals, interval_dtype)
+        if fp.ndim != 2 or fp.shape[1] != 4 or fp.shape[0] != di.size:
+            raise RuntimeError("sim_dipole: one [x, y, z, w] quaternion and one row per detector")
+        sol = None if solar is None else self._small(solar, np.float64)
+        if sol is not None and sol.shape != (3,):
+            raise RuntimeError("sim_dipole: the solar velocity has three components")
+        _check(lib().toast_hip_sim_dipole_dev(
+            _p(fp), _p(d_boresight), _p(di), _i64(di.size), _p(d_det_data), _i64(n_data_rows), _i64(n_samp), _p(iv),
+            _i64(iv.size), _p(d_shared_flags or None), _i64(n_flags), _u8(int(mask) & 255), _p(d_velocity or None), _p(sol),
+            C.c_double(float(cmb)), C.c_double(float(freq)), C.c_double(float(scale)), _p(stream)))
+
+    def sim_dipole_det_tile(self):
+        """Detectors that share one lane's per-sample work in the dipole kernel."""
+        return int(real_lib().toast_hip_sim_dipole_det_tile())
+
     def test_math(self, op, n, d_a, d_b, d_out, stream=0):
         _check(lib().toast_hip_test_math_dev(C.c_int(op), _i64(n), _p(d_a), _p(d_b), _p(d_out), _p(stream)))
 

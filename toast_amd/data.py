@@ -60,7 +60,11 @@ defaults = types.SimpleNamespace(
     det_mask_sso=4,
     det_mask_nonscience=1 | 2 | 4,
     det_data_units="K",
+    velocity="velocity",
 )
+
+#: unit_conversion(u.K, units) for the units a timestream is kept in
+KELVIN_TO = {"K": 1.0, "mK": 1.0e3, "uK": 1.0e6, "nK": 1.0e9}
 
 
 # ----------------------------------------------------------------------------- communicator

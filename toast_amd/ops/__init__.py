@@ -26,5 +26,6 @@ from .poly_filter import CommonModeFilter, PolyFilter, PolyFilter2D
 from .pointing import BuildPixelDistribution, PixelsHealpix, PointingDetectorSimple, StokesWeights
 from .sim_ground import SimGround
 from .sim_tod_atm_observe import ObserveAtmosphere
+from .sim_tod_dipole import SimDipole
 from .sim_tod_noise import SimNoise
 from .time_constant import TimeConstant

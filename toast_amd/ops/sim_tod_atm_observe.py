@@ -21,14 +21,11 @@ import numpy as np
 
 from .. import capi
 from ..accel import Resident, accel_data_update_host, accel_enabled, device_scratch
-from ..data import defaults
+from ..data import KELVIN_TO, defaults
 from ..traits import Bool, Float, Int, TraitError, Unicode
 from .operator import Operator
 
 TWOPI = 2 * np.pi
-
-#: unit_conversion(u.K, units) for the units a timestream is kept in
-_KELVIN_TO = {"K": 1.0, "mK": 1.0e3, "uK": 1.0e6, "nK": 1.0e9}
 
 
 def quats_to_azel(quats):
@@ -159,9 +156,9 @@ class ObserveAtmosphere(Operator):
             if len(dets) == 0:
                 continue
             units = ob.detdata[self.det_data].units
-            if units not in _KELVIN_TO:
+            if units not in KELVIN_TO:
                 raise RuntimeError(f"ObserveAtmosphere: no conversion from K to '{units}'")
-            scale = _KELVIN_TO[units]
+            scale = KELVIN_TO[units]
             views = ob.intervals[self.view]
             if len(views) > 1 and self.fade_time is not None:
                 raise NotImplementedError("ObserveAtmosphere: fading between wind views (fade_time) is not implemented")

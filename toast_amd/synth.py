@@ -98,6 +98,22 @@ def satellite_boresight(
     return np.ascontiguousarray(quat_normalize(q))
 
 
+def orbital_velocity(times, speed_kms=29.78, period_s=365.25 * 86400, phase=0.0):
+    """STAND-IN for the telescope's velocity relative to the solar system barycentre, ``[n, 3]`` in km/s, ecliptic
+    coordinates: a circular orbit in the ecliptic plane, ``speed_kms * (-sin a, cos a, 0)`` with
+    ``a = 2 pi t / period_s + phase`` at the ``times`` [s].
+
+    The reference takes the Earth's barycentric velocity from astropy's ephemeris and adds the satellite's own orbit
+    (src/toast/ops/sim_satellite.py); neither is available here.  This has the right size and period and nothing else:
+    no eccentricity, no motion about L2, no inclination."""
+    t = np.asarray(times, dtype=np.float64)
+    a = 2.0 * np.pi * (t / period_s) + phase
+    out = np.zeros(t.shape + (3,), dtype=np.float64)
+    out[..., 0] = -speed_kms * np.sin(a)
+    out[..., 1] = speed_kms * np.cos(a)
+    return out
+
+
 def ground_scan(n_samp, rate, az_min_deg=40.0, az_max_deg=110.0, el_deg=50.0, scan_rate_deg_s=1.0,
                 turnaround_s=2.0, site_lat_deg=-22.96, lst0_deg=30.0, with_azimuth=False):
     """Constant-elevation scan (CES) of a ground telescope: boresight quaternions ``[n_samp, 4]``

@@ -37,6 +37,27 @@ def ref_classes():
     return out
 
 
+class _Units:
+    """``astropy.units`` for the defaults that are quantities: every unit is 1."""
+
+    def __getattr__(self, name):
+        return 1.0
+
+
+def ref_constants(relpath):
+    """The module-level constants of a reference module that evaluate with every unit 1 (``dipole.t_cmb`` ...)."""
+    import types
+
+    found = {}
+    for node in ast.parse(open(os.path.join(REF, relpath)).read()).body:
+        if isinstance(node, ast.Assign) and len(node.targets) == 1 and isinstance(node.targets[0], ast.Name):
+            try:
+                found[node.targets[0].id] = eval(ast.unparse(node.value), {"u": _Units(), "__builtins__": {}}, dict(found))
+            except Exception:
+                pass
+    return types.SimpleNamespace(**found)
+
+
 def ours():
     import toast_amd.ops as ops
     import toast_amd.templates as templates
@@ -67,6 +88,7 @@ def differences():
 
     ref = ref_classes()
     mine = ours()
+    dipole_constants = ref_constants("dipole.py")     # SimDipole's defaults are quantities of toast.dipole
     out = []
     for cname, cls in sorted(mine.items()):
         if cname not in ref:
@@ -84,7 +106,8 @@ def differences():
             odef = inst_traits[tname].default
             # evaluate the reference default where it is a plain literal or a defaults.* name
             try:
-                rval = eval(rdef, {"defaults": defaults, "None": None, "True": True, "False": False}) if rdef else None
+                rval = eval(rdef, {"defaults": defaults, "None": None, "True": True, "False": False, "u": _Units(),
+                                   "dipole": dipole_constants}) if rdef else None
                 known = True
             except Exception:
                 rval, known = rdef, False

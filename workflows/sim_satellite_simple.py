@@ -10,6 +10,7 @@ configs[0] (4 detectors x 10 min @ 100 Hz, Nside 64) by default, configs[1] with
                                              [--destripe] [--sim-noise] [--estimate-noise] [--out map.npz]
                                              [--demodulate [--nskip N] [--hwp-rpm R]]
                                              [--gain-drift ORDER [--noise-free]]
+                                             [--dipole {solar,orbital,total}]
 
 ``--demodulate``: the HWP spins at ``--hwp-rpm`` (default 120, i.e. 2 Hz), a piecewise-constant input sky is scanned into
 the signal, and after the usual (modulated) map the data goes through Demodulate -> StokesWeightsDemod -> the same
@@ -21,6 +22,12 @@ binning / ``--destripe`` map-maker; the residual of both maps against the input 
 printed.  The mean of the order-0 terms over the detectors is degenerate with the map -- a common gain is a brighter sky
 -- so order 0 is reported relative to that mean.  A drift can only be told from the sky where pixels are seen again at
 another time: this run spins once a minute instead of once in ten.
+
+``--dipole MODE``: a STAND-IN telescope velocity (``synth.orbital_velocity``: a circular orbit in the ecliptic plane) is
+stored under ``ob.shared["velocity"]`` and ops.SimDipole adds the CMB dipole -- solar, orbital or both -- to the signal
+before map-making; the rms and the peak of what it added are printed.  With ``--gain-drift`` the dipole goes into the
+signal estimate, ahead of the drift: the signal is ``(sky + dipole) * (1 + drift)`` and the gain is calibrated on sky
+plus dipole, as a satellite's is.
 """
 import argparse
 import os
@@ -75,6 +82,24 @@ def residual(m, good, sky, dist):
         *np.sqrt(np.mean((flat[ok] - sky[pix[ok]]) ** 2, axis=0)), int(np.count_nonzero(ok)))
 
 
+def add_dipole(data, args, det_data):
+    """Store the stand-in velocity, run SimDipole into ``det_data`` and print what it added."""
+    from toast_amd import synth
+    from toast_amd.accel import accel_enabled
+
+    before = []
+    for ob in data.obs:
+        if defaults.velocity not in ob.shared:
+            ob.shared.create(defaults.velocity, synth.orbital_velocity(ob.shared[defaults.times].data))
+        if ob.detdata[det_data].units is None:
+            ob.detdata[det_data].update_units(defaults.det_data_units)
+        before.append(ob.detdata[det_data].data.copy())
+    ops.SimDipole(det_data=det_data, mode=args.dipole, coord="E").apply(data, use_accel=accel_enabled())
+    added = np.concatenate([(ob.detdata[det_data].data - b).reshape(-1) for ob, b in zip(data.obs, before)])
+    print(f"dipole ({args.dipole}, STAND-IN orbit) added to '{det_data}': rms {np.sqrt(np.mean(added ** 2)):.6e} K  "
+          f"peak {np.max(np.abs(added)):.6e} K")
+
+
 def inject_gain_drift(data, args):
     """Scan the input sky into the estimate, add ``estimate * (1 + drift)`` to the signal; returns the injected amplitudes
     [n_det][order + 1] (one observation)."""
@@ -83,6 +108,8 @@ def inject_gain_drift(data, args):
     for ob in data.obs:
         ob.detdata.create(GAIN_ESTIMATE, dtype=np.float64)
     scan_input_sky(data, args.nside, det_data=GAIN_ESTIMATE)
+    if args.dipole:
+        add_dipole(data, args, GAIN_ESTIMATE)
     rng = np.random.default_rng(2)
     injected = 0.03 * rng.standard_normal((args.ndet, args.gain_drift + 1))
     for ob in data.obs:
@@ -158,6 +185,9 @@ def main(argv=None):
                     help="inject a Legendre gain drift of this order per detector on a scanned input sky and solve for "
                          "[Offset, GainTemplate]; prints injected against recovered amplitudes")
     ap.add_argument("--noise-free", action="store_true", help="with --gain-drift: no detector noise")
+    ap.add_argument("--dipole", choices=("solar", "orbital", "total"), default=None,
+                    help="add the CMB dipole with ops.SimDipole from a stand-in orbital velocity before map-making; with "
+                         "--gain-drift it is part of the signal estimate")
     ap.add_argument("--out", default=None)
     args = ap.parse_args(argv)
     gain = args.gain_drift is not None
@@ -182,6 +212,8 @@ def main(argv=None):
         sky = scan_input_sky(data, args.nside)
     if gain:
         injected = inject_gain_drift(data, args)
+    elif args.dipole:
+        add_dipole(data, args, defaults.det_data)
     if args.sim_noise:
         from toast_amd.accel import accel_enabled
 
