@@ -1,4 +1,4 @@
-"""GPU: the GainTemplate kernels (k_gain_* of csrc/template_basis.hip) against tests/golden/gain_template.npz -- the
+"""GPU: the GainTemplate kernels (k_legendre_* of csrc/template_basis.hip) against tests/golden/gain_template.npz -- the
 results of the reference's own methods (tests/golden/make_golden_gain_template.py) on the inputs of
 tests/gain_template_case.py -- through the C ABI and through the class on device-resident buffers.
 
@@ -278,6 +278,50 @@ def test_kernels_short_views_chunk_edges_and_alignment(norder):
     D.gain_precond_build(norder, erows, d_est.ptr, weights, N_SAMP, ivl, d_gram.ptr)
     assert np.array_equal(d_gram.get(), gram)
     for d in (d_sig, d_est, d_amps, d_flags, d_sig2, d_out, d_out2, d_out3, d_gram):
+        d.free()
+
+
+@pytest.mark.parametrize("norder", [1, 2, 9])
+def test_both_legendre_templates_run_the_same_arithmetic(norder):
+    """C ABI.  SubHarmonic and GainTemplate are two policies of one kernel family, so with an estimate that is exactly 1.0,
+    no flags and amplitudes preset to 0.0 GainTemplate's projection and Gram matrices are SubHarmonic's bit for bit:
+    ``1.0 * s`` and ``T_k * 1.0`` are exact, both sum the same lane partials through the same butterflies and wave order,
+    and both add the chunks in chunk order starting from 0.0.  ``add_to_signal`` is not compared: the two round
+    differently there (``s += T_k a_k`` in place against ``s + e * sum``), and each has its own bit-exact test."""
+    from toast_amd import capi
+    from toast_amd.capi import interval_dtype
+
+    D = capi.dev
+    rng = np.random.default_rng(41 + norder)
+    n_det, n_view = 3, len(VIEWS)
+    ivl = np.zeros(n_view, dtype=interval_dtype)
+    ivl["first"], ivl["last"] = [v[0] for v in VIEWS], [v[1] for v in VIEWS]
+    sig0 = rng.standard_normal((n_det, N_SAMP))
+    est0 = np.ones((n_det + 1, N_SAMP))
+    n_amp = n_det * n_view * norder
+    offs = (np.array([2, 0, 1]) * n_view * norder).astype(np.int64)
+    rows = np.array([1, 2, 0], dtype=np.int32)
+    erows = np.array([3, 0, 2], dtype=np.int32)
+    weights = np.array([1.0, 0.5, 4.0])
+    d_sig, d_est = Dev(sig0), Dev(est0)
+    # ---- projection: SubHarmonic assigns (whatever was there), GainTemplate adds onto 0.0
+    d_sub, d_gain = Dev(np.full(n_amp, -7.0)), Dev(np.zeros(n_amp))
+    D.subharmonic_project_signal(norder, offs, d_sub.ptr, rows, d_sig.ptr, N_SAMP, ivl)
+    D.gain_project_signal(norder, offs, d_gain.ptr, rows, d_sig.ptr, erows, d_est.ptr, None, 0, 1, N_SAMP, ivl)
+    sub, gain = d_sub.get(), d_gain.get()
+    assert np.all(sub != -7.0) and np.all(sub != 0.0)
+    assert np.array_equal(gain, sub)
+    # ---- Gram matrices: SubHarmonic without flags counts every sample, GainTemplate never counts
+    d_gsub, d_ggain = Dev(np.full((n_det, n_view, norder, norder), -1.0)), Dev(np.full((n_det, n_view, norder, norder), -2.0))
+    d_ngood = Dev(np.full((n_det, n_view), -1, dtype=np.int64))
+    D.subharmonic_precond_build(norder, None, 0, 0, weights, N_SAMP, ivl, d_gsub.ptr, d_ngood.ptr)
+    D.gain_precond_build(norder, erows, d_est.ptr, weights, N_SAMP, ivl, d_ggain.ptr)
+    gsub, ggain = d_gsub.get(), d_ggain.get()
+    assert np.all(gsub[:, :, 0, 0] == weights[:, None] * np.array([last - first for first, last in VIEWS]))
+    assert np.array_equal(ggain, gsub)
+    assert np.array_equal(d_ngood.get(), np.tile([last - first for first, last in VIEWS], (n_det, 1)))
+    assert np.array_equal(d_sig.get(), sig0) and np.array_equal(d_est.get(), est0)
+    for d in (d_sig, d_est, d_sub, d_gain, d_gsub, d_ggain, d_ngood):
         d.free()
 
 

@@ -1,30 +1,28 @@
-// template_basis.hip -- the kernels behind toast.templates.SubHarmonic and toast.templates.Periodic on the device.
+// template_basis.hip -- the kernels behind toast.templates.SubHarmonic, toast.templates.GainTemplate and
+// toast.templates.Periodic on the device.
 //
-// Reference: src/toast/templates/subharmonic.py:143-236 and src/toast/templates/periodic.py:216-419.  Both templates
-// are pure NumPy there, one detector and one view at a time; here all detectors of an observation go in one launch.
+// Reference: src/toast/templates/subharmonic.py:143-236, src/toast/templates/gaintemplate.py:56-238 and
+// src/toast/templates/periodic.py:216-419.  The templates are pure NumPy there, one detector and one view at a time; here
+// all detectors of an observation go in one launch.
 //
-// SubHarmonic -- the [norder][view_len] Legendre matrix the reference stores per view never exists: each lane
-// evaluates r_i = i * (2 / (L - 1)) - 1 (np.linspace(-1, 1, L): the last sample is exactly 1) and the recurrence
-// T_k = (((2k - 1) r) T_{k-1} - (k - 1) T_{k-2}) / k with a true division, the reference's own operation order, so
-// the basis is the reference's bit for bit (-ffp-contract=off).
-//   k_subh_add        signal[d][view] += sum_k T_k a_k, ascending k, one rounding per product and per add; the
-//                     amplitudes of a (detector, view) are wave-uniform; aligned pairs of samples move as 16 bytes:
-//                     16 B per detector-sample.
-//   k_subh_partial    pass 1 of a_k = sum_i signal_i T_k(r_i) (NO flags, like subharmonic.py:205-218) and of the
-//                     Gram matrix sum_good T_r T_c: lane partials, xor butterflies, the four waves through LDS in wave
-//                     order; one partial vector per chunk of kBasisChunk samples.
-//   k_subh_combine    one thread per output value adds the partials of a (detector, view) in chunk order and ASSIGNS
-//                     the amplitude (or writes the weighted Gram matrix).  No atomics anywhere: order-deterministic.
-//   k_subh_precond    out[block] = P[block] in[block], one thread per output amplitude.
-//
-// GainTemplate (src/toast/templates/gaintemplate.py:56-238) -- the same basis times a per-detector signal estimate, a
-// second fp64 stream per sample with its own buffer and row list.  Same chunks, same two-pass reductions.
-//   k_gain_add        signal[d][i] += est[d][i] * sum_k T_k a_k: 24 B per detector-sample.
-//   k_gain_partial    pass 1 of a_k += sum_unflagged (est_i signal_i) T_k(r_i) (17 B per detector-sample; the flags ARE
-//                     applied and the amplitudes accumulate: the opposite of SubHarmonic, gaintemplate.py:199-220) and of
-//                     the Gram matrix sum_all (T_r est)(T_c est) (NO flags: the reference never uses its `good`, :159-170).
-//   k_gain_combine    adds the partials in chunk order ONTO the amplitude (or writes the weighted Gram matrix).
-//   The block product of the preconditioner is k_subh_precond.
+// SubHarmonic and GainTemplate -- one family of Legendre sweeps.  The [norder][view_len] Legendre matrix the reference
+// stores per view never exists: each lane evaluates r_i = i * (2 / (L - 1)) - 1 (np.linspace(-1, 1, L): the last sample is
+// exactly 1) and the recurrence T_k = (((2k - 1) r) T_{k-1} - (k - 1) T_{k-2}) / k with a true division, the reference's
+// own operation order, so the basis is the reference's bit for bit (-ffp-contract=off).  GainTemplate multiplies the same
+// basis by a per-detector signal estimate, a second fp64 stream per sample with its own buffer and row list.  The two
+// templates differ in six facts, stated by the policies SubHarmonicSweep and GainSweep and decided at compile time; chunks,
+// pair loop, reductions and the Gram write exist once.
+//   k_legendre_add      signal[d][view] += sum_k T_k a_k (GainTemplate: times the estimate); the amplitudes of a
+//                       (detector, view) are wave-uniform; aligned pairs of samples move as 16 bytes: 16 B per
+//                       detector-sample, 24 B with the estimate.
+//   k_legendre_partial  pass 1 of the projection a_k = sum_i w_i T_k(r_i) (w: the signal, or estimate * signal: 17 B per
+//                       detector-sample with estimate and flags) and of the Gram matrix sum_i T_r T_c: lane partials, xor
+//                       butterflies, the four waves through LDS in wave order; one partial vector per chunk of kBasisChunk
+//                       samples.
+//   k_legendre_combine  one thread per output value adds the partials of a (detector, view) in chunk order and assigns or
+//                       accumulates the amplitude (or writes the weighted Gram matrix).  No atomics anywhere:
+//                       order-deterministic.
+//   k_subh_precond      out[block] = P[block] in[block], one thread per output amplitude, for both templates.
 //
 // Periodic -- the bin of every sample is computed once per observation (k_periodic_index: int32((v - min) / incr) in
 // fp64, truncated, clamped to nbins - 1; -1 outside the views and where the key's own flags are set) and cached as an
@@ -41,6 +39,7 @@
 //   k_periodic_precond  out = in * hits where the amplitude is unflagged.
 
 #include <algorithm>
+#include <type_traits>
 
 #include "kernel_common.hpp"
 
@@ -84,25 +83,64 @@ __device__ __forceinline__ void subh_terms(double r, double (&t)[N]) {
     }
 }
 
-// subharmonic.py:200-203: one order after the other
-template <int N>
-__device__ __forceinline__ double subh_add(double s, double r, const double (&amp)[N], int n) {
-    double t[N];
-    subh_terms<N>(r, t);
+// ------------------------------------------------------------------------------------ the two Legendre templates
+// The six facts in which SubHarmonic and GainTemplate differ, each the opposite of the other; every one is decided with
+// `if constexpr` or inlined, so an instantiation neither tests nor reads what its template does not have.
+struct SubHarmonicSweep {
+    static constexpr bool kEstimate = false;          // 1. no estimate stream
+    // 2. subharmonic.py:200-203: one order after the other, onto the signal itself
+    template <int N>
+    static __device__ __forceinline__ double add(double s, double, const double (&t)[N], const double (&amp)[N], int n) {
 #pragma unroll
-    for (int k = 0; k < N; ++k) {
-        if (k < n) s += t[k] * amp[k];
+        for (int k = 0; k < N; ++k) {
+            if (k < n) s += t[k] * amp[k];
+        }
+        return s;
     }
-    return s;
-}
+    static constexpr bool kProjectFlags = false;      // 3. the projection covers ALL samples (subharmonic.py:205-218)
+    static constexpr bool kGramFlags = true;          // 4. sum_good T_r T_c, and the number of good samples (:157-179)
+    static constexpr bool kGramTimesEstimate = false; // 5. the bare basis
+    static constexpr bool kAccumulate = false;        // 6. the amplitude is ASSIGNED (subharmonic.py:217)
+};
 
-template <int N>
-__global__ __launch_bounds__(kThreads) void k_subh_add(double * __restrict__ signal, int64_t n_samp,
-                                                       const int32_t * __restrict__ sig_index,
-                                                       const int64_t * __restrict__ amp_offsets,
-                                                       const double * __restrict__ amplitudes,
-                                                       const BasisJob * __restrict__ jobs,
-                                                       const BasisChunk * __restrict__ chunks, int n) {
+struct GainSweep {
+    static constexpr bool kEstimate = true;           // 1. est[d][i], read next to the signal
+    // 2. gaintemplate.py:182-197: the gain fluctuation sum_k T_k a_k (ascending k, from zero), times the estimate, onto
+    // the signal
+    template <int N>
+    static __device__ __forceinline__ double add(double s, double e, const double (&t)[N], const double (&amp)[N], int n) {
+        double g = 0.0;
+#pragma unroll
+        for (int k = 0; k < N; ++k) {
+            if (k < n) g += t[k] * amp[k];
+        }
+        return s + e * g;
+    }
+    static constexpr bool kProjectFlags = true;       // 3. sum_unflagged (est_i signal_i) T_k (gaintemplate.py:199-220)
+    static constexpr bool kGramFlags = false;         // 4. ALL samples: the reference computes `good` for its
+                                                      //    preconditioner and never uses it (gaintemplate.py:159-170)
+    static constexpr bool kGramTimesEstimate = true;  // 5. sum (T_r est_i)(T_c est_i)
+    static constexpr bool kAccumulate = true;         // 6. ONTO the amplitude already there (gaintemplate.py:220)
+};
+
+// values per chunk.  GRAM = false: the N amplitudes.  GRAM = true: the packed upper triangle of the N x N Gram matrix,
+// then the number of good samples where the template counts them
+template <int N, class P, bool GRAM>
+constexpr int kSweepValues = GRAM ? N * (N + 1) / 2 + (P::kGramFlags ? 1 : 0) : N;
+
+// The signal moves as aligned pairs.  The estimate row lies in another buffer with its own row index, so its pairs may
+// start 8 bytes off a 16-byte boundary: it is read as two adjacent 8-byte values with no alignment promised.  gfx950
+// takes wide loads at 8-byte alignment, and the compiler merges the two into one global_load_dwordx4 (seen in the ISA: one
+// dwordx4 load per stream and one dwordx4 store per pair); either way a wave covers one contiguous range of the estimate.
+template <int N, class P>
+__global__ __launch_bounds__(kThreads) void k_legendre_add(double * __restrict__ signal, int64_t n_samp,
+                                                           const int32_t * __restrict__ sig_index,
+                                                           const double * __restrict__ estimate,
+                                                           const int32_t * __restrict__ est_index,
+                                                           const int64_t * __restrict__ amp_offsets,
+                                                           const double * __restrict__ amplitudes,
+                                                           const BasisJob * __restrict__ jobs,
+                                                           const BasisChunk * __restrict__ chunks, int n) {
     const BasisChunk ch = chunks[blockIdx.x];
     const BasisJob job = jobs[ch.job];
     const int64_t d = blockIdx.y;
@@ -113,7 +151,17 @@ __global__ __launch_bounds__(kThreads) void k_subh_add(double * __restrict__ sig
     const int i0 = ch.chunk * kBasisChunk;
     const int cnt = (i0 + kBasisChunk < job.len) ? kBasisChunk : job.len - i0;
     double * __restrict__ sig = signal + (int64_t)sig_index[d] * n_samp + job.first + i0;
+    const double * __restrict__ est = nullptr;
+    if constexpr (P::kEstimate) est = estimate + (int64_t)est_index[d] * n_samp + job.first + i0;
     const double step = linspace_step(job.len);
+    // one sample of the chunk (never read for SubHarmonic: its add() drops the estimate)
+    auto at = [&](double s, int j) {
+        double e = 0.0;
+        if constexpr (P::kEstimate) e = est[j];
+        double t[N];
+        subh_terms<N>(linspace_r(i0 + j, job.len, step), t);
+        return P::template add<N>(s, e, t, amp, n);
+    };
     // aligned pairs: pad = 1 when the chunk starts on an odd double
     const int pad = (int)((reinterpret_cast<uintptr_t>(sig) >> 3) & 1);
     const int n_pair = (pad + cnt + 1) >> 1;
@@ -121,12 +169,12 @@ __global__ __launch_bounds__(kThreads) void k_subh_add(double * __restrict__ sig
         const int j = 2 * p - pad;     // index inside the chunk of the pair's first sample
         if (j >= 0 && j + 2 <= cnt) {
             double2 v = *reinterpret_cast<const double2 *>(sig + j);
-            v.x = subh_add<N>(v.x, linspace_r(i0 + j, job.len, step), amp, n);
-            v.y = subh_add<N>(v.y, linspace_r(i0 + j + 1, job.len, step), amp, n);
+            v.x = at(v.x, j);
+            v.y = at(v.y, j + 1);
             *reinterpret_cast<double2 *>(sig + j) = v;
         } else {
-            if (j >= 0 && j < cnt) sig[j] = subh_add<N>(sig[j], linspace_r(i0 + j, job.len, step), amp, n);
-            if (j + 1 >= 0 && j + 1 < cnt) sig[j + 1] = subh_add<N>(sig[j + 1], linspace_r(i0 + j + 1, job.len, step), amp, n);
+            if (j >= 0 && j < cnt) sig[j] = at(sig[j], j);
+            if (j + 1 >= 0 && j + 1 < cnt) sig[j + 1] = at(sig[j + 1], j + 1);
         }
     }
 }
@@ -150,17 +198,23 @@ __device__ __forceinline__ void block_totals(const double (&v)[NV], double * wav
     }
 }
 
-// GRAM = false: v[k] = sum signal_i T_k(r_i) over ALL samples of the chunk (N values)
-// GRAM = true:  v = packed upper triangle of sum_good T_r T_c, then the number of good samples (N (N + 1) / 2 + 1 values)
-template <int N, bool GRAM>
-__global__ __launch_bounds__(kThreads) void k_subh_partial(const double * __restrict__ signal, int64_t n_samp,
-                                                           const int32_t * __restrict__ sig_index,
-                                                           const uint8_t * __restrict__ det_flags,
-                                                           const int32_t * __restrict__ flag_index, uint8_t det_mask,
-                                                           const BasisJob * __restrict__ jobs,
-                                                           const BasisChunk * __restrict__ chunks, int64_t n_chunk,
-                                                           double * __restrict__ partial) {
-    constexpr int NV = GRAM ? N * (N + 1) / 2 + 1 : N;
+// GRAM = false: v[k] = sum w_i T_k(r_i) with w = the signal, or estimate * signal
+// GRAM = true:  v = packed upper triangle of sum T_r T_c (the basis times the estimate first where the template says so),
+//               then the number of good samples where it counts them
+// over the samples of the chunk the template's flag facts admit
+template <int N, class P, bool GRAM>
+__global__ __launch_bounds__(kThreads) void k_legendre_partial(const double * __restrict__ signal, int64_t n_samp,
+                                                               const int32_t * __restrict__ sig_index,
+                                                               const double * __restrict__ estimate,
+                                                               const int32_t * __restrict__ est_index,
+                                                               const uint8_t * __restrict__ det_flags,
+                                                               const int32_t * __restrict__ flag_index, uint8_t det_mask,
+                                                               const BasisJob * __restrict__ jobs,
+                                                               const BasisChunk * __restrict__ chunks, int64_t n_chunk,
+                                                               double * __restrict__ partial) {
+    constexpr int NV = kSweepValues<N, P, GRAM>;
+    constexpr bool kFlags = GRAM ? P::kGramFlags : P::kProjectFlags;
+    constexpr bool kEst = GRAM ? P::kGramTimesEstimate : P::kEstimate;
     __shared__ double wave_tot[4 * NV];
     const BasisChunk ch = chunks[blockIdx.x];
     const BasisJob job = jobs[ch.job];
@@ -168,57 +222,68 @@ __global__ __launch_bounds__(kThreads) void k_subh_partial(const double * __rest
     const int i0 = ch.chunk * kBasisChunk;
     const int i1 = (i0 + kBasisChunk < job.len) ? i0 + kBasisChunk : job.len;
     const double step = linspace_step(job.len);
+    const double * __restrict__ est = nullptr;
+    if constexpr (kEst) est = estimate + (int64_t)est_index[d] * n_samp + job.first;
+    const double * __restrict__ sig = nullptr;
+    if constexpr (!GRAM) sig = signal + (int64_t)sig_index[d] * n_samp + job.first;
+    const uint8_t * __restrict__ fl = nullptr;
+    if constexpr (kFlags) fl = (det_flags != nullptr) ? det_flags + (int64_t)flag_index[d] * n_samp + job.first : nullptr;
     double v[NV];
 #pragma unroll
     for (int k = 0; k < NV; ++k) v[k] = 0.0;
-    if constexpr (GRAM) {
-        const uint8_t * __restrict__ fl =
-            (det_flags != nullptr) ? det_flags + (int64_t)flag_index[d] * n_samp + job.first : nullptr;
-        for (int i = i0 + threadIdx.x; i < i1; i += kThreads) {
+    for (int i = i0 + threadIdx.x; i < i1; i += kThreads) {
+        if constexpr (kFlags) {
             if (fl != nullptr && (fl[i] & det_mask) != 0) continue;
-            double t[N];
+        }
+        double e = 0.0;
+        if constexpr (kEst) e = est[i];
+        double t[N];
+        if constexpr (GRAM) {
             subh_terms<N>(linspace_r(i, job.len, step), t);
+            if constexpr (kEst) {
+#pragma unroll
+                for (int k = 0; k < N; ++k) t[k] *= e;
+            }
             int q = 0;
 #pragma unroll
             for (int r = 0; r < N; ++r) {
 #pragma unroll
                 for (int c = r; c < N; ++c) v[q++] += t[r] * t[c];
             }
-            v[NV - 1] += 1.0;
-        }
-    } else {
-        const double * __restrict__ sig = signal + (int64_t)sig_index[d] * n_samp + job.first;
-        for (int i = i0 + threadIdx.x; i < i1; i += kThreads) {
-            const double s = sig[i];
-            double t[N];
+            if constexpr (kFlags) v[NV - 1] += 1.0;
+        } else {
+            double w = sig[i];
+            if constexpr (kEst) w = e * w;
             subh_terms<N>(linspace_r(i, job.len, step), t);
 #pragma unroll
-            for (int k = 0; k < N; ++k) v[k] += s * t[k];
+            for (int k = 0; k < N; ++k) v[k] += w * t[k];
         }
     }
     block_totals<NV>(v, wave_tot, partial + ((int64_t)d * n_chunk + blockIdx.x) * NV);
 }
 
-// grid (views, detectors): thread k < n adds the partials of its value in chunk order.
-// GRAM = false: amplitudes[amp_offsets[d] + view * n + k] = total (assigned, subharmonic.py:217)
-// GRAM = true:  gram[(d * n_view + view)][r][c] = gram[..][c][r] = total * weight[d]; ngood[d * n_view + view]
-template <int N, bool GRAM>
-__global__ __launch_bounds__(64) void k_subh_combine(const BasisJob * __restrict__ jobs, int64_t n_chunk,
-                                                     const double * __restrict__ partial, int n, int64_t n_view,
-                                                     const int64_t * __restrict__ amp_offsets,
-                                                     double * __restrict__ amplitudes,
-                                                     const double * __restrict__ weights, double * __restrict__ gram,
-                                                     int64_t * __restrict__ ngood) {
-    constexpr int NV = GRAM ? N * (N + 1) / 2 + 1 : N;
+// grid (views, detectors): thread k adds the partials of its value in chunk order.
+// GRAM = false: amplitudes[amp_offsets[d] + view * n + k] = total, or += total: onto the value already there
+// GRAM = true:  gram[(d * n_view + view)][r][c] = gram[..][c][r] = total * weight[d]; ngood[d * n_view + view] where counted
+template <int N, class P, bool GRAM>
+__global__ __launch_bounds__(64) void k_legendre_combine(const BasisJob * __restrict__ jobs, int64_t n_chunk,
+                                                         const double * __restrict__ partial, int n, int64_t n_view,
+                                                         const int64_t * __restrict__ amp_offsets,
+                                                         double * __restrict__ amplitudes,
+                                                         const double * __restrict__ weights, double * __restrict__ gram,
+                                                         int64_t * __restrict__ ngood) {
+    constexpr int NV = kSweepValues<N, P, GRAM>;
     const BasisJob job = jobs[blockIdx.x];
     const int64_t d = blockIdx.y;
     const double * __restrict__ p = partial + ((int64_t)d * n_chunk + job.chunk0) * NV;
     for (int k = threadIdx.x; k < NV; k += 64) {
-        double t = 0.0;
-        for (int c = 0; c < job.n_chunk; ++c) t += p[(int64_t)c * NV + k];
         if constexpr (GRAM) {
+            double t = 0.0;
+            for (int c = 0; c < job.n_chunk; ++c) t += p[(int64_t)c * NV + k];
             const int64_t blk = d * n_view + job.view;
-            if (k == NV - 1) {
+            bool count = false;
+            if constexpr (P::kGramFlags) count = (k == NV - 1);
+            if (count) {
                 ngood[blk] = (int64_t)t;
             } else {
                 // packed index k of the N x N upper triangle -> (r, c)
@@ -235,7 +300,13 @@ __global__ __launch_bounds__(64) void k_subh_combine(const BasisJob * __restrict
                 }
             }
         } else {
-            if (k < n) amplitudes[amp_offsets[d] + (int64_t)job.view * n + k] = t;
+            if (k < n) {
+                double * __restrict__ a = amplitudes + amp_offsets[d] + (int64_t)job.view * n + k;
+                double t = 0.0;
+                if constexpr (P::kAccumulate) t = *a;
+                for (int c = 0; c < job.n_chunk; ++c) t += p[(int64_t)c * NV + k];
+                *a = t;
+            }
         }
     }
 }
@@ -251,160 +322,6 @@ __global__ __launch_bounds__(kThreads) void k_subh_precond(int n, int64_t n_amp,
         double acc = 0.0;
         for (int c = 0; c < n; ++c) acc += row[c] * x[c];
         amp_out[i] = acc;
-    }
-}
-
-// ------------------------------------------------------------------------------------ gain template
-// gaintemplate.py:182-197: the gain fluctuation sum_k T_k a_k (ascending k, from zero), times the estimate, onto the signal
-template <int N>
-__device__ __forceinline__ double gain_add(double s, double e, double r, const double (&amp)[N], int n) {
-    double t[N];
-    subh_terms<N>(r, t);
-    double g = 0.0;
-#pragma unroll
-    for (int k = 0; k < N; ++k) {
-        if (k < n) g += t[k] * amp[k];
-    }
-    return s + e * g;
-}
-
-// The signal moves as aligned pairs like k_subh_add.  The estimate row lies in another buffer with its own row index,
-// so its pairs may start 8 bytes off a 16-byte boundary: it is read as two adjacent 8-byte values with no alignment
-// promised.  gfx950 takes wide loads at 8-byte alignment, and the compiler merges the two into one global_load_dwordx4
-// (seen in the ISA: one dwordx4 load per stream and one dwordx4 store per pair); either way a wave covers one contiguous
-// range of the estimate.
-template <int N>
-__global__ __launch_bounds__(kThreads) void k_gain_add(double * __restrict__ signal, int64_t n_samp,
-                                                       const int32_t * __restrict__ sig_index,
-                                                       const double * __restrict__ estimate,
-                                                       const int32_t * __restrict__ est_index,
-                                                       const int64_t * __restrict__ amp_offsets,
-                                                       const double * __restrict__ amplitudes,
-                                                       const BasisJob * __restrict__ jobs,
-                                                       const BasisChunk * __restrict__ chunks, int n) {
-    const BasisChunk ch = chunks[blockIdx.x];
-    const BasisJob job = jobs[ch.job];
-    const int64_t d = blockIdx.y;
-    const double * __restrict__ arow = amplitudes + amp_offsets[d] + (int64_t)job.view * n;
-    double amp[N];
-#pragma unroll
-    for (int k = 0; k < N; ++k) amp[k] = (k < n) ? arow[k] : 0.0;
-    const int i0 = ch.chunk * kBasisChunk;
-    const int cnt = (i0 + kBasisChunk < job.len) ? kBasisChunk : job.len - i0;
-    double * __restrict__ sig = signal + (int64_t)sig_index[d] * n_samp + job.first + i0;
-    const double * __restrict__ est = estimate + (int64_t)est_index[d] * n_samp + job.first + i0;
-    const double step = linspace_step(job.len);
-    const int pad = (int)((reinterpret_cast<uintptr_t>(sig) >> 3) & 1);
-    const int n_pair = (pad + cnt + 1) >> 1;
-    for (int p = threadIdx.x; p < n_pair; p += kThreads) {
-        const int j = 2 * p - pad;
-        if (j >= 0 && j + 2 <= cnt) {
-            double2 v = *reinterpret_cast<const double2 *>(sig + j);
-            const double ex = est[j], ey = est[j + 1];
-            v.x = gain_add<N>(v.x, ex, linspace_r(i0 + j, job.len, step), amp, n);
-            v.y = gain_add<N>(v.y, ey, linspace_r(i0 + j + 1, job.len, step), amp, n);
-            *reinterpret_cast<double2 *>(sig + j) = v;
-        } else {
-            if (j >= 0 && j < cnt) sig[j] = gain_add<N>(sig[j], est[j], linspace_r(i0 + j, job.len, step), amp, n);
-            if (j + 1 >= 0 && j + 1 < cnt) {
-                sig[j + 1] = gain_add<N>(sig[j + 1], est[j + 1], linspace_r(i0 + j + 1, job.len, step), amp, n);
-            }
-        }
-    }
-}
-
-// GRAM = false: v[k] = sum (est_i signal_i) T_k(r_i) over the UNFLAGGED samples of the chunk (gaintemplate.py:199-220)
-// GRAM = true:  v = packed upper triangle of sum (T_r est_i)(T_c est_i) over ALL samples of the chunk: the reference
-//               computes `good` for its preconditioner and never uses it (gaintemplate.py:159-170)
-template <int N, bool GRAM>
-__global__ __launch_bounds__(kThreads) void k_gain_partial(const double * __restrict__ signal, int64_t n_samp,
-                                                           const int32_t * __restrict__ sig_index,
-                                                           const double * __restrict__ estimate,
-                                                           const int32_t * __restrict__ est_index,
-                                                           const uint8_t * __restrict__ det_flags,
-                                                           const int32_t * __restrict__ flag_index, uint8_t det_mask,
-                                                           const BasisJob * __restrict__ jobs,
-                                                           const BasisChunk * __restrict__ chunks, int64_t n_chunk,
-                                                           double * __restrict__ partial) {
-    constexpr int NV = GRAM ? N * (N + 1) / 2 : N;
-    __shared__ double wave_tot[4 * NV];
-    const BasisChunk ch = chunks[blockIdx.x];
-    const BasisJob job = jobs[ch.job];
-    const int64_t d = blockIdx.y;
-    const int i0 = ch.chunk * kBasisChunk;
-    const int i1 = (i0 + kBasisChunk < job.len) ? i0 + kBasisChunk : job.len;
-    const double step = linspace_step(job.len);
-    const double * __restrict__ est = estimate + (int64_t)est_index[d] * n_samp + job.first;
-    double v[NV];
-#pragma unroll
-    for (int k = 0; k < NV; ++k) v[k] = 0.0;
-    if constexpr (GRAM) {
-        for (int i = i0 + threadIdx.x; i < i1; i += kThreads) {
-            const double e = est[i];
-            double t[N];
-            subh_terms<N>(linspace_r(i, job.len, step), t);
-#pragma unroll
-            for (int k = 0; k < N; ++k) t[k] *= e;
-            int q = 0;
-#pragma unroll
-            for (int r = 0; r < N; ++r) {
-#pragma unroll
-                for (int c = r; c < N; ++c) v[q++] += t[r] * t[c];
-            }
-        }
-    } else {
-        const double * __restrict__ sig = signal + (int64_t)sig_index[d] * n_samp + job.first;
-        const uint8_t * __restrict__ fl =
-            (det_flags != nullptr) ? det_flags + (int64_t)flag_index[d] * n_samp + job.first : nullptr;
-        for (int i = i0 + threadIdx.x; i < i1; i += kThreads) {
-            if (fl != nullptr && (fl[i] & det_mask) != 0) continue;
-            const double w = est[i] * sig[i];
-            double t[N];
-            subh_terms<N>(linspace_r(i, job.len, step), t);
-#pragma unroll
-            for (int k = 0; k < N; ++k) v[k] += w * t[k];
-        }
-    }
-    block_totals<NV>(v, wave_tot, partial + ((int64_t)d * n_chunk + blockIdx.x) * NV);
-}
-
-// grid (views, detectors): thread k adds the partials of its value in chunk order.
-// GRAM = false: amplitudes[amp_offsets[d] + view * n + k] += total: onto the value already there (gaintemplate.py:220)
-// GRAM = true:  gram[(d * n_view + view)][r][c] = gram[..][c][r] = total * weight[d]
-template <int N, bool GRAM>
-__global__ __launch_bounds__(64) void k_gain_combine(const BasisJob * __restrict__ jobs, int64_t n_chunk,
-                                                     const double * __restrict__ partial, int n, int64_t n_view,
-                                                     const int64_t * __restrict__ amp_offsets,
-                                                     double * __restrict__ amplitudes,
-                                                     const double * __restrict__ weights, double * __restrict__ gram) {
-    constexpr int NV = GRAM ? N * (N + 1) / 2 : N;
-    const BasisJob job = jobs[blockIdx.x];
-    const int64_t d = blockIdx.y;
-    const double * __restrict__ p = partial + ((int64_t)d * n_chunk + job.chunk0) * NV;
-    for (int k = threadIdx.x; k < NV; k += 64) {
-        if constexpr (GRAM) {
-            double t = 0.0;
-            for (int c = 0; c < job.n_chunk; ++c) t += p[(int64_t)c * NV + k];
-            int r = 0, rem = k;
-            while (rem >= N - r) {
-                rem -= N - r;
-                ++r;
-            }
-            const int c = r + rem;
-            if (c < n) {
-                const int64_t blk = d * n_view + job.view;
-                const double g = t * weights[d];
-                gram[blk * n * n + r * n + c] = g;
-                gram[blk * n * n + c * n + r] = g;
-            }
-        } else {
-            if (k < n) {
-                double * __restrict__ a = amplitudes + amp_offsets[d] + (int64_t)job.view * n + k;
-                double t = *a;
-                for (int c = 0; c < job.n_chunk; ++c) t += p[(int64_t)c * NV + k];
-                *a = t;
-            }
-        }
     }
 }
 
@@ -623,6 +540,7 @@ __global__ __launch_bounds__(kThreads) void k_periodic_precond(int64_t n_amp, co
 struct BasisPlan {
     std::vector<BasisJob> jobs;
     std::vector<BasisChunk> chunks;
+    std::vector<int64_t> empty_views;     // views without a sample inside [0, n_samp): no job
 };
 
 BasisPlan basis_plan(const toast_hip_interval * ivl, int64_t n_view, int64_t n_samp, const char * what) {
@@ -631,7 +549,10 @@ BasisPlan basis_plan(const toast_hip_interval * ivl, int64_t n_view, int64_t n_s
         const int64_t first = ivl[v].first < 0 ? 0 : ivl[v].first;
         const int64_t last = ivl[v].last > n_samp ? n_samp : ivl[v].last;
         const int64_t len = last - first;
-        if (len <= 0) continue;
+        if (len <= 0) {
+            p.empty_views.push_back(v);
+            continue;
+        }
         if (len >= (int64_t(1) << 31)) fail_arg(std::string(what) + ": a view of 2^31 samples or more");
         BasisJob job{first, (int32_t)len, (int32_t)v, (int32_t)p.chunks.size(), (int32_t)((len + kBasisChunk - 1) / kBasisChunk)};
         for (int32_t c = 0; c < job.n_chunk; ++c) p.chunks.push_back(BasisChunk{(int32_t)p.jobs.size(), c});
@@ -649,16 +570,97 @@ void subh_check(int64_t norder, const char * what) {
 }
 
 // N = 2, 4 or 9 terms compiled; the runtime count n <= N
-#define SUBH_DISPATCH(norder, CALL) \
-    do {                            \
-        if ((norder) <= 2) {        \
-            CALL(2);                \
-        } else if ((norder) <= 4) { \
-            CALL(4);                \
-        } else {                    \
-            CALL(9);                \
-        }                           \
-    } while (0)
+template <class F>
+void dispatch_terms(int64_t norder, F && launch) {
+    if (norder <= 2) {
+        launch(std::integral_constant<int, 2>{});
+    } else if (norder <= 4) {
+        launch(std::integral_constant<int, 4>{});
+    } else {
+        launch(std::integral_constant<int, 9>{});
+    }
+}
+
+// The per-detector lists of one call; a list the call does not have stays nullptr.
+struct BasisRows {
+    const int32_t * sig = nullptr;          // row of each detector in the signal buffer
+    const int32_t * est = nullptr;          // ... in the estimate buffer
+    const int32_t * flags = nullptr;        // ... in the flag buffer
+    const int64_t * amp_offsets = nullptr;
+    const double * weights = nullptr;
+};
+
+// One call of a kernel that walks the chunks of a view list: the stream, the plan, the device copies of the lists and the
+// launches of the Legendre family.
+struct BasisLaunch {
+    hipStream_t st;
+    int64_t n_det, n_samp, n_view;
+    BasisPlan plan;
+    BasisRows rows;                         // on the device, after upload()
+    const BasisJob * jobs = nullptr;
+    const BasisChunk * chunks = nullptr;
+    std::vector<int32_t> zeros;             // storage of flag_rows()'s stand-in until upload()
+
+    BasisLaunch(hipStream_t stream, const toast_hip_interval * ivl, int64_t n_view_, int64_t n_samp_, int64_t n_det_,
+                const char * what)
+        : st(stream), n_det(n_det_), n_samp(n_samp_), n_view(n_view_), plan(basis_plan(ivl, n_view_, n_samp_, what)) {}
+
+    bool empty() const { return plan.chunks.empty(); }
+    dim3 chunk_grid() const { return dim3((unsigned)plan.chunks.size(), (unsigned)n_det); }
+    dim3 view_grid() const { return dim3((unsigned)plan.jobs.size(), (unsigned)n_det); }
+
+    // the flag rows, or a stand-in when there are no flags: the kernels get a valid pointer they never follow
+    const int32_t * flag_rows(const uint8_t * d_det_flags, const int32_t * flag_index) {
+        if (d_det_flags != nullptr) return flag_index;
+        zeros.assign((size_t)n_det, 0);
+        return zeros.data();
+    }
+
+    void upload(const BasisRows & host) {
+        ParamBlock pb;
+        constexpr size_t none = ~size_t(0);
+        auto push = [&](const auto * list) { return list != nullptr ? pb.push(list, sizeof(*list) * (size_t)n_det) : none; };
+        const size_t o_si = push(host.sig), o_ei = push(host.est), o_fi = push(host.flags), o_ao = push(host.amp_offsets),
+                     o_w = push(host.weights);
+        const size_t o_j = pb.push_vec(plan.jobs), o_c = pb.push_vec(plan.chunks);
+        const char * dp = pb.commit(st);
+        auto at = [&](size_t off, auto & ptr) {
+            ptr = (off != none) ? reinterpret_cast<std::remove_reference_t<decltype(ptr)>>(dp + off) : nullptr;
+        };
+        at(o_si, rows.sig); at(o_ei, rows.est); at(o_fi, rows.flags); at(o_ao, rows.amp_offsets); at(o_w, rows.weights);
+        at(o_j, jobs); at(o_c, chunks);
+    }
+
+    // signal += basis * amplitudes of template P
+    template <class P>
+    void add(int64_t norder, double * signal, const double * estimate, const double * amplitudes) {
+        dispatch_terms(norder, [&](auto terms) {
+            hipLaunchKernelGGL((k_legendre_add<decltype(terms)::value, P>), chunk_grid(), dim3(kThreads), 0, st, signal, n_samp,
+                               rows.sig, estimate, rows.est, rows.amp_offsets, amplitudes, jobs, chunks, (int)norder);
+        });
+        check_launch();
+    }
+
+    // The two-pass reduction of template P.  GRAM = false: the projection of `signal` into `amplitudes`; GRAM = true: the
+    // weighted Gram matrices into `gram` (and `ngood`).  A stream the pass does not have is nullptr.
+    template <class P, bool GRAM>
+    void reduce(int64_t norder, const double * signal, const double * estimate, const uint8_t * det_flags, uint8_t det_mask,
+                double * amplitudes, double * gram, int64_t * ngood) {
+        dispatch_terms(norder, [&](auto terms) {
+            constexpr int N = decltype(terms)::value;
+            const int64_t n_chunk = (int64_t)plan.chunks.size();
+            double * partial = static_cast<double *>(Manager::get().scratch(
+                Manager::kScratchTemplate, sizeof(double) * (size_t)(n_det * n_chunk * kSweepValues<N, P, GRAM>), st));
+            hipLaunchKernelGGL((k_legendre_partial<N, P, GRAM>), chunk_grid(), dim3(kThreads), 0, st, signal, n_samp, rows.sig,
+                               estimate, rows.est, det_flags, rows.flags, det_mask, jobs, chunks, n_chunk, partial);
+            check_launch();
+            hipLaunchKernelGGL((k_legendre_combine<N, P, GRAM>), view_grid(), dim3(64), 0, st, jobs, n_chunk,
+                               (const double *)partial, (int)norder, n_view, rows.amp_offsets, amplitudes, rows.weights, gram,
+                               ngood);
+        });
+        check_launch();
+    }
+};
 
 inline dim3 periodic_grid(int64_t n_samp, int64_t n_det) {
     return dim3((unsigned)((n_samp + kPeriodicChunk - 1) / kPeriodicChunk), (unsigned)n_det);
@@ -685,22 +687,12 @@ int toast_hip_subharmonic_add_to_signal_dev(int64_t norder, const int64_t * amp_
         subh_check(norder, "subharmonic_add_to_signal");
         if (n_det > 65535) fail_arg("subharmonic_add_to_signal: at most 65535 detectors per call");
         if ((reinterpret_cast<uintptr_t>(d_det_data) & 15) != 0) fail_arg("subharmonic_add_to_signal: the signal must be 16-byte aligned");
-        hipStream_t st = as_stream(stream);
-        const BasisPlan plan = basis_plan(intervals, n_view, n_samp, "subharmonic_add_to_signal");
-        if (plan.chunks.empty()) return;
-        ParamBlock pb;
-        const size_t o_si = pb.push(data_index, sizeof(int32_t) * n_det);
-        const size_t o_ao = pb.push(amp_offsets, sizeof(int64_t) * n_det);
-        const size_t o_j = pb.push_vec(plan.jobs);
-        const size_t o_c = pb.push_vec(plan.chunks);
-        const char * dp = pb.commit(st);
-#define CALL(NN)                                                                                                          \
-    hipLaunchKernelGGL(k_subh_add<NN>, dim3((unsigned)plan.chunks.size(), (unsigned)n_det), dim3(kThreads), 0, st, d_det_data, \
-                       n_samp, (const int32_t *)(dp + o_si), (const int64_t *)(dp + o_ao), d_amplitudes,                    \
-                       (const BasisJob *)(dp + o_j), (const BasisChunk *)(dp + o_c), (int)norder)
-        SUBH_DISPATCH(norder, CALL);
-#undef CALL
-        check_launch();
+        BasisLaunch call(as_stream(stream), intervals, n_view, n_samp, n_det, "subharmonic_add_to_signal");
+        if (call.empty()) return;
+        BasisRows rows;
+        rows.sig = data_index; rows.amp_offsets = amp_offsets;
+        call.upload(rows);
+        call.add<SubHarmonicSweep>(norder, d_det_data, nullptr, d_amplitudes);
     });
 }
 
@@ -712,42 +704,18 @@ int toast_hip_subharmonic_project_signal_dev(int64_t norder, const int64_t * amp
         if (n_det <= 0 || n_view <= 0 || n_samp <= 0) return;
         subh_check(norder, "subharmonic_project_signal");
         if (n_det > 65535) fail_arg("subharmonic_project_signal: at most 65535 detectors per call");
-        hipStream_t st = as_stream(stream);
-        const BasisPlan plan = basis_plan(intervals, n_view, n_samp, "subharmonic_project_signal");
+        BasisLaunch call(as_stream(stream), intervals, n_view, n_samp, n_det, "subharmonic_project_signal");
         // a view without samples has no job: its amplitudes are the empty sum (np.dot of empty arrays), assigned like the rest
-        for (int64_t v = 0; v < n_view; ++v) {
-            const int64_t first = intervals[v].first < 0 ? 0 : intervals[v].first;
-            const int64_t last = intervals[v].last > n_samp ? n_samp : intervals[v].last;
-            if (last > first) continue;
+        for (const int64_t v : call.plan.empty_views) {
             for (int64_t d = 0; d < n_det; ++d) {
-                TH_HIP(hipMemsetAsync(d_amplitudes + amp_offsets[d] + v * norder, 0, sizeof(double) * (size_t)norder, st));
+                TH_HIP(hipMemsetAsync(d_amplitudes + amp_offsets[d] + v * norder, 0, sizeof(double) * (size_t)norder, call.st));
             }
         }
-        if (plan.chunks.empty()) return;
-        ParamBlock pb;
-        const size_t o_si = pb.push(data_index, sizeof(int32_t) * n_det);
-        const size_t o_ao = pb.push(amp_offsets, sizeof(int64_t) * n_det);
-        const size_t o_j = pb.push_vec(plan.jobs);
-        const size_t o_c = pb.push_vec(plan.chunks);
-        const char * dp = pb.commit(st);
-        const int64_t n_chunk = (int64_t)plan.chunks.size();
-#define CALL(NN)                                                                                                              \
-    do {                                                                                                                      \
-        double * partial = static_cast<double *>(                                                                             \
-            Manager::get().scratch(Manager::kScratchTemplate, sizeof(double) * (size_t)(n_det * n_chunk * NN), st));          \
-        hipLaunchKernelGGL((k_subh_partial<NN, false>), dim3((unsigned)n_chunk, (unsigned)n_det), dim3(kThreads), 0, st,      \
-                           d_det_data, n_samp, (const int32_t *)(dp + o_si), (const uint8_t *)nullptr,                        \
-                           (const int32_t *)nullptr, (uint8_t)0, (const BasisJob *)(dp + o_j),                                \
-                           (const BasisChunk *)(dp + o_c), n_chunk, partial);                                                 \
-        check_launch();                                                                                                       \
-        hipLaunchKernelGGL((k_subh_combine<NN, false>), dim3((unsigned)plan.jobs.size(), (unsigned)n_det), dim3(64), 0, st,   \
-                           (const BasisJob *)(dp + o_j), n_chunk, (const double *)partial, (int)norder, n_view,               \
-                           (const int64_t *)(dp + o_ao), d_amplitudes, (const double *)nullptr, (double *)nullptr,            \
-                           (int64_t *)nullptr);                                                                               \
-    } while (0)
-        SUBH_DISPATCH(norder, CALL);
-#undef CALL
-        check_launch();
+        if (call.empty()) return;
+        BasisRows rows;
+        rows.sig = data_index; rows.amp_offsets = amp_offsets;
+        call.upload(rows);
+        call.reduce<SubHarmonicSweep, false>(norder, d_det_data, nullptr, nullptr, 0, d_amplitudes, nullptr, nullptr);
     });
 }
 
@@ -764,33 +732,12 @@ int toast_hip_subharmonic_precond_build_dev(int64_t norder, const int32_t * flag
         hipStream_t st = as_stream(stream);
         TH_HIP(hipMemsetAsync(d_gram, 0, sizeof(double) * (size_t)(n_det * n_view * norder * norder), st));
         TH_HIP(hipMemsetAsync(d_ngood, 0, sizeof(int64_t) * (size_t)(n_det * n_view), st));     // (an empty view has no job)
-        const BasisPlan plan = basis_plan(intervals, n_view, n_samp, "subharmonic_precond_build");
-        if (plan.chunks.empty()) return;
-        ParamBlock pb;
-        std::vector<int32_t> no_flags(n_det, 0);
-        const size_t o_fi = pb.push(d_det_flags != nullptr ? flag_index : no_flags.data(), sizeof(int32_t) * n_det);
-        const size_t o_w = pb.push(det_weights, sizeof(double) * n_det);
-        const size_t o_j = pb.push_vec(plan.jobs);
-        const size_t o_c = pb.push_vec(plan.chunks);
-        const char * dp = pb.commit(st);
-        const int64_t n_chunk = (int64_t)plan.chunks.size();
-#define CALL(NN)                                                                                                              \
-    do {                                                                                                                      \
-        constexpr int NV = NN * (NN + 1) / 2 + 1;                                                                             \
-        double * partial = static_cast<double *>(                                                                             \
-            Manager::get().scratch(Manager::kScratchTemplate, sizeof(double) * (size_t)(n_det * n_chunk * NV), st));          \
-        hipLaunchKernelGGL((k_subh_partial<NN, true>), dim3((unsigned)n_chunk, (unsigned)n_det), dim3(kThreads), 0, st,       \
-                           (const double *)nullptr, n_samp, (const int32_t *)nullptr, d_det_flags,                            \
-                           (const int32_t *)(dp + o_fi), det_flag_mask, (const BasisJob *)(dp + o_j),                         \
-                           (const BasisChunk *)(dp + o_c), n_chunk, partial);                                                 \
-        check_launch();                                                                                                       \
-        hipLaunchKernelGGL((k_subh_combine<NN, true>), dim3((unsigned)plan.jobs.size(), (unsigned)n_det), dim3(64), 0, st,    \
-                           (const BasisJob *)(dp + o_j), n_chunk, (const double *)partial, (int)norder, n_view,               \
-                           (const int64_t *)nullptr, (double *)nullptr, (const double *)(dp + o_w), d_gram, d_ngood);         \
-    } while (0)
-        SUBH_DISPATCH(norder, CALL);
-#undef CALL
-        check_launch();
+        BasisLaunch call(st, intervals, n_view, n_samp, n_det, "subharmonic_precond_build");
+        if (call.empty()) return;
+        BasisRows rows;
+        rows.flags = call.flag_rows(d_det_flags, flag_index); rows.weights = det_weights;
+        call.upload(rows);
+        call.reduce<SubHarmonicSweep, true>(norder, nullptr, nullptr, d_det_flags, det_flag_mask, nullptr, d_gram, d_ngood);
     });
 }
 
@@ -816,24 +763,12 @@ int toast_hip_gain_add_to_signal_dev(int64_t norder, const int64_t * amp_offsets
         if (n_det > 65535) fail_arg("gain_add_to_signal: at most 65535 detectors per call");
         if (d_det_data == nullptr || d_estimate == nullptr || d_amplitudes == nullptr) fail_arg("gain_add_to_signal: signal, estimate and amplitudes are required");
         if ((reinterpret_cast<uintptr_t>(d_det_data) & 7) != 0 || (reinterpret_cast<uintptr_t>(d_estimate) & 7) != 0) fail_arg("gain_add_to_signal: signal and estimate must be 8-byte aligned");
-        hipStream_t st = as_stream(stream);
-        const BasisPlan plan = basis_plan(intervals, n_view, n_samp, "gain_add_to_signal");
-        if (plan.chunks.empty()) return;
-        ParamBlock pb;
-        const size_t o_si = pb.push(data_index, sizeof(int32_t) * n_det);
-        const size_t o_ei = pb.push(est_index, sizeof(int32_t) * n_det);
-        const size_t o_ao = pb.push(amp_offsets, sizeof(int64_t) * n_det);
-        const size_t o_j = pb.push_vec(plan.jobs);
-        const size_t o_c = pb.push_vec(plan.chunks);
-        const char * dp = pb.commit(st);
-#define CALL(NN)                                                                                                          \
-    hipLaunchKernelGGL(k_gain_add<NN>, dim3((unsigned)plan.chunks.size(), (unsigned)n_det), dim3(kThreads), 0, st, d_det_data, \
-                       n_samp, (const int32_t *)(dp + o_si), d_estimate, (const int32_t *)(dp + o_ei),                      \
-                       (const int64_t *)(dp + o_ao), d_amplitudes, (const BasisJob *)(dp + o_j),                            \
-                       (const BasisChunk *)(dp + o_c), (int)norder)
-        SUBH_DISPATCH(norder, CALL);
-#undef CALL
-        check_launch();
+        BasisLaunch call(as_stream(stream), intervals, n_view, n_samp, n_det, "gain_add_to_signal");
+        if (call.empty()) return;
+        BasisRows rows;
+        rows.sig = data_index; rows.est = est_index; rows.amp_offsets = amp_offsets;
+        call.upload(rows);
+        call.add<GainSweep>(norder, d_det_data, d_estimate, d_amplitudes);
     });
 }
 
@@ -848,36 +783,14 @@ int toast_hip_gain_project_signal_dev(int64_t norder, const int64_t * amp_offset
         if (n_det > 65535) fail_arg("gain_project_signal: at most 65535 detectors per call");
         if (d_det_data == nullptr || d_estimate == nullptr || d_amplitudes == nullptr) fail_arg("gain_project_signal: signal, estimate and amplitudes are required");
         if (d_det_flags != nullptr && flag_index == nullptr) fail_arg("gain_project_signal: detector flags need their row indices");
-        hipStream_t st = as_stream(stream);
         // (a view without samples has no job: nothing is added to its amplitudes)
-        const BasisPlan plan = basis_plan(intervals, n_view, n_samp, "gain_project_signal");
-        if (plan.chunks.empty()) return;
-        ParamBlock pb;
-        std::vector<int32_t> no_flags(n_det, 0);
-        const size_t o_si = pb.push(data_index, sizeof(int32_t) * n_det);
-        const size_t o_ei = pb.push(est_index, sizeof(int32_t) * n_det);
-        const size_t o_fi = pb.push(d_det_flags != nullptr ? flag_index : no_flags.data(), sizeof(int32_t) * n_det);
-        const size_t o_ao = pb.push(amp_offsets, sizeof(int64_t) * n_det);
-        const size_t o_j = pb.push_vec(plan.jobs);
-        const size_t o_c = pb.push_vec(plan.chunks);
-        const char * dp = pb.commit(st);
-        const int64_t n_chunk = (int64_t)plan.chunks.size();
-#define CALL(NN)                                                                                                              \
-    do {                                                                                                                      \
-        double * partial = static_cast<double *>(                                                                             \
-            Manager::get().scratch(Manager::kScratchTemplate, sizeof(double) * (size_t)(n_det * n_chunk * NN), st));          \
-        hipLaunchKernelGGL((k_gain_partial<NN, false>), dim3((unsigned)n_chunk, (unsigned)n_det), dim3(kThreads), 0, st,      \
-                           d_det_data, n_samp, (const int32_t *)(dp + o_si), d_estimate, (const int32_t *)(dp + o_ei),        \
-                           d_det_flags, (const int32_t *)(dp + o_fi), det_flag_mask, (const BasisJob *)(dp + o_j),            \
-                           (const BasisChunk *)(dp + o_c), n_chunk, partial);                                                 \
-        check_launch();                                                                                                       \
-        hipLaunchKernelGGL((k_gain_combine<NN, false>), dim3((unsigned)plan.jobs.size(), (unsigned)n_det), dim3(64), 0, st,   \
-                           (const BasisJob *)(dp + o_j), n_chunk, (const double *)partial, (int)norder, n_view,               \
-                           (const int64_t *)(dp + o_ao), d_amplitudes, (const double *)nullptr, (double *)nullptr);           \
-    } while (0)
-        SUBH_DISPATCH(norder, CALL);
-#undef CALL
-        check_launch();
+        BasisLaunch call(as_stream(stream), intervals, n_view, n_samp, n_det, "gain_project_signal");
+        if (call.empty()) return;
+        BasisRows rows;
+        rows.sig = data_index; rows.est = est_index; rows.amp_offsets = amp_offsets;
+        rows.flags = call.flag_rows(d_det_flags, flag_index);
+        call.upload(rows);
+        call.reduce<GainSweep, false>(norder, d_det_data, d_estimate, d_det_flags, det_flag_mask, d_amplitudes, nullptr, nullptr);
     });
 }
 
@@ -891,32 +804,12 @@ int toast_hip_gain_precond_build_dev(int64_t norder, const int32_t * est_index, 
         if (d_gram == nullptr || d_estimate == nullptr || det_weights == nullptr || est_index == nullptr) fail_arg("gain_precond_build: estimate, weights and output are required");
         hipStream_t st = as_stream(stream);
         TH_HIP(hipMemsetAsync(d_gram, 0, sizeof(double) * (size_t)(n_det * n_view * norder * norder), st));     // (an empty view has no job)
-        const BasisPlan plan = basis_plan(intervals, n_view, n_samp, "gain_precond_build");
-        if (plan.chunks.empty()) return;
-        ParamBlock pb;
-        const size_t o_ei = pb.push(est_index, sizeof(int32_t) * n_det);
-        const size_t o_w = pb.push(det_weights, sizeof(double) * n_det);
-        const size_t o_j = pb.push_vec(plan.jobs);
-        const size_t o_c = pb.push_vec(plan.chunks);
-        const char * dp = pb.commit(st);
-        const int64_t n_chunk = (int64_t)plan.chunks.size();
-#define CALL(NN)                                                                                                              \
-    do {                                                                                                                      \
-        constexpr int NV = NN * (NN + 1) / 2;                                                                                 \
-        double * partial = static_cast<double *>(                                                                             \
-            Manager::get().scratch(Manager::kScratchTemplate, sizeof(double) * (size_t)(n_det * n_chunk * NV), st));          \
-        hipLaunchKernelGGL((k_gain_partial<NN, true>), dim3((unsigned)n_chunk, (unsigned)n_det), dim3(kThreads), 0, st,       \
-                           (const double *)nullptr, n_samp, (const int32_t *)nullptr, d_estimate,                             \
-                           (const int32_t *)(dp + o_ei), (const uint8_t *)nullptr, (const int32_t *)nullptr, (uint8_t)0,      \
-                           (const BasisJob *)(dp + o_j), (const BasisChunk *)(dp + o_c), n_chunk, partial);                   \
-        check_launch();                                                                                                       \
-        hipLaunchKernelGGL((k_gain_combine<NN, true>), dim3((unsigned)plan.jobs.size(), (unsigned)n_det), dim3(64), 0, st,    \
-                           (const BasisJob *)(dp + o_j), n_chunk, (const double *)partial, (int)norder, n_view,               \
-                           (const int64_t *)nullptr, (double *)nullptr, (const double *)(dp + o_w), d_gram);                  \
-    } while (0)
-        SUBH_DISPATCH(norder, CALL);
-#undef CALL
-        check_launch();
+        BasisLaunch call(st, intervals, n_view, n_samp, n_det, "gain_precond_build");
+        if (call.empty()) return;
+        BasisRows rows;
+        rows.est = est_index; rows.weights = det_weights;
+        call.upload(rows);
+        call.reduce<GainSweep, true>(norder, nullptr, d_estimate, nullptr, 0, nullptr, d_gram, nullptr);
     });
 }
 
@@ -929,15 +822,11 @@ int toast_hip_periodic_index_dev(const double * d_key, const uint8_t * d_flags, 
         if (!(incr != 0.0)) fail_arg("periodic_index: the bin increment is zero");
         hipStream_t st = as_stream(stream);
         TH_HIP(hipMemsetAsync(d_index, 0xff, sizeof(int32_t) * (size_t)(n_row * n_samp), st));     // -1: no bin
-        const BasisPlan plan = basis_plan(intervals, n_view, n_samp, "periodic_index");
-        if (plan.chunks.empty()) return;
-        ParamBlock pb;
-        const size_t o_j = pb.push_vec(plan.jobs);
-        const size_t o_c = pb.push_vec(plan.chunks);
-        const char * dp = pb.commit(st);
-        hipLaunchKernelGGL(k_periodic_index, dim3((unsigned)plan.chunks.size(), (unsigned)n_row), dim3(kThreads), 0, st, d_key,
-                           n_samp, d_flags, flag_mask, n_samp, obs_min, incr, (int32_t)nbins, (const BasisJob *)(dp + o_j),
-                           (const BasisChunk *)(dp + o_c), d_index);
+        BasisLaunch call(st, intervals, n_view, n_samp, n_row, "periodic_index");
+        if (call.empty()) return;
+        call.upload(BasisRows{});
+        hipLaunchKernelGGL(k_periodic_index, call.chunk_grid(), dim3(kThreads), 0, st, d_key, n_samp, d_flags, flag_mask, n_samp,
+                           obs_min, incr, (int32_t)nbins, call.jobs, call.chunks, d_index);
         check_launch();
     });
 }

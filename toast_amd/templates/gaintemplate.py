@@ -7,7 +7,7 @@ detector by observation, then by view, ``order + 1`` values per view.  No amplit
 
 Two paths.  The host path is NumPy.  The device path (``add_to_signal_multi`` / ``project_signal_multi``, what
 ``TemplateMatrix`` looks for, ``_apply_precond`` on resident vectors, and the Gram matrices at set-up when the accelerator
-is on) runs the k_gain_* kernels of csrc/template_basis.hip, which evaluate the basis per sample and never store it.
+is on) runs the Legendre sweeps of csrc/template_basis.hip, which evaluate the basis per sample and never store it.
 
 What the reference does, reproduced on both paths -- each the opposite of SubHarmonic:
 
@@ -40,24 +40,22 @@ import numpy as np
 
 from ..accel import accel_device_ptr, device_scratch
 from ..traits import Int, Unicode
-from . import Amplitudes, DeviceMirror, Template, make_resident, release_borrowed
-from .subharmonic import legendre_basis
+from . import make_resident, release_borrowed
+from .legendre import LegendreBlocks
 
 
-class GainTemplate(Template):
+class GainTemplate(LegendreBlocks):
     """Gain drifts: ``order + 1`` Legendre amplitudes per detector and view, multiplying the signal estimate."""
 
     order = Int(1, help="The order of Legendre polynomials to fit the gain amplitudes")
     template_name = Unicode(None, allow_none=True, help="detdata key encoding the signal estimate to fit the gain amplitudes")
     noise_model = Unicode(None, allow_none=True, help="Observation key containing the noise model")
 
-    # inverse of the weighted Gram matrix of every (detector, observation, view) block, in amplitude order
-    _precond = property(lambda self: self._mirrors["precond"].host)
+    _label = "GainTemplate"
 
     def __init__(self, **kwargs):
         self._borrowed = []      # estimates the sweeps uploaded, and those of them they had to register
         self._created = []
-        self._templates = {}
         super().__init__(**kwargs)
 
     # ------------------------------------------------------------------ set-up
@@ -69,26 +67,14 @@ class GainTemplate(Template):
             raise RuntimeError("GainTemplate: the order must not be negative")
         if self.template_name is None:
             raise RuntimeError(f"GainTemplate {self.name}: template_name (the detdata key of the signal estimate) is not set")
-        norder = self.order + 1
-        all_dets = {}
-        self._obs_dets = {}
-        for iob, ob in enumerate(new_data.obs):
+        for ob in new_data.obs:
             if self.template_name not in ob.detdata:
                 raise RuntimeError(f"GainTemplate {self.name}: observation {ob.name} has no detdata '{self.template_name}' "
                                    f"(the signal estimate)")
             self._check_float64(ob, self.template_name)
             if self.det_data in ob.detdata:
                 self._check_float64(ob, self.det_data)
-            dets = self._obs_detectors(ob, also_in=(self.template_name,))
-            self._obs_dets[iob] = set(dets)
-            all_dets.update(dict.fromkeys(dets))
-        self._all_dets = list(all_dets.keys())
-        self._obs_nview = {iob: len(ob.intervals[self.view]) for iob, ob in enumerate(new_data.obs)}
-        self._layout_detector_major(new_data.comm, {iob: n * norder for iob, n in self._obs_nview.items()})
-        self._templates = {}
-        self._mirrors["precond"] = DeviceMirror(np.zeros((self._n_local // norder, norder, norder), dtype=np.float64),
-                                                f"{self.name}_precond")
-        if self._n_local == 0:
+        if not self._layout_blocks(new_data, also_in=(self.template_name,)):
             return
         if accel_enabled() and self.supports_accel():
             gram = self._gram_device(new_data)
@@ -100,22 +86,6 @@ class GainTemplate(Template):
         if ob.detdata[key].buffer.dtype != np.float64:
             raise RuntimeError(f"GainTemplate {self.name}: detdata '{key}' of observation {ob.name} must be float64, "
                                f"it is {ob.detdata[key].buffer.dtype}")
-
-    @staticmethod
-    def _max_terms():
-        from .. import capi
-
-        return capi.dev.subharmonic_max_terms()
-
-    def _view_templates(self, iob, ob):
-        """The basis of every view of one observation, built on first use by the host path."""
-        if iob not in self._templates:
-            self._templates[iob] = [legendre_basis(self.order + 1, int(vw.last - vw.first)) for vw in ob.intervals[self.view]]
-        return self._templates[iob]
-
-    def _blocks(self, iob, dets):
-        """First block (amplitude index / norder) of each detector for observation ``iob``."""
-        return self.det_amp_offsets(iob, dets) // (self.order + 1)
 
     def _gram_host(self, new_data):
         """gaintemplate.py:159-170 for every block, the estimate sliced to the view -> [n_block][norder][norder]."""
@@ -155,8 +125,7 @@ class GainTemplate(Template):
                                                 ob.intervals[self.view].data, s.ptr("gram"))
             finally:
                 release_borrowed(borrowed)
-            for k, blk in enumerate(self._blocks(iob, dets)):
-                gram[blk:blk + n_view] = g[k]
+            self._scatter_blocks(iob, dets, g, gram)
         return gram
 
     def _block_samples(self, new_data):
@@ -184,44 +153,9 @@ class GainTemplate(Template):
             raise np.linalg.LinAlgError(f"GainTemplate {self.name}: {self._describe_block(new_data, int(null[0]))} has a "
                                         f"signal estimate that is zero everywhere ({null.size} such blocks): its "
                                         f"preconditioner is singular")
-        try:
-            self._precond[:] = np.linalg.inv(gram)
-        except np.linalg.LinAlgError:
-            for blk in range(gram.shape[0]):
-                try:
-                    np.linalg.inv(gram[blk])
-                except np.linalg.LinAlgError as err:
-                    raise np.linalg.LinAlgError(f"GainTemplate {self.name}: {self._describe_block(new_data, blk)} has a "
-                                                f"singular preconditioner") from err
-            raise
-        if not np.all(np.isfinite(self._precond)):
-            bad = int(np.flatnonzero(~np.isfinite(self._precond).all(axis=(1, 2)))[0])
-            raise np.linalg.LinAlgError(f"GainTemplate {self.name}: {self._describe_block(new_data, bad)} has a "
-                                        f"preconditioner that is not finite")
-
-    def _describe_block(self, new_data, blk):
-        norder = self.order + 1
-        for det in self._all_dets:
-            off = self._det_start[det] // norder
-            for iob, ob in enumerate(new_data.obs):
-                if det not in self._obs_dets[iob]:
-                    continue
-                if blk < off + self._obs_nview[iob]:
-                    return f"detector {det}, observation {ob.name}, view {blk - off}"
-                off += self._obs_nview[iob]
-        return f"block {blk}"
+        self._invert_blocks(new_data, gram)
 
     # ------------------------------------------------------------------ Template interface
-    def _detectors(self):
-        return self._all_dets
-
-    def _zeros(self):
-        # no explicit flagging of amplitudes in this template (gaintemplate.py:176-180)
-        return Amplitudes(self.data.comm, self._n_global, self._n_local)
-
-    def _supports_accel(self):
-        return self.order + 1 <= self._max_terms()
-
     def _estimate_args(self, ob, dets):
         """(rows of ``dets`` in the estimate, its device pointer); resident from the first sweep until ``clear()``."""
         est = self._resident_estimate(ob, self._borrowed)
@@ -255,7 +189,7 @@ class GainTemplate(Template):
                                          self.det_flag_mask, ob.n_local_samples, ob.intervals[self.view].data)
 
     def _add_to_signal_host(self, detector, amplitudes):
-        """gaintemplate.py:182-197 with an explicit ascending-k sum: the statement of k_gain_add, bit for bit."""
+        """gaintemplate.py:182-197 with an explicit ascending-k sum: the statement of k_legendre_add, bit for bit."""
         norder = self.order + 1
         offset = self._det_start[detector]
         local = amplitudes.local
@@ -291,26 +225,6 @@ class GainTemplate(Template):
                 local[offset:offset + norder] += np.dot(lt, row[vw.first:vw.last] * mask)
                 offset += norder
 
-    def _add_prior(self, amplitudes_in, amplitudes_out, **kwargs):
-        return      # no prior for this template (gaintemplate.py:222-224)
-
-    def _apply_precond(self, amplitudes_in, amplitudes_out, use_accel=None, **kwargs):
-        if self._n_local == 0:
-            return
-        norder = self.order + 1
-        if amplitudes_in.accel_in_use() or amplitudes_out.accel_in_use():
-            from .. import capi
-
-            amplitudes_in.accel_resident()
-            amplitudes_out.accel_resident()
-            # (the block product of SubHarmonic: the same kernel)
-            capi.dev.subharmonic_apply_precond(norder, self._n_local // norder, self._mirrors["precond"].upload().ptr,
-                                               accel_device_ptr(amplitudes_in.buffer), accel_device_ptr(amplitudes_out.buffer))
-            return
-        # gaintemplate.py:226-238: one small dense product per block
-        a_in = amplitudes_in.local.reshape(-1, norder)
-        amplitudes_out.local.reshape(-1, norder)[:] = np.einsum("brc,bc->br", self._precond, a_in)
-
     def clear(self):
         """Release the device copy of the preconditioner, hand back what the sweeps made resident, drop the host basis."""
         super().clear()
@@ -319,4 +233,3 @@ class GainTemplate(Template):
             if est.accel_exists():
                 est.accel_delete()          # (only read: the host copy is the current one)
         self._created = []
-        self._templates = {}

@@ -21,32 +21,18 @@ import numpy as np
 from ..accel import accel_device_ptr, device_scratch
 from ..data import defaults
 from ..traits import Int, Unicode
-from . import Amplitudes, DeviceMirror, Template, release_borrowed
+from . import release_borrowed
+from .legendre import LegendreBlocks, legendre_basis  # noqa: F401  (legendre_basis: imported from here by its users)
 
 
-def legendre_basis(norder, view_len):
-    """[norder][view_len] templates of one view: subharmonic.py:143-155, the same array expressions."""
-    templates = np.zeros((norder, view_len), dtype=np.float64)
-    r = np.linspace(-1.0, 1.0, view_len)
-    for order in range(norder):
-        if order == 0:
-            templates[order] = 1.0
-        elif order == 1:
-            templates[order] = r
-        else:
-            templates[order] = ((2 * order - 1) * r * templates[order - 1] - (order - 1) * templates[order - 2]) / order
-    return templates
-
-
-class SubHarmonic(Template):
+class SubHarmonic(LegendreBlocks):
     """Noise fluctuations slower than the length of a view: ``order + 1`` Legendre amplitudes per detector and view."""
 
     times = Unicode(defaults.times, help="Observation shared key for timestamps")
     order = Int(1, help="The filter order")
     noise_model = Unicode(None, allow_none=True, help="Observation key containing the optional noise model")
 
-    # inverse of the weighted Gram matrix of every (detector, observation, view) block, in amplitude order
-    _precond = property(lambda self: self._mirrors["precond"].host)
+    _label = "SubHarmonic template"
 
     # ------------------------------------------------------------------ set-up
     def _initialize(self, new_data):
@@ -55,20 +41,7 @@ class SubHarmonic(Template):
         self.clear()
         if self.order < 0:
             raise RuntimeError("SubHarmonic: the order must not be negative")
-        norder = self.order + 1
-        all_dets = {}
-        self._obs_dets = {}
-        for iob, ob in enumerate(new_data.obs):
-            dets = self._obs_detectors(ob)
-            self._obs_dets[iob] = set(dets)
-            all_dets.update(dict.fromkeys(dets))
-        self._all_dets = list(all_dets.keys())
-        self._obs_nview = {iob: len(ob.intervals[self.view]) for iob, ob in enumerate(new_data.obs)}
-        self._layout_detector_major(new_data.comm, {iob: n * norder for iob, n in self._obs_nview.items()})
-        self._templates = {}
-        self._mirrors["precond"] = DeviceMirror(np.zeros((self._n_local // norder, norder, norder), dtype=np.float64),
-                                                f"{self.name}_precond")
-        if self._n_local == 0:
+        if not self._layout_blocks(new_data):
             return
         # (set-up runs on the device for a template that will be swept there; the flags it reads are handed back)
         if accel_enabled() and self.supports_accel():
@@ -76,22 +49,6 @@ class SubHarmonic(Template):
         else:
             gram, ngood = self._gram_host(new_data)
         self._invert(new_data, gram, ngood)
-
-    @staticmethod
-    def _max_terms():
-        from .. import capi
-
-        return capi.dev.subharmonic_max_terms()
-
-    def _view_templates(self, iob, ob):
-        """The basis of every view of one observation, built on first use by the host path."""
-        if iob not in self._templates:
-            self._templates[iob] = [legendre_basis(self.order + 1, int(vw.last - vw.first)) for vw in ob.intervals[self.view]]
-        return self._templates[iob]
-
-    def _blocks(self, iob, dets):
-        """First block (amplitude index / norder) of each detector for observation ``iob``."""
-        return self.det_amp_offsets(iob, dets) // (self.order + 1)
 
     def _gram_host(self, new_data):
         """subharmonic.py:157-178 for every block -> ([n_block][norder][norder], good samples per block)."""
@@ -146,9 +103,8 @@ class SubHarmonic(Template):
                                                        s.ptr("ngood"))
             finally:
                 release_borrowed(borrowed)
-            for k, blk in enumerate(self._blocks(iob, dets)):
-                gram[blk:blk + n_view] = g[k]
-                ngood[blk:blk + n_view] = n[k]
+            self._scatter_blocks(iob, dets, g, gram)
+            self._scatter_blocks(iob, dets, n, ngood)
         return gram, ngood
 
     def _invert(self, new_data, gram, ngood):
@@ -157,45 +113,9 @@ class SubHarmonic(Template):
         if empty.size > 0:
             raise np.linalg.LinAlgError(f"SubHarmonic template {self.name}: {self._describe_block(new_data, int(empty[0]))} has "
                                         f"no unflagged sample ({empty.size} such blocks): its preconditioner is singular")
-        try:
-            self._precond[:] = np.linalg.inv(gram)
-        except np.linalg.LinAlgError:
-            for blk in range(gram.shape[0]):
-                try:
-                    np.linalg.inv(gram[blk])
-                except np.linalg.LinAlgError as err:
-                    raise np.linalg.LinAlgError(f"SubHarmonic template {self.name}: "
-                                                f"{self._describe_block(new_data, blk)} has a singular preconditioner "
-                                                f"({int(ngood[blk])} unflagged samples)") from err
-            raise
-        if not np.all(np.isfinite(self._precond)):
-            bad = int(np.flatnonzero(~np.isfinite(self._precond).all(axis=(1, 2)))[0])
-            raise np.linalg.LinAlgError(f"SubHarmonic template {self.name}: {self._describe_block(new_data, bad)} has a "
-                                        f"preconditioner that is not finite")
-
-    def _describe_block(self, new_data, blk):
-        norder = self.order + 1
-        for det in self._all_dets:
-            off = self._det_start[det] // norder
-            for iob, ob in enumerate(new_data.obs):
-                if det not in self._obs_dets[iob]:
-                    continue
-                if blk < off + self._obs_nview[iob]:
-                    return f"detector {det}, observation {ob.name}, view {blk - off}"
-                off += self._obs_nview[iob]
-        return f"block {blk}"
+        self._invert_blocks(new_data, gram, lambda blk: f" ({int(ngood[blk])} unflagged samples)")
 
     # ------------------------------------------------------------------ Template interface
-    def _detectors(self):
-        return self._all_dets
-
-    def _zeros(self):
-        # no explicit flagging of amplitudes in this template (subharmonic.py:184-188)
-        return Amplitudes(self.data.comm, self._n_global, self._n_local)
-
-    def _supports_accel(self):
-        return self.order + 1 <= self._max_terms()
-
     def add_to_signal_multi(self, detectors, amplitudes, **kwargs):
         """All detectors and all views of an observation in one launch (device-resident buffers only)."""
         from .. import capi
@@ -242,27 +162,3 @@ class SubHarmonic(Template):
                 for order, template in enumerate(self._view_templates(iob, ob)[ivw]):
                     amp_view[order] = np.dot(row[vw.first:vw.last], template)
                 offset += norder
-
-    def _add_prior(self, amplitudes_in, amplitudes_out, **kwargs):
-        return      # no prior for this template (subharmonic.py:220-222)
-
-    def _apply_precond(self, amplitudes_in, amplitudes_out, use_accel=None, **kwargs):
-        if self._n_local == 0:
-            return
-        norder = self.order + 1
-        if amplitudes_in.accel_in_use() or amplitudes_out.accel_in_use():
-            from .. import capi
-
-            amplitudes_in.accel_resident()
-            amplitudes_out.accel_resident()
-            capi.dev.subharmonic_apply_precond(norder, self._n_local // norder, self._mirrors["precond"].upload().ptr,
-                                               accel_device_ptr(amplitudes_in.buffer), accel_device_ptr(amplitudes_out.buffer))
-            return
-        # subharmonic.py:224-236: one small dense product per block
-        a_in = amplitudes_in.local.reshape(-1, norder)
-        amplitudes_out.local.reshape(-1, norder)[:] = np.einsum("brc,bc->br", self._precond, a_in)
-
-    def clear(self):
-        """Release the device copy of the preconditioner and the host basis."""
-        super().clear()
-        self._templates = {}
