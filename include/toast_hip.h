@@ -1516,6 +1516,66 @@ int toast_hip_sim_dipole_dev(
 int toast_hip_sim_dipole_det_tile(void);
 
 /* ------------------------------------------------------------------------------------
+ * filterbin: the joint regression of HWP-synchronous, ground and per-interval polynomial templates of
+ * toast.ops.FilterBin (csrc/filterbin.hip) [ref: src/toast/ops/filterbin.py:56-251 (SparseTemplates), :854-1003,
+ * :1120-1238, :1372-1410; src/toast/_libtoast/ops_filterbin.cpp:276-382 (build_template_covariance)].  The templates are
+ * split into n_dense DENSE rows dense f64[n_dense,n_samp] in device memory and n_interval intervals [starts[v],
+ * stops[v]) (host i64, sorted, disjoint, inside [0, n_samp), at least K = order + 1 samples each, order <=
+ * toast_hip_filterbin_max_order()) that carry the K Legendre polynomials P_j(x), x = (i - start + 0.5) * 2 / L - 1
+ * [filterbin.py:1395-1398], rebuilt in registers with the recurrence of toast_hip_legendre_templates_dev.  The normal
+ * matrix of a detector is [[A, C], [C^T, diag(B_v)]]; A and the dense right-hand side are toast_hip_template_fit_dev's.
+ * Samples are good where (shared_flags & shared_flag_mask) == 0 and (det_flags[flag_index[d]] & det_flag_mask) == 0; a NULL
+ * flag pointer flags nothing.  signal_index / flag_index: host i32[n_det], rows of d_signal / d_det_flags.
+ *
+ * toast_hip_fourier_templates_dev [ref: src/toast/_libtoast/tod_filter.cpp:132-176]: templates[2 (k - start_order)] =
+ *   cos(k angle), templates[2 (k - start_order) + 1] = sin(k angle), k = start_order .. stop_order - 1, the argument
+ *   formed as (double)k * angle[i]; templates f64[2 (stop_order - start_order), n_samp].
+ * toast_hip_template_spans_dev [ref: filterbin.py:117-125 trim]: first[r] / last[r] i64 = first / last i with
+ *   templates[r][i] != 0; n_samp / -1 for a row of zeros.
+ * toast_hip_filterbin_good_counts_dev [ref: filterbin.py:154, :873]: n_good i64[n_det] = good samples of a detector;
+ *   nnz i64[n_det,n_template] = good samples where templates[r][i] != 0 (n_template may be 0).
+ * toast_hip_filterbin_flag_spans_dev [ref: filterbin.py:874, :897-899, :945-946, :990]: det_flags[flag_rows[s]][firsts[s]
+ *   .. lasts[s]) |= mask for the n_span host triples; det_flags u8[n_rows,n_samp].
+ * toast_hip_filterbin_accumulate_dev, with KP = K (K + 1) / 2 and pairs (a <= b) packed row by row:
+ *   p f64[n_det,n_interval,K]          = sum over good samples of P_j signal
+ *   nnz i64[n_det,n_interval,K]        = good samples with P_j != 0
+ *   b_common f64[n_interval,KP], c_common f64[n_interval,n_dense,K]            sums over the shared-good samples
+ *   b_flagged f64[n_det,n_interval,KP], c_flagged f64[n_det,n_interval,n_dense,K]  sums over the shared-good samples
+ *                                      that detector d flags:  B_dv = b_common - b_flagged[d],  C_dv = c_common - c_flagged[d]
+ *   (all outputs are zeroed first; the c arrays are not touched when n_dense == 0).
+ * toast_hip_filterbin_subtract_dev: signal[signal_index[d]][i] -= sum_r a[d][r] dense[r][i] + sum_j b[d][v][j] P_j(x_i)
+ *   with v the interval of i (no second term outside the intervals); a f64[n_det,n_dense], b f64[n_det,n_interval,K]
+ *   in device memory [ref: filterbin.py:109-114].  Rows not named in signal_index are not touched.
+ * toast_hip_filterbin_chunk(): samples of one interval per workgroup of the accumulation; toast_hip_filterbin_det_tile():
+ * detectors per workgroup at that order (tests straddle both).
+ * ---------------------------------------------------------------------------------- */
+int toast_hip_fourier_templates_dev(const double * d_angle, int64_t n_samp, int64_t start_order, int64_t stop_order,
+                                    double * d_templates, void * stream);
+int toast_hip_template_spans_dev(const double * d_templates, int64_t n_template, int64_t n_samp, int64_t * d_first,
+                                 int64_t * d_last, void * stream);
+int toast_hip_filterbin_good_counts_dev(const double * d_templates, int64_t n_template, int64_t n_samp,
+                                        const int32_t * flag_index /*host*/, const uint8_t * d_det_flags,
+                                        uint8_t det_flag_mask, const uint8_t * d_shared_flags, uint8_t shared_flag_mask,
+                                        int64_t n_det, int64_t * d_n_good, int64_t * d_nnz, void * stream);
+int toast_hip_filterbin_flag_spans_dev(const int32_t * flag_rows /*host*/, const int64_t * firsts /*host*/,
+                                       const int64_t * lasts /*host*/, int64_t n_span, int64_t n_rows, int64_t n_samp,
+                                       uint8_t * d_det_flags, uint8_t mask, void * stream);
+int toast_hip_filterbin_accumulate_dev(int64_t order, const double * d_dense, int64_t n_dense, int64_t n_samp,
+                                       const int32_t * signal_index /*host*/, const double * d_signal,
+                                       const int32_t * flag_index /*host*/, const uint8_t * d_det_flags, uint8_t det_flag_mask,
+                                       const uint8_t * d_shared_flags, uint8_t shared_flag_mask, int64_t n_det,
+                                       const int64_t * starts /*host*/, const int64_t * stops /*host*/, int64_t n_interval,
+                                       double * d_p, int64_t * d_nnz, double * d_b_common, double * d_c_common,
+                                       double * d_b_flagged, double * d_c_flagged, void * stream);
+int toast_hip_filterbin_subtract_dev(int64_t order, const double * d_dense, int64_t n_dense, int64_t n_samp,
+                                     const int32_t * signal_index /*host*/, double * d_signal, int64_t n_det,
+                                     const double * d_a, const int64_t * starts /*host*/, const int64_t * stops /*host*/,
+                                     int64_t n_interval, const double * d_b, void * stream);
+int toast_hip_filterbin_chunk(void);
+int toast_hip_filterbin_det_tile(int64_t order);
+int toast_hip_filterbin_max_order(void);
+
+/* ------------------------------------------------------------------------------------
  * Deterministic debug mode (TOAST_HIP_DETERMINISTIC=1 in the environment, or this switch).
  * The production A^T kernels add run-reduced partial sums with fp64 atomics, so zmap / the
  * inverse covariance differ from run to run in the last bits.  With the mode on,

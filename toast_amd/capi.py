@@ -2128,6 +2128,73 @@ class _Dev:
         """Detectors that share one lane's per-sample work in the dipole kernel."""
         return int(real_lib().toast_hip_sim_dipole_det_tile())
 
+    # ---- FilterBin kernels (csrc/filterbin.hip)
+    def fourier_templates(self, d_angle, n_samp, start_order, stop_order, d_templates, stream=0):
+        """Rows cos(k angle), sin(k angle) for k = start_order .. stop_order - 1.  toast_hip_fourier_templates_dev."""
+        _check(lib().toast_hip_fourier_templates_dev(_p(d_angle), _i64(n_samp), _i64(start_order), _i64(stop_order),
+                                                     _p(d_templates), _p(stream)))
+
+    def template_spans(self, d_templates, n_template, n_samp, d_first, d_last, stream=0):
+        """First / last non-zero sample of every row (int64; n_samp / -1 for a row of zeros)."""
+        _check(lib().toast_hip_template_spans_dev(_p(d_templates), _i64(n_template), _i64(n_samp), _p(d_first), _p(d_last),
+                                                  _p(stream)))
+
+    def filterbin_good_counts(self, d_templates, n_template, n_samp, flag_index, d_det_flags, det_flag_mask, d_shared_flags,
+                              shared_flag_mask, n_det, d_n_good, d_nnz, stream=0):
+        fi = self._small(flag_index if flag_index is not None else np.zeros(n_det), np.int32)
+        if fi.size != n_det:
+            raise RuntimeError("filterbin_good_counts: one flag row per detector")
+        _check(lib().toast_hip_filterbin_good_counts_dev(
+            _p(d_templates), _i64(n_template), _i64(n_samp), _p(fi), _p(d_det_flags), _u8(det_flag_mask), _p(d_shared_flags),
+            _u8(shared_flag_mask), _i64(n_det), _p(d_n_good), _p(d_nnz), _p(stream)))
+
+    def filterbin_flag_spans(self, flag_rows, firsts, lasts, n_rows, n_samp, d_det_flags, mask, stream=0):
+        """``det_flags[flag_rows[s], firsts[s]:lasts[s]] |= mask`` on the device."""
+        fr = self._small(flag_rows, np.int32)
+        a = self._small(firsts, np.int64)
+        b = self._small(lasts, np.int64)
+        if not (fr.size == a.size == b.size):
+            raise RuntimeError("filterbin_flag_spans: one row, first and last per span")
+        _check(lib().toast_hip_filterbin_flag_spans_dev(_p(fr), _p(a), _p(b), _i64(fr.size), _i64(n_rows), _i64(n_samp),
+                                                        _p(d_det_flags), _u8(mask), _p(stream)))
+
+    def filterbin_accumulate(self, order, d_dense, n_dense, n_samp, signal_index, d_signal, flag_index, d_det_flags,
+                             det_flag_mask, d_shared_flags, shared_flag_mask, starts, stops, d_p, d_nnz, d_b_common,
+                             d_c_common, d_b_flagged, d_c_flagged, stream=0):
+        """The interval blocks of the FilterBin normal matrix (layouts: include/toast_hip.h)."""
+        si = self._small(signal_index, np.int32)
+        fi = self._small(flag_index if flag_index is not None else np.zeros(si.size), np.int32)
+        st = self._small(starts, np.int64)
+        sp = self._small(stops, np.int64)
+        if st.size != sp.size or fi.size != si.size:
+            raise RuntimeError("filterbin_accumulate: starts / stops or signal / flag rows do not match")
+        _check(lib().toast_hip_filterbin_accumulate_dev(
+            _i64(order), _p(d_dense), _i64(n_dense), _i64(n_samp), _p(si), _p(d_signal), _p(fi), _p(d_det_flags),
+            _u8(det_flag_mask), _p(d_shared_flags), _u8(shared_flag_mask), _i64(si.size), _p(st), _p(sp), _i64(st.size),
+            _p(d_p), _p(d_nnz), _p(d_b_common), _p(d_c_common), _p(d_b_flagged), _p(d_c_flagged), _p(stream)))
+
+    def filterbin_subtract(self, order, d_dense, n_dense, n_samp, signal_index, d_signal, d_a, starts, stops, d_b,
+                           stream=0):
+        si = self._small(signal_index, np.int32)
+        st = self._small(starts, np.int64)
+        sp = self._small(stops, np.int64)
+        if st.size != sp.size:
+            raise RuntimeError("Starts / stops buffer sizes are not consistent.")
+        _check(lib().toast_hip_filterbin_subtract_dev(
+            _i64(order), _p(d_dense), _i64(n_dense), _i64(n_samp), _p(si), _p(d_signal), _i64(si.size), _p(d_a), _p(st),
+            _p(sp), _i64(st.size), _p(d_b), _p(stream)))
+
+    def filterbin_chunk(self):
+        """Samples of one interval per workgroup of ``filterbin_accumulate``."""
+        return int(real_lib().toast_hip_filterbin_chunk())
+
+    def filterbin_det_tile(self, order):
+        """Detectors per workgroup of ``filterbin_accumulate`` at this polynomial order."""
+        return int(real_lib().toast_hip_filterbin_det_tile(_i64(order)))
+
+    def filterbin_max_order(self):
+        return int(real_lib().toast_hip_filterbin_max_order())
+
     def test_math(self, op, n, d_a, d_b, d_out, stream=0):
         _check(lib().toast_hip_test_math_dev(C.c_int(op), _i64(n), _p(d_a), _p(d_b), _p(d_out), _p(stream)))
 

@@ -17,6 +17,7 @@ from .mapmaker_ops import (
 )
 from .mapmaker_solve import SolverLHS, SolverRHS, TemplateMatrix, solve
 from .demodulation import Demodulate, StokesWeightsDemod
+from .filterbin import FilterBin
 from .ground_filter import GroundFilter
 from .noise_estimation import NoiseEstim
 from .noise_filter import NoiseFilter

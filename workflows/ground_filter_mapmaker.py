@@ -13,6 +13,11 @@ the atmosphere as configs[4] does (GenerateAtmosphere, CHOLMOD) is not part of t
                                                [--subharmonic ORDER] [--periodic-az BINS] [--fourier2d ORDER]
                                                [--time-constant MS [--time-constant-sigma S]]
                                                [--atmosphere {1,2}]
+                                               [--filterbin [--hwp-filter-order N] [--ground-filter-order N]
+                                                            [--poly-filter-order N]]
+
+`--filterbin` replaces the separate filters and MapMaker by `FilterBin`: HWP-synchronous harmonics, ground polynomials and
+per-subscan polynomials regressed in one fit per detector, then the binned map.
 """
 import argparse
 import os
@@ -65,6 +70,52 @@ def observe_standin_atmosphere(data, n_slab):
         del ob.shared[defaults.boresight_azel]
 
 
+def filter_and_bin(data, args, lap, rms_before):
+    """--filterbin: ops.FilterBin instead of the separate filters and MapMaker.  The polynomial view is the list of single
+    throws (the `throw` list of SimGround is the union of both directions: one interval); observations of the synthetic
+    generator get their scan range from the azimuth and, with --hwp-filter-order, a 2 Hz HWP angle."""
+    from toast_amd.data import IntervalList
+
+    for o in data.obs:
+        single = sorted((int(iv.first), int(iv.last)) for name in (defaults.throw_leftright_interval,
+                                                                    defaults.throw_rightleft_interval)
+                        for iv in o.intervals[name])
+        o.intervals["subscans"] = IntervalList(o.shared[defaults.times].data, samplespans=single)
+        if "scan_min_az" not in o:
+            az = o.shared[defaults.azimuth].data
+            o["scan_min_az"], o["scan_max_az"] = float(az.min()), float(az.max())
+        if args.hwp_filter_order is not None and not np.any(o.shared[defaults.hwp_angle].data):
+            times = o.shared[defaults.times].data
+            o.shared[defaults.hwp_angle].data[:] = 2 * np.pi * (((times - times[0]) * 2.0) % 1.0)
+    det_pointing = ops.PointingDetectorSimple()
+    pixels = ops.PixelsHealpix(detector_pointing=det_pointing, nside=args.nside, nest=True, view=defaults.scanning_interval)
+    weights = ops.StokesWeights(detector_pointing=det_pointing, mode="IQU", view=defaults.scanning_interval)
+    binner = ops.BinMap(pixel_dist="pixel_dist", pixel_pointing=pixels, stokes_weights=weights)
+    fb = ops.FilterBin(name="filterbin", binning=binner, hwp_filter_order=args.hwp_filter_order,
+                       ground_filter_order=args.ground_filter_order, split_ground_template=args.split,
+                       poly_filter_order=args.poly_filter_order, poly_filter_view="subscans", keep_final_products=True,
+                       report_timing=True)
+    fb.apply(data)
+    lap("FilterBin (regression + cov + bin)")
+    ob = data.obs[0]
+    good = (ob.shared[defaults.shared_flags].data & fb.shared_flag_mask) == 0
+    good &= (ob.detdata[defaults.det_flags].data[0] & fb.det_flag_mask) == 0
+    rms_after = float(np.std(ob.detdata[defaults.det_data].data[0][good]))
+    routes = [r for per_obs in fb.routes.values() for r in per_obs.values()]
+    fitted = [a for per_obs in fb.amplitudes.values() for a in per_obs.values() if a is not None]
+    print(f"detectors {args.ndet}  samples/det {ob.n_local_samples}  subscans {len(ob.intervals['subscans'])}  nside "
+          f"{args.nside}  templates {len(fitted[0]) if fitted else 0}  routes inv {routes.count(0)} pinv {routes.count(1)} "
+          f"rejected {routes.count(2)} not fitted {routes.count(3)}")
+    print(f"ground signal: rms of detector 0 over good samples {rms_before:.2f} -> {rms_after:.3f} (white noise rms 1)")
+    print("FilterBin phases [ms]: " + "  ".join(f"{k} {1e3 * v:.1f}" for k, v in fb.seconds.items()))
+    fmap = np.asarray(data["filterbin_filtered_map"].data)
+    hit = np.asarray(data["filterbin_filtered_hits"].data).reshape(-1) > 0
+    print(f"hit pixels {int(np.count_nonzero(hit))}  rms of the filtered map (I, hit pixels) "
+          f"{float(np.std(fmap.reshape(hit.size, -1)[hit, 0])):.4f}")
+    if args.save_map is not None:
+        np.save(args.save_map, fmap)
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--ndet", type=int, default=256)
@@ -114,6 +165,14 @@ def main(argv=None):
                     help="observe SLABS (1 or 2) atmosphere slabs into the signal with ops.ObserveAtmosphere before the "
                          "filters.  The slabs are a STAND-IN, not the reference's generator: a box around the scan cone, "
                          "cells kept by a cone predicate, a smooth random field from a filtered FFT (off by default)")
+    ap.add_argument("--filterbin", action="store_true",
+                    help="replace the separate filters and the MapMaker call by ops.FilterBin: one joint regression of "
+                         "HWP-synchronous harmonics, ground polynomials (split with --split) and per-subscan polynomials, "
+                         "then the binned map; prints the rms of the filtered map and the phase times")
+    ap.add_argument("--hwp-filter-order", type=int, default=None, metavar="ORDER", help="with --filterbin: hwp_filter_order")
+    ap.add_argument("--ground-filter-order", type=int, default=5, metavar="ORDER",
+                    help="with --filterbin: ground_filter_order")
+    ap.add_argument("--poly-filter-order", type=int, default=1, metavar="ORDER", help="with --filterbin: poly_filter_order")
     ap.add_argument("--save-map", default=None, metavar="FILE", help="save the binned map as a .npy file")
     args = ap.parse_args(argv)
     n_samp = int(args.minutes * 60 * args.rate)
@@ -133,6 +192,8 @@ def main(argv=None):
         schedule = make_ces_schedule(args.scheduled, scan_seconds=args.minutes * 60.0, az_min=40.0, az_max=110.0, el=50.0)
         el_motion = dict(elnod_start=True, elnod_end=True, elnods=[1.0, -1.0, 0.0], scan_rate_el=1.0, scan_accel_el=1.0,
                          el_mod_step=0.05) if args.elnods else {}
+        if args.filterbin and args.hwp_filter_order is not None:
+            el_motion.update(hwp_angle=defaults.hwp_angle, hwp_rpm=120.0)
         data = create_ground_data_from_schedule(schedule, n_det=args.ndet, rate=args.rate, fov_deg=8.0,
                                                 scan_rate_az=1.0, scan_accel_az=1.0, fix_rate_on_sky=False, **el_motion)
         for ob in data.obs:     # the map-maker skips samples with any non-science bit: raise "invalid" too
@@ -192,6 +253,9 @@ def main(argv=None):
         del untouched, diffs
     good = (ob.shared[defaults.shared_flags].data & 1) == 0
     rms_before = float(np.std(sig[0][good]))
+    if args.filterbin:
+        filter_and_bin(data, args, lap, rms_before)
+        return data
     if args.polyfilter is not None:
         for o in data.obs:
             if "throw" not in o.intervals:      # the synthetic generator names the sweeps `scanning` only
