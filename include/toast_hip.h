@@ -153,6 +153,43 @@ int toast_hip_arena_zone_threshold(const double * rates, int n, double level, do
 /* The sub-allocation logic exercised on HOST memory (no device needed): n_ops random allocations / releases with the
  * bookkeeping and the contents of every live block checked after each step.  0 = sound. */
 int toast_hip_arena_selftest(uint64_t seed, int n_ops, size_t granule, size_t slab_bytes, size_t max_block);
+/* The packed pointing cache of toast_hip_build_noise_weighted_dev / toast_hip_scan_map_dev (csrc/pointing_cache.hpp,
+ * DESIGN.md): when the pixels and the (I, Q, U) weights of a call were written by the library's own expansion calls
+ * (toast_hip_pixels_healpix_dev, toast_hip_stokes_weights_IQU_dev) into blocks of the arena, on the same stream and with
+ * the same interval list, and nothing the library can see has written to them since, the third such call packs them
+ * (int32 pixel + (Q, U), 20 instead of 32 B per sample; the intensity weight is the detector's cal) and this and the
+ * later calls read the copy: same scan_map results bit for bit, build_noise_weighted up to the order of its atomics.
+ * Every entry point that is not known to write only through the pointers it declares drops the seals.  A caller whose OWN
+ * kernels write into a sealed arena block must say so with toast_hip_pointing_cache_drop.
+ * TOAST_HIP_POINTING_CACHE=0 switches the cache off; TOAST_HIP_POINTING_CACHE_TRACE=1 prints these counters at exit. */
+typedef struct toast_hip_pointing_cache_stats_t {
+    int32_t enabled;
+    int32_t pack_after_calls;     /* the eligible call since sealing that packs (3) */
+    int64_t seals;                /* seals written */
+    int64_t packs;                /* calls that made a packed copy */
+    int64_t hits;                 /* calls served from a packed copy */
+    int64_t misses;               /* calls that looked and were not */
+    int64_t drops_foreign_call;   /* seals dropped by an entry point that is not whitelisted */
+    int64_t drops_overlap_write;  /* ... by a whitelisted entry point that wrote over them */
+    int64_t drops_free;           /* ... because their arena block was freed */
+    int64_t drops_manager;        /* ... by a memory-manager upload / reset / device change */
+    int64_t drops_reseal;         /* ... by a new expansion into the same rows */
+    int64_t drops_explicit;       /* ... by toast_hip_pointing_cache_drop / _enable(0) */
+    int64_t evictions;            /* packed copies given up for an allocation */
+    int64_t pack_no_room;         /* packs that found no free arena space (the call ran un-cached) */
+    int64_t live_seals;
+    uint64_t packed_bytes;        /* bytes in packed copies now */
+} toast_hip_pointing_cache_stats_t;
+int toast_hip_pointing_cache_stats(toast_hip_pointing_cache_stats_t * out);
+int toast_hip_pointing_cache_enable(int on);
+int toast_hip_pointing_cache_drop(void);
+/* The registry driven on HOST memory (no device needed).  scenario 0: a seeded random sequence of n_ops seal / consume /
+ * overlapping write / free / non-whitelisted call / allocation pressure steps, checked against a model that knows when a
+ * hit is allowed and against the arrays' contents, with a stand-in backend that comes back into the registry from its pack
+ * and defers its releases; 1-7: one named scenario (the pack happens on the third call; another interval list misses; a
+ * reseal discards the copy; eviction under allocation pressure; a non-whitelisted call drops every seal; an expansion that
+ * does not seal still drops what it overwrites; the pack re-enters the registry).  0 = sound. */
+int toast_hip_pointing_cache_selftest(uint64_t seed, int n_ops, int scenario);
 /* Raw device memory from the arena (flags = -1, also -2: a read-mostly block; -3 = a STREAMED block: a timestream that
  * sweeps read and write, placed in a slab whose 1 GB chunks come from two HBM zones in the pattern P Q Q P ... so that its
  * rows are spread over both -- such sweeps run at 6.1 instead of 5.1 TB/s there; -4 = a SCATTER TARGET: a map or amplitude

@@ -381,6 +381,36 @@ def arena_selftest(seed, n_ops, granule, slab_bytes, max_block):
                                                C.c_size_t(int(slab_bytes)), C.c_size_t(int(max_block))))
 
 
+class _PointingCacheStats(C.Structure):
+    _fields_ = [("enabled", C.c_int32), ("pack_after_calls", C.c_int32), ("seals", C.c_int64), ("packs", C.c_int64),
+                ("hits", C.c_int64), ("misses", C.c_int64), ("drops_foreign_call", C.c_int64),
+                ("drops_overlap_write", C.c_int64), ("drops_free", C.c_int64), ("drops_manager", C.c_int64),
+                ("drops_reseal", C.c_int64), ("drops_explicit", C.c_int64), ("evictions", C.c_int64),
+                ("pack_no_room", C.c_int64), ("live_seals", C.c_int64), ("packed_bytes", C.c_uint64)]
+
+
+def pointing_cache_stats():
+    """Counters of the packed pointing cache of build_noise_weighted / scan_map (toast_hip_pointing_cache_stats)."""
+    st = _PointingCacheStats()
+    _check(real_lib().toast_hip_pointing_cache_stats(C.byref(st)))
+    return {name: int(getattr(st, name)) for name, _ in _PointingCacheStats._fields_}
+
+
+def pointing_cache_enable(on):
+    """Switch the packed pointing cache on / off at run time (off drops every seal and packed copy)."""
+    _check(real_lib().toast_hip_pointing_cache_enable(C.c_int(1 if on else 0)))
+
+
+def pointing_cache_drop():
+    """Forget every seal: for a caller whose own kernels wrote into a sealed arena block."""
+    _check(real_lib().toast_hip_pointing_cache_drop())
+
+
+def pointing_cache_selftest(seed, n_ops, scenario=0):
+    """The sealed-pointing registry on host memory (toast_hip_pointing_cache_selftest); raises on a broken contract."""
+    _check(real_lib().toast_hip_pointing_cache_selftest(C.c_uint64(int(seed)), C.c_int(int(n_ops)), C.c_int(int(scenario))))
+
+
 def probe_stream(ptr, nbytes):
     """ms of one read + write pass over a device range with 1024 rows in flight (toast_hip_probe_stream)."""
     ms = C.c_double(0.0)

@@ -257,6 +257,23 @@ bool Arena::owns(const void * p) const {
     return false;
 }
 
+bool Arena::block_of(const void * p, const char ** base, size_t * bytes) const {
+    std::lock_guard<std::mutex> lock(mutex_);
+    const char * c = static_cast<const char *>(p);
+    for (const Slab & s : slabs_) {
+        if (c < s.base || c >= s.base + s.bytes) continue;
+        const size_t off = (size_t)(c - s.base);
+        auto it = s.live.upper_bound(off);
+        if (it == s.live.begin()) return false;
+        --it;
+        if (off >= it->first + it->second) return false;
+        *base = s.base + it->first;
+        *bytes = it->second;
+        return true;
+    }
+    return false;
+}
+
 bool Arena::slab_offset(const void * p, size_t * off) const {
     std::lock_guard<std::mutex> lock(mutex_);
     const char * c = static_cast<const char *>(p);

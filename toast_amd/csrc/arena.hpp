@@ -82,6 +82,8 @@ public:
     // false when p is not a live block of this arena
     bool release(void * p);
     bool owns(const void * p) const;
+    // the live block that CONTAINS p (its base and granule-rounded length); false when p lies in no live block
+    bool block_of(const void * p, const char ** base, size_t * bytes) const;
     // offset of an address inside its slab; false when it lies in none
     bool slab_offset(const void * p, size_t * off) const;
     // make the capacity (free + used) at least `bytes` by taking ONE more slab for the difference; false if the

@@ -25,6 +25,7 @@
 
 #include "../../include/toast_hip.h"
 #include "runtime.hpp"
+#include "pointing_cache.hpp"
 
 namespace {
 
@@ -257,6 +258,8 @@ int toast_hip_comm_destroy(void) {
 
 int toast_hip_comm_allreduce_dev(void * d_buf, int64_t count, int dtype, int op, void * stream) {
     return guarded([&] {
+        // (pointing cache: what this call writes, each to the end of its arena block)
+        pointing_cache::global().wrote(d_buf, 0);
         if (count <= 0) return;
         const DType t = dtype_of(dtype);
         if (peer_allreduce(d_buf, count, dtype, op, as_stream(stream))) return;
@@ -883,6 +886,8 @@ int toast_hip_comm_get_mode(char * text, size_t len) {
 int toast_hip_comm_map_reduce_apply_dev(int64_t n_px, int64_t nnz, const double * d_cov, double * d_map, int reduce,
                                         void * stream) {
     return guarded([&] {
+        // (pointing cache: what this call writes, each to the end of its arena block)
+        pointing_cache::global().wrote(d_map, 0);
         if (n_px <= 0) return;
         if (nnz <= 0) fail_arg("nnz must be positive");
         (void)comm();

@@ -13,6 +13,7 @@
 #include <hip/hip_runtime.h>
 
 #include "kernel_common.hpp"
+#include "pointing_cache.hpp"
 
 using namespace toast_hip;
 
@@ -433,6 +434,88 @@ __global__ __launch_bounds__(kThreads) void k_scan_map_v2(
     }
 }
 
+// k_scan_map_v2 on the packed pointing cache (pointing_cache.hpp): the pixel pair is one 8-byte lane access (int32 global
+// pixels, -1 kept), the two (Q, U) pairs two 16-byte ones, and the intensity weight -- one number per detector,
+// k_stokes_iqu writes w[0] = cal -- comes from the parameter block: 36 instead of 48 B per sample.  Everything else is
+// k_scan_map_v2: same expressions in the same order on the same values, so the results are bit-identical.
+template <typename T>
+__global__ __launch_bounds__(kThreads) void k_scan_map_pk(
+    const Chunk * __restrict__ chunks, int n_chunks, const int32_t * __restrict__ d_idx,
+    const int32_t * __restrict__ p_row, const int32_t * __restrict__ q_row, const double * __restrict__ cal,
+    const int64_t * __restrict__ g2l, const T * __restrict__ map, double * __restrict__ tod,
+    const int32_t * __restrict__ pix32, const double2 * __restrict__ qu,
+    FastDiv nps_div, double scale, int zero, int subtract, int mult,
+    const double * __restrict__ det_w, int64_t n_samp) {
+    const int det = blockIdx.x;
+    double * drow = tod + (int64_t)d_idx[det] * n_samp;
+    const int32_t * prow = pix32 + (int64_t)p_row[det] * n_samp;
+    const double2 * qrow = qu + (int64_t)q_row[det] * n_samp;
+    const double w0 = cal[det];
+    const bool fuse = det_w != nullptr;
+    const double dw = fuse ? det_w[det] : 1.0;
+    for (int ci = blockIdx.y; ci < n_chunks; ci += gridDim.y) {
+        const Chunk c = chunks[ci];
+        const int head = (int)(c.first & 1);
+        const int64_t s0 = c.first + head;          // even
+        const int n_pair = (c.count - head) >> 1;
+        for (int j = threadIdx.x; j < n_pair; j += kThreads) {
+            const int64_t s = s0 + 2 * (int64_t)j;
+            const int2 pq = *reinterpret_cast<const int2 *>(prow + s);
+            double2 dd = make_double2(0.0, 0.0);
+            if (!zero) dd = *reinterpret_cast<const double2 *>(drow + s);
+            const double2 wa = qrow[s], wb = qrow[s + 1];
+            const int64_t pa = pq.x, pb = pq.y;
+            const int64_t ga = scan_submap(pa, nps_div), gb = scan_submap(pb, nps_div);
+            const int64_t la = g2l[ga], lb = g2l[gb];
+            const ScanGather qa = scan_locate(pa, ga, la, nps_div), qb = scan_locate(pb, gb, lb, nps_div);
+            const T * ma = map + qa.off;
+            const T * mb = map + qb.off;
+            const T a0 = ma[0], a1 = ma[1], a2 = ma[2], b0 = mb[0], b1 = mb[1], b2 = mb[2];
+            dd.x = scan_combine(qa.hit, dd.x, w0, wa.x, wa.y, (double)a0, (double)a1, (double)a2, scale, subtract, mult);
+            dd.y = scan_combine(qb.hit, dd.y, w0, wb.x, wb.y, (double)b0, (double)b1, (double)b2, scale, subtract, mult);
+            if (fuse) {
+                dd.x *= dw;
+                dd.y *= dw;
+            }
+            *reinterpret_cast<double2 *>(drow + s) = dd;
+        }
+        // the peeled first sample and the odd last one: lanes 0 and 1 of the workgroup
+        const int tail = (c.count - head) & 1;
+        if ((threadIdx.x == 0 && head) || (threadIdx.x == 1 && tail)) {
+            const int64_t s = (threadIdx.x == 0) ? c.first : c.first + c.count - 1;
+            const double2 w = qrow[s];
+            const int64_t p = prow[s];
+            const int64_t gs = scan_submap(p, nps_div);
+            const ScanGather q = scan_locate(p, gs, g2l[gs], nps_div);
+            const T * m = map + q.off;
+            double d = scan_combine(q.hit, zero ? 0.0 : drow[s], w0, w.x, w.y, (double)m[0], (double)m[1], (double)m[2],
+                                    scale, subtract, mult);
+            if (fuse) d *= dw;
+            drow[s] = d;
+        }
+    }
+}
+
+// The packed copies themselves: row k of the copy = row rows[k] of the caller's array, whole rows (what lies outside the
+// intervals is never read back: a consumer hits only with the interval list the array was expanded with).
+__global__ __launch_bounds__(kThreads) void k_pack_pixels32(const int64_t * __restrict__ src, int32_t * __restrict__ dst,
+                                                            const int32_t * __restrict__ rows, int64_t n_samp) {
+    const int64_t * s = src + (int64_t)rows[blockIdx.y] * n_samp;
+    int32_t * d = dst + (int64_t)blockIdx.y * n_samp;
+    for (int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x; i < n_samp; i += (int64_t)gridDim.x * kThreads) {
+        d[i] = (int32_t)s[i];
+    }
+}
+
+__global__ __launch_bounds__(kThreads) void k_pack_qu(const double * __restrict__ src, double2 * __restrict__ dst,
+                                                      const int32_t * __restrict__ rows, int64_t n_samp) {
+    const double * s = src + (int64_t)rows[blockIdx.y] * n_samp * 3;
+    double2 * d = dst + (int64_t)blockIdx.y * n_samp;
+    for (int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x; i < n_samp; i += (int64_t)gridDim.x * kThreads) {
+        d[i] = make_double2(s[3 * i + 1], s[3 * i + 2]);
+    }
+}
+
 // ------------------------------------------------------------------------------------
 // build_noise_weighted   [ref: ops_mapmaker_utils.cpp:15-86]
 // R 8 B pixel + 8*nnz B weights + 8 B tod + 1 B det flag (+ shared flag); the scatter is
@@ -694,6 +777,135 @@ __global__ __launch_bounds__(kThreads) void k_build_noise_weighted_v2(
                 const double * w = wrow[e] + NNZ * s;
                 double * z = zmap + NNZ * key;
                 for (int k = 0; k < NNZ; ++k) unsafeAtomicAdd(z + k, sd * w[k]);
+            }
+        }
+    }
+}
+
+// k_build_noise_weighted_v2 on the packed pointing cache (see k_scan_map_pk): 8 bytes for the pixel pair, 2 x 16 for the
+// two (Q, U) pairs, cal[det] from the parameter block as the intensity weight -- 29 instead of 41 B per sample.  Same
+// products, same scan, same launch grid: the map differs from k_build_noise_weighted_v2's by the order of the atomics only.
+template <int E>
+__global__ __launch_bounds__(kThreads) void k_build_noise_weighted_pk(
+    const Chunk * __restrict__ chunks, int n_chunks, int n_det, const int32_t * __restrict__ p_row,
+    const int32_t * __restrict__ q_row, const double * __restrict__ cal, const int32_t * __restrict__ d_idx,
+    const int32_t * __restrict__ f_idx, const double * __restrict__ det_scale,
+    const int64_t * __restrict__ g2l, double * __restrict__ zmap,
+    const int32_t * __restrict__ pix32, const double2 * __restrict__ qu,
+    const double * __restrict__ tod, const uint8_t * __restrict__ dflags, uint8_t dmask,
+    int use_dflags, const uint8_t * __restrict__ sflags, uint8_t smask, int use_sflags,
+    FastDiv nps_div, int64_t n_samp) {
+    constexpr int NNZ = 3;
+    const int det0 = E * blockIdx.x;
+    int dets[E];
+    bool on[E];
+    const int32_t * prow[E];
+    const double2 * qrow[E];
+    const double * drow[E];
+    const uint8_t * frow[E];
+    double ds[E], wi[E];
+#pragma unroll
+    for (int e = 0; e < E; ++e) {
+        on[e] = det0 + e < n_det;
+        dets[e] = on[e] ? det0 + e : det0;
+        prow[e] = pix32 + (int64_t)p_row[dets[e]] * n_samp;
+        qrow[e] = qu + (int64_t)q_row[dets[e]] * n_samp;
+        drow[e] = tod + (int64_t)d_idx[dets[e]] * n_samp;
+        frow[e] = use_dflags ? dflags + (int64_t)f_idx[dets[e]] * n_samp : nullptr;
+        ds[e] = det_scale[dets[e]];
+        wi[e] = cal[dets[e]];
+    }
+    const int64_t nps = nps_div.d;
+    const uint16_t dmask2 = (uint16_t)(dmask | (dmask << 8));
+    const uint16_t smask2 = (uint16_t)(smask | (smask << 8));
+    for (int ci = blockIdx.y; ci < n_chunks; ci += gridDim.y) {
+        const Chunk c = chunks[ci];
+        const int head = (int)(c.first & 1);
+        const int64_t s0 = c.first + head;          // even
+        const int n_pair = (c.count - head) >> 1;
+        for (int base = 0; base < n_pair; base += kThreads) {
+            const int j = base + threadIdx.x;
+            const bool active = j < n_pair;
+            const int64_t s = s0 + 2 * (int64_t)(active ? j : 0);
+            int64_t ka[E], kb[E];
+            double va[E][NNZ], vb[E][NNZ];
+            // all streaming loads of both samples of all detectors first (inactive lanes re-read pair 0: same lines)
+            int2 pq[E];
+            double2 tt[E], wa[E], wb[E];
+            uint16_t fd[E];
+            const uint16_t fs = use_sflags ? *reinterpret_cast<const uint16_t *>(sflags + s) : (uint16_t)0;
+#pragma unroll
+            for (int e = 0; e < E; ++e) {
+                pq[e] = *reinterpret_cast<const int2 *>(prow[e] + s);
+                fd[e] = use_dflags ? *reinterpret_cast<const uint16_t *>(frow[e] + s) : (uint16_t)0;
+                tt[e] = *reinterpret_cast<const double2 *>(drow[e] + s);
+                wa[e] = qrow[e][s];
+                wb[e] = qrow[e][s + 1];
+            }
+            // global2local of every sample in one round trip (sample without a pixel: submap 0, discarded)
+            int64_t pa[E], pb[E], ga[E], gb[E], la[E], lb[E];
+#pragma unroll
+            for (int e = 0; e < E; ++e) {
+                pa[e] = pq[e].x;
+                pb[e] = pq[e].y;
+                ga[e] = fastdiv(pa[e] >= 0 ? pa[e] : 0, nps_div);
+                gb[e] = fastdiv(pb[e] >= 0 ? pb[e] : 0, nps_div);
+                la[e] = g2l[ga[e]];
+                lb[e] = g2l[gb[e]];
+            }
+#pragma unroll
+            for (int e = 0; e < E; ++e) {
+                const uint16_t bad = (uint16_t)((fd[e] & dmask2) | (fs & smask2));
+                const bool good_a = active & on[e] & (pa[e] >= 0) & (la[e] >= 0) & ((bad & 0x00ff) == 0);
+                const bool good_b = active & on[e] & (pb[e] >= 0) & (lb[e] >= 0) & ((bad & 0xff00) == 0);
+                ka[e] = good_a ? la[e] * nps + (pa[e] - ga[e] * nps) : -1;
+                kb[e] = good_b ? lb[e] * nps + (pb[e] - gb[e] * nps) : -1;
+                const double sa = tt[e].x * ds[e], sb = tt[e].y * ds[e];
+                va[e][0] = good_a ? sa * wi[e] : 0.0;
+                va[e][1] = good_a ? sa * wa[e].x : 0.0;
+                va[e][2] = good_a ? sa * wa[e].y : 0.0;
+                vb[e][0] = good_b ? sb * wi[e] : 0.0;
+                vb[e][1] = good_b ? sb * wb[e].x : 0.0;
+                vb[e][2] = good_b ? sb * wb[e].y : 0.0;
+            }
+            if constexpr (E == 2) {
+                const bool mergeable = ((ka[0] == ka[1]) | (ka[0] < 0) | (ka[1] < 0)) &
+                                       ((kb[0] == kb[1]) | (kb[0] < 0) | (kb[1] < 0));
+                if (__all(mergeable)) {
+                    const int64_t kam = (ka[0] >= 0) ? ka[0] : ka[1];
+                    const int64_t kbm = (kb[0] >= 0) ? kb[0] : kb[1];
+                    double vam[NNZ], vbm[NNZ];
+#pragma unroll
+                    for (int k = 0; k < NNZ; ++k) {
+                        vam[k] = va[0][k] + va[1][k];
+                        vbm[k] = vb[0][k] + vb[1][k];
+                    }
+                    scatter_runs2<NNZ>(kam, vam, kbm, vbm, zmap);
+                    continue;
+                }
+            }
+#pragma unroll
+            for (int e = 0; e < E; ++e) scatter_runs2<NNZ>(ka[e], va[e], kb[e], vb[e], zmap);
+        }
+        // the peeled first sample (lane 0) and the odd last one (lane 1)
+        const int tail = (c.count - head) & 1;
+        if ((threadIdx.x == 0 && head) || (threadIdx.x == 1 && tail)) {
+            const int64_t s = (threadIdx.x == 0) ? c.first : c.first + c.count - 1;
+            const uint8_t fs = use_sflags ? sflags[s] : (uint8_t)0;
+            for (int e = 0; e < E; ++e) {
+                if (!on[e]) continue;
+                const int64_t p = prow[e][s];
+                const uint8_t fd = use_dflags ? frow[e][s] : (uint8_t)0;
+                if ((p < 0) | ((fd & dmask) != 0) | ((fs & smask) != 0)) continue;
+                const int64_t gsm = fastdiv(p, nps_div);
+                const int64_t key = g2l[gsm] * nps + (p - gsm * nps);
+                if (key < 0) continue;
+                const double sd = drow[e][s] * ds[e];
+                const double2 w = qrow[e][s];
+                double * z = zmap + NNZ * key;
+                unsafeAtomicAdd(z, sd * wi[e]);
+                unsafeAtomicAdd(z + 1, sd * w.x);
+                unsafeAtomicAdd(z + 2, sd * w.y);
             }
         }
     }
@@ -2125,14 +2337,29 @@ namespace {
 
 inline bool rows_16b(const void * p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
+// device side of a pointing-cache hit (pointing_cache::Hit with its per-detector arrays in the parameter block)
+struct PackedArgs {
+    const int32_t * pix;
+    const double2 * qu;
+    const int32_t * p_row;
+    const int32_t * q_row;
+    const double * cal;
+};
+
+
 template <typename T>
 void launch_scan_map(dim3 grid, hipStream_t st, const Chunk * ch, int n_ch, const int32_t * di,
                      const int32_t * pi, const int32_t * wi, const int64_t * g2l, const void * map,
                      double * tod, const int64_t * pix, const double * w, int nnz, FastDiv dv,
                      double scale, int zero, int sub, int mult, const double * det_w,
-                     int64_t n_samp) {
+                     int64_t n_samp, const PackedArgs * pk = nullptr) {
     const T * m = static_cast<const T *>(map);
     const int dm = det_major_grid() ? 1 : 0;
+    if (pk != nullptr) {
+        hipLaunchKernelGGL((k_scan_map_pk<T>), grid, dim3(kThreads), 0, st, ch, n_ch, di, pk->p_row, pk->q_row, pk->cal, g2l, m,
+                           tod, pk->pix, pk->qu, dv, scale, zero, sub, mult, det_w, n_samp);
+        return;
+    }
     if (nnz == 3 && !dm && vec2_lanes() && (n_samp & 1) == 0 && rows_16b(tod) && rows_16b(pix) && rows_16b(w)) {
         hipLaunchKernelGGL((k_scan_map_v2<T>), grid, dim3(kThreads), 0, st, ch, n_ch, di, pi, wi, g2l, m, tod, pix, w,
                            dv, scale, zero, sub, mult, det_w, n_samp);
@@ -2215,6 +2442,11 @@ int toast_hip_pixels_healpix_dev(const int32_t * quat_index, int64_t n_det, cons
                            d_shared_flags, mask, use_flags, d_pixels, d_hit_submaps, dv, nside,
                            factor, n_samp);
         check_launch();
+        // provenance for the packed pointing cache: these rows hold pixels of this nside inside these intervals
+        auto & pc = pointing_cache::global();
+        pc.wrote(d_hit_submaps, (size_t)n_submap);
+        pc.seal(pointing_cache::kPixels, current_device(), stream, d_pixels, n_samp, pixel_index, n_det, intervals, n_view,
+                nside, nullptr);
     });
 }
 
@@ -2247,6 +2479,14 @@ static int stokes_weights_pol_dev(int n_out, const int32_t * quat_index, int64_t
                            d_weights, d_hwp, (const double *)(d + o_e), (const double *)(d + o_g),
                            (const double *)(d + o_c), usign, n_samp, stokes_reference_nan() ? 1 : 0);
         check_launch();
+        auto & pc = pointing_cache::global();
+        if (n_out == 3) {
+            // provenance: the intensity weight of row weight_index[det] is cal[det] in every sample of these intervals
+            pc.seal(pointing_cache::kWeights, current_device(), stream, d_weights, n_samp, weight_index, n_det, intervals,
+                    n_view, 0, cal);
+        } else {
+            pc.wrote_rows(d_weights, sizeof(double) * 2 * (size_t)n_samp, weight_index, n_det);
+        }
     });
 }
 
@@ -2304,13 +2544,27 @@ int toast_hip_scan_map_dev(int map_dtype, const int64_t * d_g2l, int64_t n_pix_s
         if (n_pix_submap <= 0) fail_arg("n_pix_submap must be positive");
         const auto chunks = make_chunks(intervals, n_view, n_samp);
         if (chunks.empty()) return;
+        // the timestream rows are written: whatever is sealed there is gone BEFORE the cache is asked
+        auto & pc = pointing_cache::global();
+        pc.wrote_rows(d_det_data, sizeof(double) * (size_t)n_samp, data_index, n_det);
+        pointing_cache::Hit hit;
+        const bool packed = nnz == 3 && !det_major_grid() && vec2_lanes() && (n_samp & 1) == 0 && rows_16b(d_det_data) &&
+                            map_dtype >= TOAST_HIP_MAP_F64 && map_dtype <= TOAST_HIP_MAP_I32 &&
+                            pc.consume(current_device(), stream, d_pixels, pixel_index, d_weights, weight_index, n_det, n_samp,
+                                       intervals, n_view, &hit);
         ParamBlock pb;
         const size_t o_ch = pb.push_vec(chunks);
         const size_t o_di = pb.push(data_index, sizeof(int32_t) * n_det);
         const size_t o_pi = pb.push(pixel_index, sizeof(int32_t) * n_det);
         const size_t o_wi = pb.push(weight_index, sizeof(int32_t) * n_det);
         const size_t o_dw = det_weights ? pb.push(det_weights, sizeof(double) * n_det) : 0;
+        const size_t o_pr = packed ? pb.push_vec(hit.pix_row) : 0;
+        const size_t o_qr = packed ? pb.push_vec(hit.qu_row) : 0;
+        const size_t o_cl = packed ? pb.push_vec(hit.cal) : 0;
         const char * d = pb.commit(as_stream(stream));
+        const PackedArgs pka = {hit.pix, reinterpret_cast<const double2 *>(hit.qu), (const int32_t *)(d + o_pr),
+                                (const int32_t *)(d + o_qr), (const double *)(d + o_cl)};
+        const PackedArgs * pk = packed ? &pka : nullptr;
         const double * dw = det_weights ? (const double *)(d + o_dw) : nullptr;
         const FastDiv dv = make_fastdiv(n_pix_submap);
         const dim3 grid = chunk_grid(n_det, chunks.size());
@@ -2324,22 +2578,22 @@ int toast_hip_scan_map_dev(int map_dtype, const int64_t * d_g2l, int64_t n_pix_s
             case TOAST_HIP_MAP_F64:
                 launch_scan_map<double>(grid, st, ch, n_ch, di, pi, wi, d_g2l, d_mapdata, d_det_data,
                                         d_pixels, d_weights, (int)nnz, dv, data_scale, should_zero,
-                                        should_subtract, should_scale, dw, n_samp);
+                                        should_subtract, should_scale, dw, n_samp, pk);
                 break;
             case TOAST_HIP_MAP_F32:
                 launch_scan_map<float>(grid, st, ch, n_ch, di, pi, wi, d_g2l, d_mapdata, d_det_data,
                                        d_pixels, d_weights, (int)nnz, dv, data_scale, should_zero,
-                                       should_subtract, should_scale, dw, n_samp);
+                                       should_subtract, should_scale, dw, n_samp, pk);
                 break;
             case TOAST_HIP_MAP_I64:
                 launch_scan_map<int64_t>(grid, st, ch, n_ch, di, pi, wi, d_g2l, d_mapdata, d_det_data,
                                          d_pixels, d_weights, (int)nnz, dv, data_scale, should_zero,
-                                         should_subtract, should_scale, dw, n_samp);
+                                         should_subtract, should_scale, dw, n_samp, pk);
                 break;
             case TOAST_HIP_MAP_I32:
                 launch_scan_map<int32_t>(grid, st, ch, n_ch, di, pi, wi, d_g2l, d_mapdata, d_det_data,
                                          d_pixels, d_weights, (int)nnz, dv, data_scale, should_zero,
-                                         should_subtract, should_scale, dw, n_samp);
+                                         should_subtract, should_scale, dw, n_samp, pk);
                 break;
             default:
                 fail_arg("unknown map_dtype");
@@ -2364,6 +2618,9 @@ int toast_hip_build_noise_weighted_dev(
         if (chunks.empty()) return;
         const int use_d = (n_flag_samp == n_samp) ? 1 : 0;
         const int use_s = (n_shared_flags == n_samp) ? 1 : 0;
+        // the map is written (its extent is not an argument: to the end of its arena block)
+        auto & pc = pointing_cache::global();
+        pc.wrote(d_zmap, 0);
         if (deterministic_mode()) {
             // debug mode: the reference host path's summation order, bit for bit (deterministic.hip)
             deterministic_scatter(0, d_g2l, d_zmap, n_pix_submap, nnz, pixel_index, d_pixels, weight_index,
@@ -2374,6 +2631,12 @@ int toast_hip_build_noise_weighted_dev(
         }
         std::vector<int32_t> fidx(n_det, 0);
         if (use_d) std::memcpy(fidx.data(), flag_index, sizeof(int32_t) * n_det);
+        // the packed pointing cache serves the shape k_build_noise_weighted_v2 serves (its own rows are always aligned)
+        const bool v2_rest = vec2_lanes() && nnz == 3 && !det_major_grid() && (n_samp & 1) == 0 && rows_16b(d_det_data) &&
+                             (!use_d || rows_16b(d_det_flags)) && (!use_s || rows_16b(d_shared_flags));
+        pointing_cache::Hit hit;
+        const bool packed = v2_rest && pc.consume(current_device(), stream, d_pixels, pixel_index, d_weights, weight_index,
+                                                  n_det, n_samp, intervals, n_view, &hit);
         ParamBlock pb;
         const size_t o_ch = pb.push_vec(chunks);
         const size_t o_pi = pb.push(pixel_index, sizeof(int32_t) * n_det);
@@ -2381,10 +2644,25 @@ int toast_hip_build_noise_weighted_dev(
         const size_t o_di = pb.push(data_index, sizeof(int32_t) * n_det);
         const size_t o_fi = pb.push_vec(fidx);
         const size_t o_ds = pb.push(det_scale, sizeof(double) * n_det);
+        const size_t o_pr = packed ? pb.push_vec(hit.pix_row) : 0;
+        const size_t o_qr = packed ? pb.push_vec(hit.qu_row) : 0;
+        const size_t o_cl = packed ? pb.push_vec(hit.cal) : 0;
         const char * d = pb.commit(as_stream(stream));
         const FastDiv dv = make_fastdiv(n_pix_submap);
         const dim3 grid = chunk_grid(n_det, chunks.size());
         hipStream_t st = as_stream(stream);
+        if (packed) {
+            const bool pr = pair_detectors() && n_det >= 2;
+            const dim3 gp((unsigned)(pr ? (n_det + 1) / 2 : n_det), grid.y, 1);
+            hipLaunchKernelGGL(pr ? k_build_noise_weighted_pk<2> : k_build_noise_weighted_pk<1>, gp, dim3(kThreads), 0, st,
+                               (const Chunk *)(d + o_ch), (int)chunks.size(), (int)n_det, (const int32_t *)(d + o_pr),
+                               (const int32_t *)(d + o_qr), (const double *)(d + o_cl), (const int32_t *)(d + o_di),
+                               (const int32_t *)(d + o_fi), (const double *)(d + o_ds), d_g2l, d_zmap, hit.pix,
+                               reinterpret_cast<const double2 *>(hit.qu), d_det_data, d_det_flags, det_flag_mask, use_d,
+                               d_shared_flags, shared_flag_mask, use_s, dv, n_samp);
+            check_launch();
+            return;
+        }
 #define TH_BNW_ARGS                                                                               \
     (const Chunk *)(d + o_ch), (int)chunks.size(), (const int32_t *)(d + o_pi),                   \
         (const int32_t *)(d + o_wi), (const int32_t *)(d + o_di), (const int32_t *)(d + o_fi),    \
@@ -2443,6 +2721,7 @@ int toast_hip_noise_weight_dev(double * d_det_data, int64_t n_samp, const int32_
         const size_t o_di = pb.push(data_index, sizeof(int32_t) * n_det);
         const size_t o_w = pb.push(detector_weights, sizeof(double) * n_det);
         const char * d = pb.commit(as_stream(stream));
+        pointing_cache::global().wrote_rows(d_det_data, sizeof(double) * (size_t)n_samp, data_index, n_det);
         const bool v2 = vec2_lanes() && (n_samp & 1) == 0 && rows_16b(d_det_data);
         hipLaunchKernelGGL(v2 ? k_noise_weight_v2 : k_noise_weight, chunk_grid(n_det, chunks.size()), dim3(kThreads), 0,
                            as_stream(stream), (const Chunk *)(d + o_ch), (int)chunks.size(),
@@ -2621,6 +2900,7 @@ int toast_hip_cov_apply_diag_dev(int64_t n_sub, int64_t subsize, int64_t nnz, co
     return guarded([&] {
         const int64_t n_px = n_sub * subsize;
         if (n_px <= 0) return;
+        if (nnz > 0) pointing_cache::global().wrote(d_vec, sizeof(double) * (size_t)n_px * (size_t)nnz);
         const dim3 grid = flat_grid(n_px);
         hipStream_t st = as_stream(stream);
         switch (nnz) {
@@ -2641,6 +2921,8 @@ int toast_hip_template_offset_add_to_signal_multi_dev(
     int64_t n_det, double * d_det_data, int64_t n_samp, const toast_hip_interval * intervals,
     int64_t n_view, void * stream) {
     return guarded([&] {
+        // (pointing cache: what this call writes, each to the end of its arena block)
+        pointing_cache::global().wrote(d_det_data, 0);
         if (n_det <= 0) return;
         if (step_length <= 0) fail_arg("step_length must be positive");
         const auto chunks = make_chunks(intervals, n_view, n_samp);
@@ -2677,6 +2959,8 @@ int toast_hip_template_offset_project_signal_multi_dev(
     const int64_t * n_amp_views, double * d_amplitudes, const uint8_t * d_amplitude_flags, int64_t n_det,
     int64_t n_samp, const toast_hip_interval * intervals, int64_t n_view, void * stream) {
     return guarded([&] {
+        // (pointing cache: what this call writes, each to the end of its arena block)
+        pointing_cache::global().wrote(d_amplitudes, 0);
         if (n_det <= 0) return;
         if (step_length <= 0) fail_arg("step_length must be positive");
         if (flag_index != nullptr && d_flag_data != nullptr) {
@@ -2755,6 +3039,8 @@ int offset_accumulate_impl(
     const uint8_t * d_shared_flags, int64_t n_shared_flags, uint8_t shared_flag_mask, const int32_t * data_index,
     const double * d_signal, void * stream) {
     return guarded([&] {
+        // (pointing cache: what this call writes, to the end of its arena block)
+        pointing_cache::global().wrote(d_zmap, 0);
         if (n_det <= 0) return;
         if (step_length <= 0) fail_arg("step_length must be positive");
         if (nnz != 1 && nnz != 3) fail_arg("offset_accumulate: nnz must be 1 or 3");
@@ -2870,6 +3156,8 @@ static int offset_scan_project_launch(
     int64_t n_view, const int32_t * signal_index, const double * d_signal, void * stream,
     const char * fn = __builtin_FUNCTION()) {
     return guarded([&] {
+        // (pointing cache: what this call writes, to the end of its arena block)
+        pointing_cache::global().wrote(d_amplitudes_out, 0);
         if (n_det <= 0) return;
         const bool sigbuf = d_signal != nullptr;
         if (sigbuf && signal_index == nullptr) fail_arg("offset_scan_project: signal_index is NULL");
@@ -2964,6 +3252,8 @@ int toast_hip_template_offset_apply_diag_precond_dev(const double * d_offset_var
                                                      double * d_amp_out, int64_t n_amp,
                                                      void * stream) {
     return guarded([&] {
+        // (pointing cache: what this call writes, each to the end of its arena block)
+        pointing_cache::global().wrote(d_amp_out, 0);
         if (n_amp <= 0) return;
         hipLaunchKernelGGL(k_offset_apply_diag_precond, flat_grid(n_amp), dim3(kThreads), 0,
                            as_stream(stream), n_amp, d_offset_var, d_amp_in, d_amplitude_flags,
@@ -3575,6 +3865,25 @@ void probe_byte_mix(const int64_t * pixels, const double * weights, const double
     if (sink == nullptr) TH_HIP(hipMalloc(reinterpret_cast<void **>(&sink), sizeof(double)));
     hipLaunchKernelGGL(k_probe_byte_mix, dim3((unsigned)n_det, (unsigned)gy), dim3(kThreads), 0, st, pixels, weights, tod, out,
                        sink, n_samp);
+    check_launch();
+}
+
+void launch_pointing_pack(int kind, const void * src, void * dst, const int32_t * rows, int n_rows, int64_t n_samp,
+                          hipStream_t st) {
+    if (n_rows <= 0 || n_samp <= 0) return;
+    ParamBlock pb;
+    const size_t o_r = pb.push(rows, sizeof(int32_t) * (size_t)n_rows);
+    const char * d = pb.commit(st);
+    int64_t gx = (n_samp + kThreads - 1) / kThreads;
+    if (gx > 256) gx = 256;
+    const dim3 grid((unsigned)gx, (unsigned)n_rows, 1);
+    if (kind == pointing_cache::kPixels) {
+        hipLaunchKernelGGL(k_pack_pixels32, grid, dim3(kThreads), 0, st, static_cast<const int64_t *>(src),
+                           static_cast<int32_t *>(dst), (const int32_t *)(d + o_r), n_samp);
+    } else {
+        hipLaunchKernelGGL(k_pack_qu, grid, dim3(kThreads), 0, st, static_cast<const double *>(src),
+                           static_cast<double2 *>(dst), (const int32_t *)(d + o_r), n_samp);
+    }
     check_launch();
 }
 

@@ -15,6 +15,7 @@
 // operations.  The per-sample arithmetic is the device functions of hpix_math.hpp that the
 // stand-alone kernels use, so pixels are bit-identical and weights identical to the cached path.
 #include "kernel_common.hpp"
+#include "pointing_cache.hpp"
 
 namespace {
 
@@ -971,6 +972,11 @@ int toast_hip_otf_pixels_healpix_dev(const toast_hip_otf_pointing * pointing, co
                            (const Chunk *)(d + o_ch), (int)chunks.size(), (int)n_det, h.dev,
                            (const int32_t *)(d + o_pi), d_pixels, d_hit_submaps, n_samp);
         check_launch();
+        // provenance for the packed pointing cache (pointing_cache.hpp), as toast_hip_pixels_healpix_dev
+        auto & pc = pointing_cache::global();
+        pc.wrote(d_hit_submaps, (size_t)n_submap);
+        pc.seal(pointing_cache::kPixels, current_device(), stream, d_pixels, n_samp, pixel_index, n_det, intervals, n_view, pointing->nside,
+                nullptr);
     });
 }
 
@@ -999,6 +1005,15 @@ int toast_hip_otf_stokes_weights_dev(const toast_hip_otf_pointing * pointing, co
         else TH_OTF_W(2);
 #undef TH_OTF_W
         check_launch();
+        auto & pc = pointing_cache::global();
+        if (h.mode != 0) {
+            // three outputs: the intensity weight of row weight_index[det] is the descriptor's cal[det] (1 without one)
+            const std::vector<double> ones((size_t)n_det, 1.0);
+            pc.seal(pointing_cache::kWeights, current_device(), stream, d_weights, n_samp, weight_index, n_det, intervals, n_view, 0,
+                    pt.cal != nullptr ? pt.cal : ones.data());
+        } else {
+            pc.wrote_rows(d_weights, sizeof(double) * (size_t)n_samp, weight_index, n_det);
+        }
     });
 }
 

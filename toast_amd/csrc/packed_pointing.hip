@@ -16,6 +16,7 @@
 // compute exactly what k_offset_accumulate_v2 / k_offset_scan_project_v2 compute from the original arrays -- same
 // products, same order -- from 20 B per sample, without the division and the global2local gather.
 #include "kernel_common.hpp"
+#include "pointing_cache.hpp"
 
 #include "../../include/toast_hip.h"
 
@@ -975,6 +976,8 @@ int toast_hip_offset_accumulate_packed_dev(
     const double * det_scale, int pair_words, const float * d_pair_corr, int64_t n_det, int64_t n_samp,
     const toast_hip_interval * intervals, int64_t n_view, void * stream) {
     return guarded([&] {
+        // (pointing cache: what this call writes, each to the end of its arena block)
+        pointing_cache::global().wrote(d_zmap, 0);
         if (d_pair_corr != nullptr && !pair_words) fail_arg("offset_accumulate_packed: pair weight sums need pair words");
         if (n_det <= 0) return;
         if (step_length <= 0) fail_arg("step_length must be positive");
@@ -1025,6 +1028,8 @@ int toast_hip_offset_scan_project_packed_dev(
     const double * d_qu, const double * d_cal, const double * det_weights, int pair_words, const float * d_pair_corr,
     int64_t n_det, int64_t n_samp, const toast_hip_interval * intervals, int64_t n_view, void * stream) {
     return guarded([&] {
+        // (pointing cache: what this call writes, each to the end of its arena block)
+        pointing_cache::global().wrote(d_amps_out, 0);
         if (n_det <= 0) return;
         if (d_pair_corr != nullptr && !pair_words) fail_arg("offset_scan_project_packed: pair weight sums need pair words");
         if (step_length <= 0) fail_arg("step_length must be positive");

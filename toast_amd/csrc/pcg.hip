@@ -14,6 +14,7 @@
 // Several processes: the local dot product is summed over the ranks by the library's communicator on the same stream
 // (toast_hip_comm, comm.cpp) before the stage kernel reads it.
 #include "kernel_common.hpp"
+#include "pointing_cache.hpp"
 
 #include "../../include/toast_hip.h"
 
@@ -335,6 +336,8 @@ static void dot_launch(int mode, void * d_state, int64_t n, double * d_x, const 
 int toast_hip_pcg_dot_dev(void * d_state, int64_t n, const double * d_x, const double * d_y, const uint8_t * d_flags_x,
                           const uint8_t * d_flags_y, int accumulate, int stage, void * stream) {
     return guarded([&] {
+        // (pointing cache: what this call writes, each to the end of its arena block)
+        pointing_cache::global().wrote(d_state, 0);
         dot_launch(kDotPlain, d_state, n, const_cast<double *>(d_x), d_y, d_flags_x, d_flags_y, DotFused{}, accumulate,
                    stage, stream);
     });
@@ -344,6 +347,10 @@ int toast_hip_pcg_step_dot_dev(void * d_state, int64_t n, const double * d_propo
                                const double * d_lhs_out, double * d_residual, const uint8_t * d_flags, int accumulate,
                                int stage, void * stream) {
     return guarded([&] {
+        // (pointing cache: what this call writes, each to the end of its arena block)
+        pointing_cache::global().wrote(d_state, 0);
+        pointing_cache::global().wrote(d_result, 0);
+        pointing_cache::global().wrote(d_residual, 0);
         DotFused f{};
         f.p = d_proposal;
         f.result = d_result;
@@ -356,6 +363,9 @@ int toast_hip_pcg_precond_diag_dot_dev(void * d_state, int64_t n, const double *
                                        const uint8_t * d_flags_residual, double * d_out, const uint8_t * d_flags_out,
                                        int accumulate, int stage, void * stream) {
     return guarded([&] {
+        // (pointing cache: what this call writes, each to the end of its arena block)
+        pointing_cache::global().wrote(d_state, 0);
+        pointing_cache::global().wrote(d_out, 0);
         if (d_flags_residual == nullptr) fail_arg("the diagonal preconditioner needs the amplitude flags");
         DotFused f{};
         f.var = d_var;
@@ -367,6 +377,9 @@ int toast_hip_pcg_precond_diag_dot_dev(void * d_state, int64_t n, const double *
 int toast_hip_pcg_step_dev(const void * d_state, int64_t n, const double * d_proposal, double * d_result,
                            const double * d_lhs_out, double * d_residual, void * stream) {
     return guarded([&] {
+        // (pointing cache: what this call writes, each to the end of its arena block)
+        pointing_cache::global().wrote(d_result, 0);
+        pointing_cache::global().wrote(d_residual, 0);
         if (n <= 0) return;
         hipLaunchKernelGGL(k_pcg_step, flat_grid(n), dim3(kThreads), 0, as_stream(stream),
                            static_cast<const PcgState *>(d_state), n, d_proposal, d_result, d_lhs_out, d_residual);
@@ -376,6 +389,8 @@ int toast_hip_pcg_step_dev(const void * d_state, int64_t n, const double * d_pro
 
 int toast_hip_pcg_stage_dev(void * d_state, int stage, int allreduce, void * stream) {
     return guarded([&] {
+        // (pointing cache: what this call writes, each to the end of its arena block)
+        pointing_cache::global().wrote(d_state, 0);
         if (stage < 1 || stage > 3) fail_arg("pcg stage must be 1, 2 or 3");
         PcgState * s = static_cast<PcgState *>(d_state);
         if (allreduce) {
@@ -390,6 +405,8 @@ int toast_hip_pcg_stage_dev(void * d_state, int stage, int allreduce, void * str
 int toast_hip_pcg_axpby_dev(const void * d_state, int64_t n, int a_sel, const double * d_x, int b_sel, double * d_y,
                             void * stream) {
     return guarded([&] {
+        // (pointing cache: what this call writes, each to the end of its arena block)
+        pointing_cache::global().wrote(d_y, 0);
         if (n <= 0) return;
         hipLaunchKernelGGL(k_pcg_axpby, flat_grid(n), dim3(kThreads), 0, as_stream(stream),
                            static_cast<const PcgState *>(d_state), n, a_sel, d_x, b_sel, d_y);
@@ -399,6 +416,8 @@ int toast_hip_pcg_axpby_dev(const void * d_state, int64_t n, int a_sel, const do
 
 int toast_hip_pcg_status_dev(void * d_state, int lag, toast_hip_pcg_status * out, void * stream) {
     return guarded([&] {
+        // (pointing cache: what this call writes, each to the end of its arena block)
+        pointing_cache::global().wrote(d_state, 0);
         if (lag < 0 || lag >= StatusRing::kSlots) fail_arg("pcg status lag must be 0 .. 3");
         StatusRing & r = ring();
         hipStream_t st = as_stream(stream);

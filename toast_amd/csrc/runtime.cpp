@@ -1,6 +1,7 @@
 // runtime.cpp -- see runtime.hpp.  Reference counterpart of the memory manager:
 // /root/reference/src/toast/_libtoast/accelerator.cpp:233-766 (OmpManager).
 #include "runtime.hpp"
+#include "pointing_cache.hpp"
 
 #include <chrono>
 #include <condition_variable>
@@ -16,6 +17,10 @@
 #include <vector>
 
 namespace toast_hip {
+
+namespace pointing_cache {
+size_t evict_from(bool small_arena);   // (below, with the cache's device side)
+}
 
 namespace {
 thread_local std::string g_last_error;
@@ -794,7 +799,14 @@ void * Manager::device_alloc(size_t nbytes, int kind) {
         if (p != nullptr) return p;
     }
     Arena & a = nbytes < kSmallBlock ? small_arena() : big_arena();
-    void * p = a.alloc(nbytes, stream_);
+    // the packed pointing cache lives in this arena's free space on sufferance: a request that the free ranges cannot
+    // serve gets the cache's blocks before the arena asks the driver for another slab
+    void * p = nullptr;
+    if (pointing_cache::global().holds_blocks()) {
+        p = a.alloc(nbytes, stream_, false);
+        if (p == nullptr) pointing_cache::evict_from(nbytes < kSmallBlock);
+    }
+    if (p == nullptr) p = a.alloc(nbytes, stream_);
     if (p == nullptr) {
         // the driver refused a slab: slabs that hold nothing may be what is in the way (a 16 GB default slab with one
         // block in it does not move, but empty ones do); then exactly what is asked for
@@ -810,6 +822,7 @@ void * Manager::device_alloc(size_t nbytes, int kind) {
 
 void Manager::device_free(void * p) {
     if (p == nullptr) return;
+    pointing_cache::global().freed(p);   // seals and packed copies of what lies in the block go with it
     if (big_arena().release(p) || small_arena().release(p) || stream_arena().release(p)) return;
     (void)hipFree(p);
 }
@@ -905,6 +918,7 @@ void zone_references_release(const ZoneRefs & r) {
 void Manager::drop_arenas() {
     builder_wait();
     (void)hipDeviceSynchronize();
+    pointing_cache::global().drop_all(pointing_cache::kDropManager, true);   // (every copy back before the slabs go)
     drop_param_blocks();
     big_arena().destroy();
     small_arena().destroy();
@@ -1056,6 +1070,7 @@ void Manager::adopt(const void * host, size_t nbytes, void * device, const char 
 void Manager::reset(const void * host, size_t nbytes, const char * name) {
     require_device();
     Entry & e = lookup(host, nbytes, name, "reset data");
+    pointing_cache::global().wrote(e.dev, nbytes, pointing_cache::kDropManager);
     const double t0 = trace_begin();
     TH_HIP(hipMemsetAsync(e.dev, 0, nbytes, stream_));
     trace("reset", e.name, nbytes, t0);   // (enqueue time only: the fill itself is asynchronous)
@@ -1064,6 +1079,7 @@ void Manager::reset(const void * host, size_t nbytes, const char * name) {
 void Manager::update_device(const void * host, size_t nbytes, const char * name) {
     require_device();
     Entry & e = lookup(host, nbytes, name, "update device");
+    pointing_cache::global().wrote(e.dev, nbytes, pointing_cache::kDropManager);
     const double t0 = trace_begin();
     pin_for_transfer(host, e);
     if (e.host_registered) {
@@ -1080,6 +1096,7 @@ void Manager::update_device_parts(const void * host, size_t nbytes, const char *
                                   int n_parts) {
     require_device();
     Entry & e = lookup(host, nbytes, name, "update device");
+    pointing_cache::global().wrote(e.dev, nbytes, pointing_cache::kDropManager);
     if (n_parts < 1 || part_end == nullptr || part_end[n_parts - 1] != nbytes) {
         fail_arg("update_device_parts: the last part must end at the size of the buffer");
     }
@@ -1289,6 +1306,124 @@ Staging::~Staging() {
     }
 }
 
+// ------------------------------------------------------------------ packed pointing cache: the device side
+namespace pointing_cache {
+namespace {
+
+bool stream_capturing(void * stream) {
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(static_cast<hipStream_t>(stream), &cs) != hipSuccess) {
+        (void)hipGetLastError();
+        return true;   // (cannot tell: as if it were)
+    }
+    return cs != hipStreamCaptureStatusNone;
+}
+
+bool dev_block_of(const void * p, const char ** base, size_t * bytes) {
+    if (alloc_policy().plain) return false;
+    return big_arena().block_of(p, base, bytes) || small_arena().block_of(p, base, bytes) ||
+           stream_arena().block_of(p, base, bytes);
+}
+
+// from the free ranges of the slabs the arena already holds: the cache never makes the process take memory from the driver
+void * dev_take(size_t bytes, void * stream) {
+    if (alloc_policy().plain) return nullptr;
+    Arena & a = bytes < kSmallBlock ? small_arena() : big_arena();
+    return a.alloc(bytes, static_cast<hipStream_t>(stream), false);
+}
+
+// Giving a packed copy back.  The first time a block is asked for, an event is recorded behind the last kernel that can
+// read it; the block returns to the arena once that event has completed.  A drop can come at any moment -- also while
+// another stream of the thread is being captured, when a synchronising call would invalidate the capture -- so
+// wait = false only polls (hipEventQuery) and leaves the block with the registry until a later call finds the event
+// done.  wait = true (an allocation needs the room; allocating is not something a capture allows either) waits for it.
+std::mutex g_parting_mutex;
+std::unordered_map<void *, hipEvent_t> g_parting;   // block -> the event behind its last reader
+
+bool dev_give(void * p, void * stream, bool wait) {
+    hipEvent_t ev = nullptr;
+    {
+        std::lock_guard<std::mutex> lock(g_parting_mutex);
+        auto it = g_parting.find(p);
+        if (it != g_parting.end()) ev = it->second;
+    }
+    if (ev == nullptr) {
+        if (stream_capturing(stream)) return false;   // (an event recorded now would become part of the capture)
+        if (hipEventCreateWithFlags(&ev, hipEventDisableTiming) != hipSuccess) {
+            (void)hipGetLastError();
+            return false;
+        }
+        if (hipEventRecord(ev, static_cast<hipStream_t>(stream)) != hipSuccess) {
+            (void)hipGetLastError();
+            (void)hipEventDestroy(ev);
+            return false;
+        }
+        std::lock_guard<std::mutex> lock(g_parting_mutex);
+        g_parting[p] = ev;
+    }
+    if ((wait ? hipEventSynchronize(ev) : hipEventQuery(ev)) != hipSuccess) {
+        (void)hipGetLastError();   // hipErrorNotReady: later
+        return false;
+    }
+    {
+        std::lock_guard<std::mutex> lock(g_parting_mutex);
+        g_parting.erase(p);
+    }
+    (void)hipEventDestroy(ev);
+    // (a block of an arena that has been destroyed meanwhile is nobody's any more: done as well)
+    (void)(big_arena().release(p) || small_arena().release(p));
+    return true;
+}
+
+bool in_big_arena(const void * p) { return big_arena().owns(p); }
+bool in_small_arena(const void * p) { return small_arena().owns(p); }
+
+void dev_pack(int kind, const void * src, void * dst, const int32_t * rows, int n_rows, int64_t n_samp, void * stream) {
+    launch_pointing_pack(kind, src, dst, rows, n_rows, n_samp, static_cast<hipStream_t>(stream));
+}
+
+bool dev_may_cache(void * stream) { return !deterministic_mode() && !stream_capturing(stream); }
+
+void print_stats_at_exit() {
+    const Stats s = global().stats();
+    std::fprintf(stderr,
+                 "[toast_hip] pointing cache: seals %lld packs %lld hits %lld misses %lld evictions %lld pack_no_room %lld "
+                 "packed_bytes %llu drops{foreign_call %lld overlap_write %lld free %lld manager %lld reseal %lld explicit %lld}\n",
+                 (long long)s.seals, (long long)s.packs, (long long)s.hits, (long long)s.misses, (long long)s.evictions,
+                 (long long)s.pack_no_room, (unsigned long long)s.packed_bytes, (long long)s.drops[kDropForeignCall],
+                 (long long)s.drops[kDropOverlapWrite], (long long)s.drops[kDropFree], (long long)s.drops[kDropManager],
+                 (long long)s.drops[kDropReseal], (long long)s.drops[kDropExplicit]);
+}
+
+}  // namespace
+
+Registry & global() {
+    // (never destroyed: nothing of it may run into the runtime's own exit)
+    static Registry * const r = [] {
+        static const Backend be = {dev_block_of, dev_take, dev_give, dev_pack, dev_may_cache};
+        Registry * reg = new Registry(be);
+        const char * e = std::getenv("TOAST_HIP_POINTING_CACHE");
+        if (e != nullptr && e[0] == '0') reg->enable(false);
+        const char * t = std::getenv("TOAST_HIP_POINTING_CACHE_TRACE");
+        if (t != nullptr && t[0] == '1') std::atexit(print_stats_at_exit);
+        return reg;
+    }();
+    return *r;
+}
+
+// Manager::device_alloc: the packed copies that lie in the arena that could not serve a request (copies in the other
+// arena would be thrown away for nothing)
+size_t evict_from(bool small) { return global().evict(small ? in_small_arena : in_big_arena); }
+
+}  // namespace pointing_cache
+
+void pointing_cache_entered(const char * fn) noexcept {
+    try {
+        pointing_cache::global().entered(fn);
+    } catch (...) {
+    }
+}
+
 }  // namespace toast_hip
 
 // ------------------------------------------------------------------ C ABI: runtime part
@@ -1388,6 +1523,44 @@ int toast_hip_arena_zone_threshold(const double * rates, int n, double level, do
     return guarded([&] {
         if (rates == nullptr || threshold == nullptr || n < 0) fail_arg("toast_hip_arena_zone_threshold: null argument");
         *threshold = vmm_zone_threshold(rates, n, level);
+    });
+}
+
+int toast_hip_pointing_cache_stats(toast_hip_pointing_cache_stats_t * out) {
+    return guarded([&] {
+        if (out == nullptr) fail_arg("toast_hip_pointing_cache_stats: out is NULL");
+        const pointing_cache::Stats s = pointing_cache::global().stats();
+        out->enabled = pointing_cache::global().enabled() ? 1 : 0;
+        out->pack_after_calls = pointing_cache::kPackAfterCalls;
+        out->seals = s.seals;
+        out->packs = s.packs;
+        out->hits = s.hits;
+        out->misses = s.misses;
+        out->drops_foreign_call = s.drops[pointing_cache::kDropForeignCall];
+        out->drops_overlap_write = s.drops[pointing_cache::kDropOverlapWrite];
+        out->drops_free = s.drops[pointing_cache::kDropFree];
+        out->drops_manager = s.drops[pointing_cache::kDropManager];
+        out->drops_reseal = s.drops[pointing_cache::kDropReseal];
+        out->drops_explicit = s.drops[pointing_cache::kDropExplicit];
+        out->evictions = s.evictions;
+        out->pack_no_room = s.pack_no_room;
+        out->live_seals = s.live_seals;
+        out->packed_bytes = s.packed_bytes;
+    });
+}
+
+int toast_hip_pointing_cache_enable(int on) {
+    return guarded([&] { pointing_cache::global().enable(on != 0); });
+}
+
+int toast_hip_pointing_cache_drop(void) {
+    return guarded([&] { pointing_cache::global().drop_all(pointing_cache::kDropExplicit); });
+}
+
+int toast_hip_pointing_cache_selftest(uint64_t seed, int n_ops, int scenario) {
+    return guarded([&] {
+        const std::string e = pointing_cache::selftest(seed, n_ops, scenario);
+        if (!e.empty()) throw Error(TOAST_HIP_ERR_MEMORY, "pointing cache selftest: " + e);
     });
 }
 

@@ -43,10 +43,25 @@ void set_last_error(const std::string & msg);
 double call_trace_begin() noexcept;
 void call_trace_end(const char * fn, double t0) noexcept;
 
+// The packed pointing cache (pointing_cache.hpp) hears of every entry point: one that is not whitelisted as "writes only
+// through the pointers it declares" may have changed a sealed array and drops every seal (runtime.cpp).
+void pointing_cache_entered(const char * fn) noexcept;
+// kernels.hip: the pack kernels of the pointing cache, queued on st (kind: pointing_cache::Kind)
+void launch_pointing_pack(int kind, const void * src, void * dst, const int32_t * rows, int n_rows, int64_t n_samp,
+                          hipStream_t st);
+
+// the device that is current (0 when the runtime cannot say)
+inline int current_device() {
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess) (void)hipGetLastError();
+    return dev;
+}
+
 // Wrap the body of an extern "C" entry point.
 template <typename F>
 int guarded(F && f, const char * fn = __builtin_FUNCTION()) noexcept {
     try {
+        pointing_cache_entered(fn);
         const double t0 = call_trace_begin();
         f();
         if (t0 >= 0) call_trace_end(fn, t0);
