@@ -159,6 +159,13 @@ int toast_hip_arena_selftest(uint64_t seed, int n_ops, size_t granule, size_t sl
  * the same interval list, and nothing the library can see has written to them since, the third such call packs them
  * (int32 pixel + (Q, U), 20 instead of 32 B per sample; the intensity weight is the detector's cal) and this and the
  * later calls read the copy: same scan_map results bit for bit, build_noise_weighted up to the order of its atomics.
+ * Where detectors (2 b, 2 b + 1) of the packing call see the same pixel and carry opposite Q / U weights in (nearly)
+ * every sample -- the orthogonally polarised pairs of a focal plane, with equal cal and efficiency -- the copy takes the
+ * PAIR FORM instead: one int32 pixel word, (q_a, u_a) and the float2 sums (q_a + q_b, u_a + u_b) per pair-sample, 28 B
+ * for two detector-samples.  A sample the form cannot express exactly is marked and read from the caller's arrays, so
+ * the results are the plain form's; more than one marked pair-sample in a hundred (counted on the device and read back
+ * once per packing call) and the plain form is packed in the same call (pair_demotions).  A pair copy serves the calls
+ * whose detectors, taken in twos, are pairs of the call that packed; TOAST_HIP_PAIR=0 switches the pair form off.
  * Every entry point that is not known to write only through the pointers it declares drops the seals.  A caller whose OWN
  * kernels write into a sealed arena block must say so with toast_hip_pointing_cache_drop.
  * TOAST_HIP_POINTING_CACHE=0 switches the cache off; TOAST_HIP_POINTING_CACHE_TRACE=1 prints these counters at exit. */
@@ -179,6 +186,9 @@ typedef struct toast_hip_pointing_cache_stats_t {
     int64_t pack_no_room;         /* packs that found no free arena space (the call ran un-cached) */
     int64_t live_seals;
     uint64_t packed_bytes;        /* bytes in packed copies now */
+    int64_t pair_packs;           /* packs that took the pair form (counted in packs as well) */
+    int64_t pair_demotions;       /* packs that tried the pair form and took the plain one */
+    int64_t pair_escapes;         /* marked pair-samples inside the intervals of the live pair copies */
 } toast_hip_pointing_cache_stats_t;
 int toast_hip_pointing_cache_stats(toast_hip_pointing_cache_stats_t * out);
 int toast_hip_pointing_cache_enable(int on);
@@ -186,9 +196,11 @@ int toast_hip_pointing_cache_drop(void);
 /* The registry driven on HOST memory (no device needed).  scenario 0: a seeded random sequence of n_ops seal / consume /
  * overlapping write / free / non-whitelisted call / allocation pressure steps, checked against a model that knows when a
  * hit is allowed and against the arrays' contents, with a stand-in backend that comes back into the registry from its pack
- * and defers its releases; 1-7: one named scenario (the pack happens on the third call; another interval list misses; a
+ * and defers its releases; 1-10: one named scenario (the pack happens on the third call; another interval list misses; a
  * reseal discards the copy; eviction under allocation pressure; a non-whitelisted call drops every seal; an expansion that
- * does not seal still drops what it overwrites; the pack re-enters the registry).  0 = sound. */
+ * does not seal still drops what it overwrites; the pack re-enters the registry; co-pointing pairs take the pair form and
+ * hit; escapes over the threshold demote to the plain form in the same call; a call that splits a pair misses).
+ * 0 = sound. */
 int toast_hip_pointing_cache_selftest(uint64_t seed, int n_ops, int scenario);
 /* Raw device memory from the arena (flags = -1, also -2: a read-mostly block; -3 = a STREAMED block: a timestream that
  * sweeps read and write, placed in a slab whose 1 GB chunks come from two HBM zones in the pattern P Q Q P ... so that its

@@ -386,7 +386,8 @@ class _PointingCacheStats(C.Structure):
                 ("hits", C.c_int64), ("misses", C.c_int64), ("drops_foreign_call", C.c_int64),
                 ("drops_overlap_write", C.c_int64), ("drops_free", C.c_int64), ("drops_manager", C.c_int64),
                 ("drops_reseal", C.c_int64), ("drops_explicit", C.c_int64), ("evictions", C.c_int64),
-                ("pack_no_room", C.c_int64), ("live_seals", C.c_int64), ("packed_bytes", C.c_uint64)]
+                ("pack_no_room", C.c_int64), ("live_seals", C.c_int64), ("packed_bytes", C.c_uint64),
+                ("pair_packs", C.c_int64), ("pair_demotions", C.c_int64), ("pair_escapes", C.c_int64)]
 
 
 def pointing_cache_stats():

@@ -496,6 +496,143 @@ __global__ __launch_bounds__(kThreads) void k_scan_map_pk(
     }
 }
 
+// k_scan_map_pk on the PAIR FORM of the cache (k_pack_pairs_pp): one workgroup per pair (2 b, 2 b + 1) of the call, and per
+// lane and trip an int2 of pixel words, two double2 (q_a, u_a), one float4 of weight sums and, per detector, the
+// timestream pair -- 30 instead of 36 B per detector-sample, and ONE global2local look-up and ONE map gather per
+// pair-sample.  B's weights are (double)sum - q_a; a NaN sum reads them from the caller's weights row instead, a word
+// that says "escape" reads both pixels from the caller's pixel rows, and a wave with such a lane does that trip with a
+// look-up and a gather per detector.  scan_combine runs once per detector with that detector's cal, Q / U and det_w: the
+// same expressions in the same order on the same values as k_scan_map_pk, so the results are bit-identical.
+template <typename T>
+__global__ __launch_bounds__(kThreads) void k_scan_map_pp(
+    const Chunk * __restrict__ chunks, int n_chunks, int n_det, const int32_t * __restrict__ d_idx,
+    const int32_t * __restrict__ p_idx, const int32_t * __restrict__ w_idx, const int32_t * __restrict__ pair_row,
+    const double * __restrict__ cal, const int64_t * __restrict__ g2l, const T * __restrict__ map, double * __restrict__ tod,
+    const int32_t * __restrict__ word, const double2 * __restrict__ qu, const float2 * __restrict__ sums,
+    const int64_t * __restrict__ pixels, const double * __restrict__ weights,
+    FastDiv nps_div, double scale, int zero, int subtract, int mult,
+    const double * __restrict__ det_w, int64_t n_samp) {
+    constexpr int32_t kEsc = pointing_cache::kPairEscape;
+    const int det0 = 2 * blockIdx.x;
+    const bool two = det0 + 1 < n_det;
+    const int det1 = two ? det0 + 1 : det0;
+    double * drow[2] = {tod + (int64_t)d_idx[det0] * n_samp, tod + (int64_t)d_idx[det1] * n_samp};
+    // (the caller's own rows: read only where the copy says "escape")
+    const int64_t * prow[2] = {pixels + (int64_t)p_idx[det0] * n_samp, pixels + (int64_t)p_idx[det1] * n_samp};
+    const double * wrow_b = weights + (int64_t)w_idx[det1] * n_samp * 3;
+    const int64_t row = (int64_t)pair_row[blockIdx.x] * n_samp;
+    const int32_t * krow = word + row;
+    const double2 * qrow = qu + row;
+    const float2 * srow = sums + row;
+    const double w0[2] = {cal[det0], cal[det1]};
+    const bool fuse = det_w != nullptr;
+    const double dw[2] = {fuse ? det_w[det0] : 1.0, fuse ? det_w[det1] : 1.0};
+    for (int ci = blockIdx.y; ci < n_chunks; ci += gridDim.y) {
+        const Chunk c = chunks[ci];
+        const int head = (int)(c.first & 1);
+        const int64_t s0 = c.first + head;          // even
+        const int n_pair = (c.count - head) >> 1;
+        for (int j = threadIdx.x; j < n_pair; j += kThreads) {
+            const int64_t s = s0 + 2 * (int64_t)j;
+            // all streaming loads first
+            const int2 pw = *reinterpret_cast<const int2 *>(krow + s);
+            const double2 wa0 = qrow[s], wa1 = qrow[s + 1];
+            const float4 sm = *reinterpret_cast<const float4 *>(srow + s);
+            double2 dd[2] = {make_double2(0.0, 0.0), make_double2(0.0, 0.0)};
+            if (!zero) {
+                dd[0] = *reinterpret_cast<const double2 *>(drow[0] + s);
+                if (two) dd[1] = *reinterpret_cast<const double2 *>(drow[1] + s);
+            }
+            // B's weights: from the sums, or (NaN marker) from B's own row
+            double2 wb0 = make_double2((double)sm.x - wa0.x, (double)sm.y - wa0.y);
+            double2 wb1 = make_double2((double)sm.z - wa1.x, (double)sm.w - wa1.y);
+            if (sm.x != sm.x) wb0.x = wrow_b[3 * s + 1];
+            if (sm.y != sm.y) wb0.y = wrow_b[3 * s + 2];
+            if (sm.z != sm.z) wb1.x = wrow_b[3 * s + 4];
+            if (sm.w != sm.w) wb1.y = wrow_b[3 * s + 5];
+            const bool esc_a = pw.x == kEsc, esc_b = pw.y == kEsc;
+            const bool slow = __any(esc_a | esc_b);
+            int64_t pa[2] = {pw.x, pw.x}, pb[2] = {pw.y, pw.y};
+            if (slow) {
+                if (esc_a) {
+                    pa[0] = prow[0][s];
+                    pa[1] = prow[1][s];
+                }
+                if (esc_b) {
+                    pb[0] = prow[0][s + 1];
+                    pb[1] = prow[1][s + 1];
+                }
+            }
+            ScanGather qa[2], qb[2];
+            T a0[2], a1[2], a2[2], b0[2], b1[2], b2[2];
+            {
+                const int64_t ga = scan_submap(pa[0], nps_div), gb = scan_submap(pb[0], nps_div);
+                const int64_t la = g2l[ga], lb = g2l[gb];
+                qa[0] = scan_locate(pa[0], ga, la, nps_div);
+                qb[0] = scan_locate(pb[0], gb, lb, nps_div);
+                const T * ma = map + qa[0].off;
+                const T * mb = map + qb[0].off;
+                a0[0] = ma[0], a1[0] = ma[1], a2[0] = ma[2], b0[0] = mb[0], b1[0] = mb[1], b2[0] = mb[2];
+            }
+            if (slow) {   // (wave-uniform) a look-up and a gather of B's own
+                const int64_t ga = scan_submap(pa[1], nps_div), gb = scan_submap(pb[1], nps_div);
+                const int64_t la = g2l[ga], lb = g2l[gb];
+                qa[1] = scan_locate(pa[1], ga, la, nps_div);
+                qb[1] = scan_locate(pb[1], gb, lb, nps_div);
+                const T * ma = map + qa[1].off;
+                const T * mb = map + qb[1].off;
+                a0[1] = ma[0], a1[1] = ma[1], a2[1] = ma[2], b0[1] = mb[0], b1[1] = mb[1], b2[1] = mb[2];
+            } else {
+                qa[1] = qa[0], qb[1] = qb[0];
+                a0[1] = a0[0], a1[1] = a1[0], a2[1] = a2[0], b0[1] = b0[0], b1[1] = b1[0], b2[1] = b2[0];
+            }
+            dd[0].x = scan_combine(qa[0].hit, dd[0].x, w0[0], wa0.x, wa0.y, (double)a0[0], (double)a1[0], (double)a2[0], scale,
+                                   subtract, mult);
+            dd[0].y = scan_combine(qb[0].hit, dd[0].y, w0[0], wa1.x, wa1.y, (double)b0[0], (double)b1[0], (double)b2[0], scale,
+                                   subtract, mult);
+            if (fuse) {
+                dd[0].x *= dw[0];
+                dd[0].y *= dw[0];
+            }
+            *reinterpret_cast<double2 *>(drow[0] + s) = dd[0];
+            if (two) {
+                dd[1].x = scan_combine(qa[1].hit, dd[1].x, w0[1], wb0.x, wb0.y, (double)a0[1], (double)a1[1], (double)a2[1],
+                                       scale, subtract, mult);
+                dd[1].y = scan_combine(qb[1].hit, dd[1].y, w0[1], wb1.x, wb1.y, (double)b0[1], (double)b1[1], (double)b2[1],
+                                       scale, subtract, mult);
+                if (fuse) {
+                    dd[1].x *= dw[1];
+                    dd[1].y *= dw[1];
+                }
+                *reinterpret_cast<double2 *>(drow[1] + s) = dd[1];
+            }
+        }
+        // the peeled first sample and the odd last one: lanes 0 and 1 of the workgroup, one detector after the other
+        const int tail = (c.count - head) & 1;
+        if ((threadIdx.x == 0 && head) || (threadIdx.x == 1 && tail)) {
+            const int64_t s = (threadIdx.x == 0) ? c.first : c.first + c.count - 1;
+            const int32_t pw = krow[s];
+            const double2 wa = qrow[s];
+            const float2 sm = srow[s];
+            for (int e = 0; e < (two ? 2 : 1); ++e) {
+                double2 w = wa;
+                if (e == 1) {
+                    w.x = (sm.x != sm.x) ? wrow_b[3 * s + 1] : (double)sm.x - wa.x;
+                    w.y = (sm.y != sm.y) ? wrow_b[3 * s + 2] : (double)sm.y - wa.y;
+                }
+                const int64_t p = (pw == kEsc) ? prow[e][s] : (int64_t)pw;
+                const int64_t gs = scan_submap(p, nps_div);
+                const ScanGather q = scan_locate(p, gs, g2l[gs], nps_div);
+                const T * m = map + q.off;
+                double d = scan_combine(q.hit, zero ? 0.0 : drow[e][s], w0[e], w.x, w.y, (double)m[0], (double)m[1], (double)m[2],
+                                        scale, subtract, mult);
+                if (fuse) d *= dw[e];
+                drow[e][s] = d;
+            }
+        }
+    }
+}
+
 // The packed copies themselves: row k of the copy = row rows[k] of the caller's array, whole rows (what lies outside the
 // intervals is never read back: a consumer hits only with the interval list the array was expanded with).
 __global__ __launch_bounds__(kThreads) void k_pack_pixels32(const int64_t * __restrict__ src, int32_t * __restrict__ dst,
@@ -514,6 +651,69 @@ __global__ __launch_bounds__(kThreads) void k_pack_qu(const double * __restrict_
     for (int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x; i < n_samp; i += (int64_t)gridDim.x * kThreads) {
         d[i] = make_double2(s[3 * i + 1], s[3 * i + 2]);
     }
+}
+
+// The PAIR FORM of the packed copy (pointing_cache::PairLayout), in one sweep: detectors A and B of a pair -- the two
+// orthogonally polarised detectors of a focal-plane pixel -- see the same sky pixel in every sample and carry opposite
+// Q / U weights up to a few ulp, so the pair keeps ONE int32 pixel word (-1 kept; kPairEscape where the two differ),
+// (q_a, u_a) and the float2 sums (q_a + q_b, u_a + u_b), from which q_b = (double)sum - q_a comes back exactly
+// (packed_pointing.hip: k_pair_weights' test; a component that fails it gets a NaN marker): 28 B per pair-sample = 14
+// per detector-sample instead of 20.  The copy holds no second row of anything: the consumers read a marked sample
+// from the caller's own arrays, which the seal guarantees are unchanged.  rows: per pair (pixel row A, pixel row B,
+// weight row A, weight row B), B = -1 for a lone detector.  Whole rows are written (dst given); the marked pair-samples
+// are COUNTED only inside the intervals (ivl: first, last, ...), where the arrays hold something defined.
+__global__ __launch_bounds__(kThreads) void k_pack_pairs_pp(
+    const int64_t * __restrict__ pixels, const double * __restrict__ weights, const int32_t * __restrict__ rows,
+    const int64_t * __restrict__ ivl, int n_view, int ivl_sorted, int64_t s_begin, int64_t s_end, int64_t n_samp,
+    int32_t * __restrict__ word, double2 * __restrict__ qu, float2 * __restrict__ sums,
+    unsigned long long * __restrict__ n_escaped) {
+    const int32_t * r = rows + 4 * blockIdx.y;
+    const bool lone = r[1] < 0;
+    const int64_t * pa_row = pixels + (int64_t)r[0] * n_samp;
+    const int64_t * pb_row = pixels + (int64_t)(lone ? r[0] : r[1]) * n_samp;
+    const double * wa_row = weights + (int64_t)r[2] * n_samp * 3;
+    const double * wb_row = weights + (int64_t)(lone ? r[2] : r[3]) * n_samp * 3;
+    const int64_t out = (int64_t)blockIdx.y * n_samp;
+    auto sum_or_marker = [](double a, double b) {
+        const double d = a + b;
+        const float f = (float)d;
+        return ((double)f == d && (double)f - a == b) ? f : __builtin_nanf("");
+    };
+    int escaped = 0;
+    for (int64_t i = s_begin + (int64_t)blockIdx.x * kThreads + threadIdx.x; i < s_end; i += (int64_t)gridDim.x * kThreads) {
+        const int64_t pa = pa_row[i], pb = pb_row[i];
+        const double qa = wa_row[3 * i + 1], ua = wa_row[3 * i + 2];
+        float2 f = make_float2(0.0f, 0.0f);
+        // (a sample without a pixel in either detector contributes nothing and its weights are never used -- under shared
+        //  flags they are often the reference's NaN: no marker for it)
+        if (!lone && !((pa < 0) & (pb < 0))) {
+            f.x = sum_or_marker(qa, wb_row[3 * i + 1]);
+            f.y = sum_or_marker(ua, wb_row[3 * i + 2]);
+        }
+        const int32_t w = (pa == pb) ? (int32_t)pa : pointing_cache::kPairEscape;
+        // inside an interval?  A sorted, disjoint list (the launcher looked) is searched, any other is scanned.
+        bool in_view = false;
+        if (ivl_sorted) {
+            int lo = 0, hi = n_view;   // the last interval that starts at or before i
+            while (lo < hi) {
+                const int mid = (lo + hi) >> 1;
+                if (ivl[2 * mid] <= i) lo = mid + 1;
+                else hi = mid;
+            }
+            in_view = lo > 0 && i < ivl[2 * (lo - 1) + 1];
+        } else {
+            for (int v = 0; v < n_view; ++v) in_view |= (i >= ivl[2 * v]) & (i < ivl[2 * v + 1]);
+        }
+        if (in_view & ((w == pointing_cache::kPairEscape) | (f.x != f.x) | (f.y != f.y))) ++escaped;
+        if (word != nullptr) {
+            word[out + i] = w;
+            qu[out + i] = make_double2(qa, ua);
+            sums[out + i] = f;
+        }
+    }
+    // one atomic per wave that saw any
+    for (int o = warpSize / 2; o > 0; o >>= 1) escaped += __shfl_xor(escaped, o);
+    if (escaped != 0 && (threadIdx.x & (warpSize - 1)) == 0) atomicAdd(n_escaped, (unsigned long long)escaped);
 }
 
 // ------------------------------------------------------------------------------------
@@ -902,6 +1102,175 @@ __global__ __launch_bounds__(kThreads) void k_build_noise_weighted_pk(
                 if (key < 0) continue;
                 const double sd = drow[e][s] * ds[e];
                 const double2 w = qrow[e][s];
+                double * z = zmap + NNZ * key;
+                unsafeAtomicAdd(z, sd * wi[e]);
+                unsafeAtomicAdd(z + 1, sd * w.x);
+                unsafeAtomicAdd(z + 2, sd * w.y);
+            }
+        }
+    }
+}
+
+// k_build_noise_weighted_pk<2> on the PAIR FORM of the cache (k_pack_pairs_pp, k_scan_map_pp): per lane and trip an int2 of
+// pixel words, two double2 (q_a, u_a), a float4 of weight sums and, per detector, the timestream pair and the flag pair --
+// 23 instead of 29 B per detector-sample.  One global2local look-up per pair-sample, and the two detectors' products are
+// added before the scan without asking (the key is common); the `good` predicates stay per detector.  A wave with a lane
+// whose word says "escape" reads that lane's pixels from the caller's rows and takes k_build_noise_weighted_pk's two-key
+// path for the trip.  Same products, same scan: the map differs from the _pk kernel's by the order of the atomics only.
+__global__ __launch_bounds__(kThreads) void k_build_noise_weighted_pp(
+    const Chunk * __restrict__ chunks, int n_chunks, int n_det, const int32_t * __restrict__ p_idx,
+    const int32_t * __restrict__ w_idx, const int32_t * __restrict__ pair_row, const double * __restrict__ cal,
+    const int32_t * __restrict__ d_idx, const int32_t * __restrict__ f_idx, const double * __restrict__ det_scale,
+    const int64_t * __restrict__ g2l, double * __restrict__ zmap,
+    const int32_t * __restrict__ word, const double2 * __restrict__ qu, const float2 * __restrict__ sums,
+    const int64_t * __restrict__ pixels, const double * __restrict__ weights,
+    const double * __restrict__ tod, const uint8_t * __restrict__ dflags, uint8_t dmask,
+    int use_dflags, const uint8_t * __restrict__ sflags, uint8_t smask, int use_sflags,
+    FastDiv nps_div, int64_t n_samp) {
+    constexpr int NNZ = 3;
+    constexpr int E = 2;
+    constexpr int32_t kEsc = pointing_cache::kPairEscape;
+    const int det0 = E * blockIdx.x;
+    int dets[E];
+    bool on[E];
+    const int64_t * prow[E];
+    const double * drow[E];
+    const uint8_t * frow[E];
+    double ds[E], wi[E];
+#pragma unroll
+    for (int e = 0; e < E; ++e) {
+        on[e] = det0 + e < n_det;
+        dets[e] = on[e] ? det0 + e : det0;
+        prow[e] = pixels + (int64_t)p_idx[dets[e]] * n_samp;
+        drow[e] = tod + (int64_t)d_idx[dets[e]] * n_samp;
+        frow[e] = use_dflags ? dflags + (int64_t)f_idx[dets[e]] * n_samp : nullptr;
+        ds[e] = det_scale[dets[e]];
+        wi[e] = cal[dets[e]];
+    }
+    const double * wrow_b = weights + (int64_t)w_idx[dets[1]] * n_samp * 3;
+    const int64_t row = (int64_t)pair_row[blockIdx.x] * n_samp;
+    const int32_t * krow = word + row;
+    const double2 * qrow = qu + row;
+    const float2 * srow = sums + row;
+    const int64_t nps = nps_div.d;
+    const uint16_t dmask2 = (uint16_t)(dmask | (dmask << 8));
+    const uint16_t smask2 = (uint16_t)(smask | (smask << 8));
+    for (int ci = blockIdx.y; ci < n_chunks; ci += gridDim.y) {
+        const Chunk c = chunks[ci];
+        const int head = (int)(c.first & 1);
+        const int64_t s0 = c.first + head;          // even
+        const int n_pair = (c.count - head) >> 1;
+        for (int base = 0; base < n_pair; base += kThreads) {
+            const int j = base + threadIdx.x;
+            const bool active = j < n_pair;
+            const int64_t s = s0 + 2 * (int64_t)(active ? j : 0);
+            int64_t ka[E], kb[E];
+            double va[E][NNZ], vb[E][NNZ];
+            // all streaming loads of both samples of both detectors first (inactive lanes re-read pair 0: same lines)
+            const int2 pw = *reinterpret_cast<const int2 *>(krow + s);
+            const float4 sm = *reinterpret_cast<const float4 *>(srow + s);
+            double2 tt[E], wa[E], wb[E];
+            uint16_t fd[E];
+            const uint16_t fs = use_sflags ? *reinterpret_cast<const uint16_t *>(sflags + s) : (uint16_t)0;
+            wa[0] = qrow[s];
+            wb[0] = qrow[s + 1];
+#pragma unroll
+            for (int e = 0; e < E; ++e) {
+                fd[e] = use_dflags ? *reinterpret_cast<const uint16_t *>(frow[e] + s) : (uint16_t)0;
+                tt[e] = *reinterpret_cast<const double2 *>(drow[e] + s);
+            }
+            // B's weights: from the sums, or (NaN marker) from B's own row
+            wa[1] = make_double2((double)sm.x - wa[0].x, (double)sm.y - wa[0].y);
+            wb[1] = make_double2((double)sm.z - wb[0].x, (double)sm.w - wb[0].y);
+            if (sm.x != sm.x) wa[1].x = wrow_b[3 * s + 1];
+            if (sm.y != sm.y) wa[1].y = wrow_b[3 * s + 2];
+            if (sm.z != sm.z) wb[1].x = wrow_b[3 * s + 4];
+            if (sm.w != sm.w) wb[1].y = wrow_b[3 * s + 5];
+            const bool esc_a = pw.x == kEsc, esc_b = pw.y == kEsc;
+            const bool slow = __any(esc_a | esc_b);
+            int64_t pa[E] = {pw.x, pw.x}, pb[E] = {pw.y, pw.y};
+            if (slow) {
+                if (esc_a) {
+                    pa[0] = prow[0][s];
+                    pa[1] = prow[1][s];
+                }
+                if (esc_b) {
+                    pb[0] = prow[0][s + 1];
+                    pb[1] = prow[1][s + 1];
+                }
+            }
+            // global2local: one look-up per pair-sample, or (a wave with an escape) one per detector-sample
+            int64_t ga[E], gb[E], la[E], lb[E];
+            ga[0] = fastdiv(pa[0] >= 0 ? pa[0] : 0, nps_div);
+            gb[0] = fastdiv(pb[0] >= 0 ? pb[0] : 0, nps_div);
+            la[0] = g2l[ga[0]];
+            lb[0] = g2l[gb[0]];
+            if (slow) {
+                ga[1] = fastdiv(pa[1] >= 0 ? pa[1] : 0, nps_div);
+                gb[1] = fastdiv(pb[1] >= 0 ? pb[1] : 0, nps_div);
+                la[1] = g2l[ga[1]];
+                lb[1] = g2l[gb[1]];
+            } else {
+                ga[1] = ga[0], gb[1] = gb[0], la[1] = la[0], lb[1] = lb[0];
+            }
+#pragma unroll
+            for (int e = 0; e < E; ++e) {
+                const uint16_t bad = (uint16_t)((fd[e] & dmask2) | (fs & smask2));
+                const bool good_a = active & on[e] & (pa[e] >= 0) & (la[e] >= 0) & ((bad & 0x00ff) == 0);
+                const bool good_b = active & on[e] & (pb[e] >= 0) & (lb[e] >= 0) & ((bad & 0xff00) == 0);
+                ka[e] = good_a ? la[e] * nps + (pa[e] - ga[e] * nps) : -1;
+                kb[e] = good_b ? lb[e] * nps + (pb[e] - gb[e] * nps) : -1;
+                const double sa = tt[e].x * ds[e], sb = tt[e].y * ds[e];
+                va[e][0] = good_a ? sa * wi[e] : 0.0;
+                va[e][1] = good_a ? sa * wa[e].x : 0.0;
+                va[e][2] = good_a ? sa * wa[e].y : 0.0;
+                vb[e][0] = good_b ? sb * wi[e] : 0.0;
+                vb[e][1] = good_b ? sb * wb[e].x : 0.0;
+                vb[e][2] = good_b ? sb * wb[e].y : 0.0;
+            }
+            bool merge = !slow;   // (the key is common: nothing to ask)
+            if (slow) {
+                const bool mergeable = ((ka[0] == ka[1]) | (ka[0] < 0) | (ka[1] < 0)) &
+                                       ((kb[0] == kb[1]) | (kb[0] < 0) | (kb[1] < 0));
+                merge = __all(mergeable);
+            }
+            if (merge) {
+                const int64_t kam = (ka[0] >= 0) ? ka[0] : ka[1];
+                const int64_t kbm = (kb[0] >= 0) ? kb[0] : kb[1];
+                double vam[NNZ], vbm[NNZ];
+#pragma unroll
+                for (int k = 0; k < NNZ; ++k) {
+                    vam[k] = va[0][k] + va[1][k];
+                    vbm[k] = vb[0][k] + vb[1][k];
+                }
+                scatter_runs2<NNZ>(kam, vam, kbm, vbm, zmap);
+                continue;
+            }
+#pragma unroll
+            for (int e = 0; e < E; ++e) scatter_runs2<NNZ>(ka[e], va[e], kb[e], vb[e], zmap);
+        }
+        // the peeled first sample (lane 0) and the odd last one (lane 1)
+        const int tail = (c.count - head) & 1;
+        if ((threadIdx.x == 0 && head) || (threadIdx.x == 1 && tail)) {
+            const int64_t s = (threadIdx.x == 0) ? c.first : c.first + c.count - 1;
+            const uint8_t fs = use_sflags ? sflags[s] : (uint8_t)0;
+            const int32_t pw = krow[s];
+            const double2 w_a = qrow[s];
+            const float2 sm = srow[s];
+            for (int e = 0; e < E; ++e) {
+                if (!on[e]) continue;
+                const int64_t p = (pw == kEsc) ? prow[e][s] : (int64_t)pw;
+                const uint8_t fd = use_dflags ? frow[e][s] : (uint8_t)0;
+                if ((p < 0) | ((fd & dmask) != 0) | ((fs & smask) != 0)) continue;
+                const int64_t gsm = fastdiv(p, nps_div);
+                const int64_t key = g2l[gsm] * nps + (p - gsm * nps);
+                if (key < 0) continue;
+                const double sd = drow[e][s] * ds[e];
+                double2 w = w_a;
+                if (e == 1) {
+                    w.x = (sm.x != sm.x) ? wrow_b[3 * s + 1] : (double)sm.x - w_a.x;
+                    w.y = (sm.y != sm.y) ? wrow_b[3 * s + 2] : (double)sm.y - w_a.y;
+                }
                 double * z = zmap + NNZ * key;
                 unsafeAtomicAdd(z, sd * wi[e]);
                 unsafeAtomicAdd(z + 1, sd * w.x);
@@ -2344,6 +2713,12 @@ struct PackedArgs {
     const int32_t * p_row;
     const int32_t * q_row;
     const double * cal;
+    // the pair form (pix == nullptr): one row of the copy per pair (2 b, 2 b + 1) of the call
+    const int32_t * word;
+    const double2 * qu_a;
+    const float2 * sums;
+    const int32_t * pair_row;
+    int n_det;
 };
 
 
@@ -2355,6 +2730,12 @@ void launch_scan_map(dim3 grid, hipStream_t st, const Chunk * ch, int n_ch, cons
                      int64_t n_samp, const PackedArgs * pk = nullptr) {
     const T * m = static_cast<const T *>(map);
     const int dm = det_major_grid() ? 1 : 0;
+    if (pk != nullptr && pk->pix == nullptr) {
+        const dim3 gp((unsigned)((pk->n_det + 1) / 2), grid.y, 1);
+        hipLaunchKernelGGL((k_scan_map_pp<T>), gp, dim3(kThreads), 0, st, ch, n_ch, pk->n_det, di, pi, wi, pk->pair_row, pk->cal,
+                           g2l, m, tod, pk->word, pk->qu_a, pk->sums, pix, w, dv, scale, zero, sub, mult, det_w, n_samp);
+        return;
+    }
     if (pk != nullptr) {
         hipLaunchKernelGGL((k_scan_map_pk<T>), grid, dim3(kThreads), 0, st, ch, n_ch, di, pk->p_row, pk->q_row, pk->cal, g2l, m,
                            tod, pk->pix, pk->qu, dv, scale, zero, sub, mult, det_w, n_samp);
@@ -2561,9 +2942,12 @@ int toast_hip_scan_map_dev(int map_dtype, const int64_t * d_g2l, int64_t n_pix_s
         const size_t o_pr = packed ? pb.push_vec(hit.pix_row) : 0;
         const size_t o_qr = packed ? pb.push_vec(hit.qu_row) : 0;
         const size_t o_cl = packed ? pb.push_vec(hit.cal) : 0;
+        const size_t o_pp = packed && hit.pair ? pb.push_vec(hit.pair_row) : 0;
         const char * d = pb.commit(as_stream(stream));
         const PackedArgs pka = {hit.pix, reinterpret_cast<const double2 *>(hit.qu), (const int32_t *)(d + o_pr),
-                                (const int32_t *)(d + o_qr), (const double *)(d + o_cl)};
+                                (const int32_t *)(d + o_qr), (const double *)(d + o_cl), hit.word,
+                                reinterpret_cast<const double2 *>(hit.qu_a), reinterpret_cast<const float2 *>(hit.sums),
+                                (const int32_t *)(d + o_pp), (int)n_det};
         const PackedArgs * pk = packed ? &pka : nullptr;
         const double * dw = det_weights ? (const double *)(d + o_dw) : nullptr;
         const FastDiv dv = make_fastdiv(n_pix_submap);
@@ -2647,10 +3031,22 @@ int toast_hip_build_noise_weighted_dev(
         const size_t o_pr = packed ? pb.push_vec(hit.pix_row) : 0;
         const size_t o_qr = packed ? pb.push_vec(hit.qu_row) : 0;
         const size_t o_cl = packed ? pb.push_vec(hit.cal) : 0;
+        const size_t o_pp = packed && hit.pair ? pb.push_vec(hit.pair_row) : 0;
         const char * d = pb.commit(as_stream(stream));
         const FastDiv dv = make_fastdiv(n_pix_submap);
         const dim3 grid = chunk_grid(n_det, chunks.size());
         hipStream_t st = as_stream(stream);
+        if (packed && hit.pair) {
+            const dim3 gp((unsigned)((n_det + 1) / 2), grid.y, 1);
+            hipLaunchKernelGGL(k_build_noise_weighted_pp, gp, dim3(kThreads), 0, st, (const Chunk *)(d + o_ch), (int)chunks.size(),
+                               (int)n_det, (const int32_t *)(d + o_pi), (const int32_t *)(d + o_wi), (const int32_t *)(d + o_pp),
+                               (const double *)(d + o_cl), (const int32_t *)(d + o_di), (const int32_t *)(d + o_fi),
+                               (const double *)(d + o_ds), d_g2l, d_zmap, hit.word, reinterpret_cast<const double2 *>(hit.qu_a),
+                               reinterpret_cast<const float2 *>(hit.sums), d_pixels, d_weights, d_det_data, d_det_flags,
+                               det_flag_mask, use_d, d_shared_flags, shared_flag_mask, use_s, dv, n_samp);
+            check_launch();
+            return;
+        }
         if (packed) {
             const bool pr = pair_detectors() && n_det >= 2;
             const dim3 gp((unsigned)(pr ? (n_det + 1) / 2 : n_det), grid.y, 1);
@@ -3884,6 +4280,32 @@ void launch_pointing_pack(int kind, const void * src, void * dst, const int32_t 
         hipLaunchKernelGGL(k_pack_qu, grid, dim3(kThreads), 0, st, static_cast<const double *>(src),
                            static_cast<double2 *>(dst), (const int32_t *)(d + o_r), n_samp);
     }
+    check_launch();
+}
+
+void launch_pointing_pack_pairs(const int64_t * pixels, const double * weights, const int32_t * rows, int n_pairs,
+                                int64_t n_samp, const int64_t * ivl, int n_view, int64_t s_begin, int64_t s_end, void * dst,
+                                unsigned long long * d_escaped, hipStream_t st) {
+    if (s_begin < 0) s_begin = 0;
+    if (s_end > n_samp) s_end = n_samp;
+    if (n_pairs <= 0 || s_end <= s_begin) return;
+    if (n_pairs > pointing_cache::kMaxSealedRows) fail_arg("pointing cache: more pairs than one grid dimension holds");
+    ParamBlock pb;
+    const size_t o_r = pb.push(rows, sizeof(int32_t) * 4 * (size_t)n_pairs);
+    const size_t o_v = pb.push(ivl, sizeof(int64_t) * 2 * (size_t)(n_view > 0 ? n_view : 0));
+    const char * d = pb.commit(st);
+    int sorted = 1;
+    for (int v = 0; v < n_view; ++v) {
+        if (ivl[2 * v] > ivl[2 * v + 1] || (v + 1 < n_view && ivl[2 * v + 1] > ivl[2 * v + 2])) sorted = 0;
+    }
+    int64_t gx = (s_end - s_begin + kThreads - 1) / kThreads;
+    if (gx > 256) gx = 256;
+    using L = pointing_cache::PairLayout;
+    hipLaunchKernelGGL(k_pack_pairs_pp, dim3((unsigned)gx, (unsigned)n_pairs, 1), dim3(kThreads), 0, st, pixels, weights,
+                       (const int32_t *)(d + o_r), (const int64_t *)(d + o_v), n_view, sorted, s_begin, s_end, n_samp,
+                       dst ? const_cast<int32_t *>(L::word(dst, n_pairs, n_samp)) : nullptr,
+                       dst ? reinterpret_cast<double2 *>(const_cast<double *>(L::qu(dst, n_pairs, n_samp))) : nullptr,
+                       dst ? reinterpret_cast<float2 *>(const_cast<float *>(L::sums(dst, n_pairs, n_samp))) : nullptr, d_escaped);
     check_launch();
 }
 

@@ -129,8 +129,33 @@ void Registry::reap(bool wait) {
     settle(again, wait);
 }
 
+Registry::PairCopy * Registry::pair_of(uint64_t pix_id, uint64_t wts_id) {
+    for (PairCopy & pc : pair_copies_) {
+        if (pc.pix_id == pix_id && pc.wts_id == wts_id) return &pc;
+    }
+    return nullptr;
+}
+
+// a pair copy goes with EITHER of its two seals; the seal that stays counts its calls from zero, as after an eviction
+void Registry::release_pair_copy(size_t k, Parting & parting) {
+    PairCopy & pc = pair_copies_[k];
+    if (Seal * sp = by_id(pc.pix_id)) sp->calls = 0;
+    if (Seal * sw = by_id(pc.wts_id)) sw->calls = 0;
+    st_.packed_bytes -= pc.bytes;
+    parting.emplace_back(pc.block, pc.stream);
+    if (k + 1 != pair_copies_.size()) pair_copies_[k] = std::move(pair_copies_.back());
+    pair_copies_.pop_back();
+}
+
+void Registry::drop_pair_copies_of(uint64_t seal_id, Parting & parting) {
+    for (size_t k = pair_copies_.size(); k-- > 0;) {
+        if (pair_copies_[k].pix_id == seal_id || pair_copies_[k].wts_id == seal_id) release_pair_copy(k, parting);
+    }
+}
+
 void Registry::drop_at(size_t i, DropReason why, Parting & parting) {
     Seal & s = seals_[i];
+    drop_pair_copies_of(s.id, parting);
     if (s.packed != nullptr) {
         st_.packed_bytes -= s.packed_bytes;
         parting.emplace_back(s.packed, s.stream);
@@ -210,6 +235,7 @@ Stats Registry::stats() {
     Lock lock(*this);
     Stats s = st_;
     s.live_seals = (int64_t)seals_.size();
+    for (const PairCopy & pc : pair_copies_) s.pair_escapes += pc.escapes;
     return s;
 }
 
@@ -230,6 +256,13 @@ size_t Registry::evict(bool (*wanted)(const void *)) {
             s.packed_bytes = 0;
             s.calls = 0;
             ++st_.evictions;
+        }
+        for (size_t k = pair_copies_.size(); k-- > 0;) {
+            PairCopy & pc = pair_copies_[k];
+            if (wanted != nullptr && !wanted(pc.block)) continue;
+            bytes += pc.bytes;
+            ++st_.evictions;
+            release_pair_copy(k, parting);   // (both seals stay and count from zero)
         }
     }
     settle(parting, true);   // the allocation that asked is waiting for this room
@@ -313,6 +346,10 @@ bool Registry::consume(int device, void * stream, const void * pixels, const int
         size_t bytes = 0;
         void * block = nullptr;
     } job[2];
+    // ... and what the pair form needs: the call's detectors in twos, the interval list, the arrays
+    std::vector<int32_t> pair_rows;
+    std::vector<int64_t> view;
+    bool try_pair = false;
     {
         Lock lock(*this);
         auto miss = [&] {
@@ -341,6 +378,13 @@ bool Registry::consume(int device, void * stream, const void * pixels, const int
         // an eligible call
         ++sp->calls;
         ++sw->calls;
+        if (const PairCopy * pc = pair_of(sp->id, sw->id)) {
+            // the pair form is all there is of these two seals: a call that does not take its detectors in the recorded
+            // pairs computes from the caller's arrays
+            if (!pair_hit(*pc, pixel_index, weight_index, n_det, out)) return miss();
+            ++st_.hits;
+            return true;
+        }
         if (sp->packed != nullptr && sw->packed != nullptr) {
             out->pix = static_cast<const int32_t *>(sp->packed);
             out->qu = static_cast<const double *>(sw->packed);
@@ -362,28 +406,97 @@ bool Registry::consume(int device, void * stream, const void * pixels, const int
             job[1].rows = sw->rows;
             job[1].bytes = sw->rows.size() * (size_t)n_samp * 16;
         }
+        // The pair form is all or nothing: tried when neither array has a copy yet, the call has a pair to offer and names
+        // no row twice.  Its pairs are detectors (2 b, 2 b + 1) of THIS call; a lone last detector is a pair without a B.
+        try_pair = be_.pack_pairs != nullptr && n_det >= 2 && sp->packed == nullptr && sw->packed == nullptr && n_view > 0;
+        if (try_pair) {
+            std::vector<int32_t> seen_p(pixel_index, pixel_index + n_det), seen_w(weight_index, weight_index + n_det);
+            std::sort(seen_p.begin(), seen_p.end());
+            std::sort(seen_w.begin(), seen_w.end());
+            try_pair = std::adjacent_find(seen_p.begin(), seen_p.end()) == seen_p.end() &&
+                       std::adjacent_find(seen_w.begin(), seen_w.end()) == seen_w.end();
+        }
+        if (try_pair) {
+            for (int64_t d = 0; d < n_det; d += 2) {
+                const bool lone = d + 1 >= n_det;
+                pair_rows.push_back(pixel_index[d]);
+                pair_rows.push_back(lone ? -1 : pixel_index[d + 1]);
+                pair_rows.push_back(weight_index[d]);
+                pair_rows.push_back(lone ? -1 : weight_index[d + 1]);
+            }
+            view = sp->ivl;
+        }
     }
     // ---- the pack, without the lock: taking the blocks and launching the kernels goes through the arena and the
     // parameter-block cache, both of which may come back here (freed, evict)
     reap(false);
-    bool room = true;
-    for (Job & j : job) {
-        if (j.bytes == 0) continue;
-        j.block = be_.take(j.bytes, stream);
-        room = room && j.block != nullptr;
-    }
-    bool launched = false;
-    if (room) {
+    // -- the pair form first.  A probe over the head of the first interval keeps a focal plane without co-pointing pairs
+    // (or with pairs of different calibration) from paying a wasted sweep; then the sweep itself, whose escape count --
+    // read back from the device, which blocks on the stream once per sealing -- decides.  More than one pair-sample in a
+    // hundred escaped: the block goes back and the plain form is packed in this same call.
+    PairCopy made;
+    bool demoted = false;
+    if (try_pair) {
+        const int64_t n_pairs = (int64_t)pair_rows.size() / 4;
+        // the threshold's denominator: the pair-samples in view of EVERY row of the copy, a lone detector's included
         try {
-            for (int k = 0; k < 2; ++k) {
-                if (job[k].bytes != 0) {
-                    be_.pack(k == 0 ? kPixels : kWeights, job[k].base, job[k].block, job[k].rows.data(), (int)job[k].rows.size(),
-                             n_samp, stream);
+            const int64_t p0 = view[0], p1 = std::min(view[1], view[0] + kPairProbeSamples);
+            int64_t esc = p1 > p0 ? be_.pack_pairs(pixels, weights, pair_rows.data(), (int)n_pairs, n_samp, view.data(),
+                                                   (int)n_view, p0, p1, nullptr, stream)
+                                  : 0;
+            if (esc >= 0 && esc * 100 > (p1 - p0) * n_pairs) {
+                demoted = true;
+            } else if (esc >= 0) {
+                const size_t bytes = PairLayout::bytes(n_pairs, n_samp);
+                void * block = be_.take(bytes, stream);
+                if (block != nullptr) {
+                    int64_t in_view = 0;
+                    for (int64_t v = 0; v < n_view; ++v) in_view += std::max<int64_t>(view[2 * v + 1] - view[2 * v], 0);
+                    try {
+                        esc = be_.pack_pairs(pixels, weights, pair_rows.data(), (int)n_pairs, n_samp, view.data(), (int)n_view, 0,
+                                             n_samp, block, stream);
+                    } catch (...) {
+                        esc = -1;
+                    }
+                    if (esc >= 0 && esc * 100 <= in_view * n_pairs) {
+                        made.block = block;
+                        made.bytes = bytes;
+                        made.stream = stream;
+                        made.n_pairs = n_pairs;
+                        made.n_samp = n_samp;
+                        made.escapes = esc;
+                    } else {
+                        demoted = esc >= 0;
+                        Parting back;
+                        n_blocks_.fetch_add(1, std::memory_order_relaxed);
+                        back.emplace_back(block, stream);
+                        settle(back, false);   // (before the plain form asks for its room)
+                    }
                 }
             }
-            launched = true;
         } catch (...) {
-            launched = false;
+        }
+    }
+    bool room = true;
+    bool launched = false;
+    if (made.block == nullptr) {
+        for (Job & j : job) {
+            if (j.bytes == 0) continue;
+            j.block = be_.take(j.bytes, stream);
+            room = room && j.block != nullptr;
+        }
+        if (room) {
+            try {
+                for (int k = 0; k < 2; ++k) {
+                    if (job[k].bytes != 0) {
+                        be_.pack(k == 0 ? kPixels : kWeights, job[k].base, job[k].block, job[k].rows.data(),
+                                 (int)job[k].rows.size(), n_samp, stream);
+                    }
+                }
+                launched = true;
+            } catch (...) {
+                launched = false;
+            }
         }
     }
     // ---- publish, if the seals are still the ones the copies were made from
@@ -395,8 +508,23 @@ bool Registry::consume(int device, void * stream, const void * pixels, const int
         Seal * sw = by_id(job[1].id);
         if (sp != nullptr) sp->packing = false;
         if (sw != nullptr) sw->packing = false;
-        if (launched && sp != nullptr && sw != nullptr && (job[0].bytes == 0) == (sp->packed != nullptr) &&
-            (job[1].bytes == 0) == (sw->packed != nullptr)) {
+        const bool same = sp != nullptr && sw != nullptr && (job[0].bytes == 0) == (sp->packed != nullptr) &&
+                          (job[1].bytes == 0) == (sw->packed != nullptr);
+        if (made.block != nullptr && same) {
+            made.pix_id = sp->id;
+            made.wts_id = sw->id;
+            made.rows = std::move(pair_rows);
+            for (int64_t k = 0; k < made.n_pairs; ++k) made.by_pixel_a.emplace_back(made.rows[(size_t)(4 * k)], (int32_t)k);
+            std::sort(made.by_pixel_a.begin(), made.by_pixel_a.end());
+            st_.packed_bytes += made.bytes;
+            n_blocks_.fetch_add(1, std::memory_order_relaxed);
+            pair_copies_.push_back(std::move(made));
+            made.block = nullptr;
+            hit = pair_hit(pair_copies_.back(), pixel_index, weight_index, n_det, out);
+            ++st_.packs;
+            ++st_.pair_packs;
+            ++st_.hits;
+        } else if (made.block == nullptr && launched && same) {
             Seal * both[2] = {sp, sw};
             for (int k = 0; k < 2; ++k) {
                 if (job[k].bytes == 0) continue;
@@ -409,6 +537,7 @@ bool Registry::consume(int device, void * stream, const void * pixels, const int
             out->pix = static_cast<const int32_t *>(sp->packed);
             out->qu = static_cast<const double *>(sw->packed);
             ++st_.packs;
+            if (demoted) ++st_.pair_demotions;   // (the pair form was tried and the plain one TAKEN)
             ++st_.hits;
             hit = true;
         } else {
@@ -424,9 +553,36 @@ bool Registry::consume(int device, void * stream, const void * pixels, const int
                 parting.emplace_back(j.block, stream);
             }
         }
+        if (made.block != nullptr) {
+            n_blocks_.fetch_add(1, std::memory_order_relaxed);
+            parting.emplace_back(made.block, stream);
+        }
     }
     settle(parting, false);
     return hit;
+}
+
+// The hit rule of the pair form: the call's detectors, taken in twos, are recorded pairs in the same A / B orientation
+// (any subset of the pairs, in any order); a lone last detector is the recorded lone.
+bool Registry::pair_hit(const PairCopy & pc, const int32_t * pixel_index, const int32_t * weight_index, int64_t n_det,
+                        Hit * out) const {
+    out->pair_row.clear();
+    for (int64_t d = 0; d < n_det; d += 2) {
+        const bool lone = d + 1 >= n_det;
+        const auto it = std::lower_bound(pc.by_pixel_a.begin(), pc.by_pixel_a.end(), std::make_pair(pixel_index[d], (int32_t)0));
+        if (it == pc.by_pixel_a.end() || it->first != pixel_index[d]) return false;
+        const int32_t * r = pc.rows.data() + 4 * (size_t)it->second;
+        if (r[2] != weight_index[d]) return false;
+        if (lone ? (r[1] != -1 || r[3] != -1) : (r[1] != pixel_index[d + 1] || r[3] != weight_index[d + 1])) return false;
+        out->pair_row.push_back(it->second);
+    }
+    out->pair = true;
+    out->pix = nullptr;
+    out->qu = nullptr;
+    out->qu_a = PairLayout::qu(pc.block, pc.n_pairs, pc.n_samp);
+    out->sums = PairLayout::sums(pc.block, pc.n_pairs, pc.n_samp);
+    out->word = PairLayout::word(pc.block, pc.n_pairs, pc.n_samp);
+    return true;
 }
 
 // ------------------------------------------------------------------------------------------------ selftest
@@ -466,6 +622,7 @@ std::mutex g_selftest_mutex;     // one selftest at a time: the backend's functi
 HostArena * g_arena = nullptr;
 bool g_may_cache = true;
 bool g_lazy_give = false;        // give(wait = false) says "not yet" the first time it is asked for a block
+bool g_pair_form = true;         // false: the stand-in's pack_pairs says "not to be had" (TOAST_HIP_PAIR=0)
 std::vector<void *> g_asked;     // ... the blocks it was asked for once
 // Every backend function reports here.  The device backend's pack goes through the parameter-block cache and the arena and
 // can come back into the registry (freed, evict), and so can take and give: the stand-in does exactly that from pack --
@@ -509,6 +666,52 @@ const Backend & host_backend() {
             }
         },
         [](void *) { return g_may_cache; },
+        // the pair pack on host memory: k_pack_pairs_pp's arithmetic (kernels.hip), the count "read back" at once.  The probe
+        // (dst = nullptr) reports like take / give, the sweep like pack: it comes back into the registry under pressure.
+        [](const void * pixels, const void * weights, const int32_t * rows, int n_pairs, int64_t n_samp, const int64_t * ivl,
+           int n_view, int64_t s_begin, int64_t s_end, void * dst, void *) -> int64_t {
+            backend_called(dst != nullptr);
+            if (!g_pair_form) return -1;
+            const int64_t * pix = static_cast<const int64_t *>(pixels);
+            const double * wts = static_cast<const double *>(weights);
+            double * qu = dst ? const_cast<double *>(PairLayout::qu(dst, n_pairs, n_samp)) : nullptr;
+            float * sums = dst ? const_cast<float *>(PairLayout::sums(dst, n_pairs, n_samp)) : nullptr;
+            int32_t * word = dst ? const_cast<int32_t *>(PairLayout::word(dst, n_pairs, n_samp)) : nullptr;
+            auto sum_or_marker = [](double a, double b) {
+                const double d = a + b;
+                const float f = (float)d;
+                return ((double)f == d && (double)f - a == b) ? f : __builtin_nanf("");
+            };
+            int64_t escaped = 0;
+            for (int k = 0; k < n_pairs; ++k) {
+                const int32_t * r = rows + 4 * k;
+                const bool lone = r[1] < 0;
+                for (int64_t i = s_begin; i < s_end; ++i) {
+                    const int64_t pa = pix[(int64_t)r[0] * n_samp + i];
+                    const int64_t pb = lone ? pa : pix[(int64_t)r[1] * n_samp + i];
+                    const double * wa = wts + 3 * ((int64_t)r[2] * n_samp + i);
+                    float fq = 0.0f, fu = 0.0f;
+                    if (!lone && !(pa < 0 && pb < 0)) {   // (no pixel in either: the weights are never used)
+                        const double * wb = wts + 3 * ((int64_t)r[3] * n_samp + i);
+                        fq = sum_or_marker(wa[1], wb[1]);
+                        fu = sum_or_marker(wa[2], wb[2]);
+                    }
+                    const int32_t w = pa == pb ? (int32_t)pa : kPairEscape;
+                    bool in_view = false;
+                    for (int v = 0; v < n_view; ++v) in_view = in_view || (i >= ivl[2 * v] && i < ivl[2 * v + 1]);
+                    if (in_view && (w == kPairEscape || fq != fq || fu != fu)) ++escaped;
+                    if (dst != nullptr) {
+                        const int64_t at = (int64_t)k * n_samp + i;
+                        word[at] = w;
+                        qu[2 * at] = wa[1];
+                        qu[2 * at + 1] = wa[2];
+                        sums[2 * at] = fq;
+                        sums[2 * at + 1] = fu;
+                    }
+                }
+            }
+            return escaped;
+        },
     };
     return be;
 }
@@ -533,6 +736,7 @@ struct ModelPair {
     int ivl_p = -1, ivl_w = -1;                  // interval list each was expanded with
     int eligible = 0;                            // consumer calls that could have hit since both were expanded
     std::vector<double> cal;
+    std::vector<int32_t> pair_dets;              // the detector list of the call that packed the pair form (empty: none live)
 };
 
 constexpr int kRows = 4;
@@ -552,6 +756,10 @@ struct Harness {
     size_t pack_pressure = 0;     // bytes that the backend's pack allocates and releases through the harness (0: none)
     int64_t pack_reentries = 0;
     bool lock_violation = false;
+    // what the expansions write: rows (0, 1) and (2, 3) as co-pointing pairs (same pixel, same cal, opposite Q / U), with
+    // B's pixel moved away in every sample from pair_escape_from on
+    bool paired = false;
+    int64_t pair_escape_from = kSamp;
 
     void from_backend(bool from_pack) {
         if (reg.locked_here()) {
@@ -570,6 +778,7 @@ struct Harness {
         g_arena = &arena;
         g_may_cache = true;
         g_lazy_give = false;
+        g_pair_form = true;
         g_asked.clear();
         g_harness = this;
         ivls[0][0] = {0.0, 0.0, 1, 21};
@@ -605,6 +814,15 @@ struct Harness {
     void expand_pixels(ModelPair & m, int iv) {
         const int32_t rows[kRows] = {2, 0, 3, 1};
         for (int64_t i = 0; i < kRows * kSamp; ++i) m.pix[i] = (rng.below(8) == 0) ? -1 : (int64_t)rng.below(1 << 20);
+        if (paired) {
+            for (int k = 1; k < kRows; k += 2) {
+                for (int64_t i = 0; i < kSamp; ++i) {
+                    const int64_t a = m.pix[(k - 1) * kSamp + i];
+                    m.pix[k * kSamp + i] = i < pair_escape_from ? a : a + 1;
+                }
+            }
+        }
+        m.pair_dets.clear();
         reg.seal(kPixels, 0, nullptr, m.pix, kSamp, rows, kRows, ivls[iv], 2, 64, nullptr);
         m.pix_clean = g_may_cache && reg.enabled();
         m.ivl_p = iv;
@@ -618,14 +836,22 @@ struct Harness {
             cal[k] = 1.0 + 0.001 * rng.below(1000);
             m.cal[(size_t)rows[k]] = cal[k];
         }
+        if (paired) {   // (rows[k] and cal[k] go together: the pair's cal is its even row's)
+            for (int k = 0; k < kRows; ++k) cal[k] = m.cal[(size_t)rows[k]] = m.cal[(size_t)(rows[k] & ~1)];
+        }
         for (int k = 0; k < kRows; ++k) {
             for (int64_t i = 0; i < kSamp; ++i) {
                 double * w = m.wts + 3 * (k * kSamp + i);
                 w[0] = m.cal[(size_t)k];
                 w[1] = rng.below(1000) * 0.001;
                 w[2] = rng.below(1000) * -0.002;
+                if (paired && (k & 1) != 0) {
+                    w[1] = -w[1 - 3 * kSamp];
+                    w[2] = -w[2 - 3 * kSamp];
+                }
             }
         }
+        m.pair_dets.clear();
         reg.seal(kWeights, 0, nullptr, m.wts, kSamp, rows, kRows, ivls[iv], 2, 0, cal);
         m.wts_clean = g_may_cache && reg.enabled();
         m.ivl_w = iv;
@@ -634,7 +860,9 @@ struct Harness {
     // a consumer call over detectors (rows) dets with interval list iv; false = the registry broke its contract
     bool consume(ModelPair & m, int iv, const std::vector<int32_t> & dets) {
         Hit h;
+        const int64_t pair_packs = reg.stats().pair_packs;
         const bool hit = reg.consume(0, nullptr, m.pix, dets.data(), m.wts, dets.data(), (int64_t)dets.size(), kSamp, ivls[iv], 2, &h);
+        if (reg.stats().pair_packs != pair_packs) m.pair_dets = dets;   // this call packed the pair form: its twos are the pairs
         const bool allowed = m.pix_clean && m.wts_clean && m.ivl_p == iv && m.ivl_w == iv && g_may_cache && reg.enabled();
         if (allowed) ++m.eligible;
         if (!hit) return true;
@@ -647,6 +875,7 @@ struct Harness {
             err << "a hit on eligible call " << m.eligible << " since sealing (packing is due on call " << kPackAfterCalls << ")";
             return false;
         }
+        if (h.pair) return pair_hit_sound(m, iv, dets, h);
         // the packed copy holds what the arrays hold, inside the intervals
         for (size_t d = 0; d < dets.size(); ++d) {
             if (h.cal[d] != m.cal[(size_t)dets[d]]) {
@@ -660,6 +889,53 @@ struct Harness {
                     if ((int64_t)h.pix[(int64_t)h.pix_row[d] * kSamp + i] != m.pix[src] || q[0] != m.wts[3 * src + 1] ||
                         q[1] != m.wts[3 * src + 2] || h.cal[d] != m.wts[3 * src]) {
                         err << "the packed copy differs from the arrays at detector " << d << " sample " << i;
+                        return false;
+                    }
+                }
+            }
+        }
+        return true;
+    }
+    // A hit on the pair form.  The rule: the call's detectors in twos are pairs of the call that packed, in the same
+    // orientation; a lone last detector is that call's lone.  The content: what the consumer kernels reconstruct from the
+    // copy -- or read from the arrays where it says "escape" -- is what the arrays hold, inside the intervals.
+    bool pair_hit_sound(const ModelPair & m, int iv, const std::vector<int32_t> & dets, const Hit & h) {
+        if (h.pair_row.size() != (dets.size() + 1) / 2 || h.cal.size() != dets.size()) {
+            err << "a pair hit without a row per pair";
+            return false;
+        }
+        for (size_t d = 0; d < dets.size(); d += 2) {
+            const bool lone = d + 1 >= dets.size();
+            bool recorded = false;
+            for (size_t r = 0; r < m.pair_dets.size() && !recorded; r += 2) {
+                const bool r_lone = r + 1 >= m.pair_dets.size();
+                recorded = m.pair_dets[r] == dets[d] && lone == r_lone && (lone || m.pair_dets[r + 1] == dets[d + 1]) &&
+                           h.pair_row[d / 2] == (int32_t)(r / 2);
+            }
+            if (!recorded) {
+                err << "a pair hit for detectors that are not a pair of the call that packed (position " << d << ")";
+                return false;
+            }
+            const int64_t row = h.pair_row[d / 2];
+            for (size_t e = 0; e < (lone ? 1u : 2u); ++e) {
+                if (h.cal[d + e] != m.cal[(size_t)dets[d + e]]) {
+                    err << "wrong cal for detector " << d + e;
+                    return false;
+                }
+            }
+            for (int v = 0; v < 2; ++v) {
+                for (int64_t i = ivls[iv][v].first; i < ivls[iv][v].last; ++i) {
+                    const int64_t a = (int64_t)dets[d] * kSamp + i, at = row * kSamp + i;
+                    const int64_t b = lone ? a : (int64_t)dets[d + 1] * kSamp + i;
+                    const int32_t w = h.word[at];
+                    bool ok = w == kPairEscape ? m.pix[a] != m.pix[b] : ((int64_t)w == m.pix[a] && (int64_t)w == m.pix[b]);
+                    ok = ok && h.qu_a[2 * at] == m.wts[3 * a + 1] && h.qu_a[2 * at + 1] == m.wts[3 * a + 2];
+                    for (int c = 0; c < 2 && ok && !lone && !(m.pix[a] < 0 && m.pix[b] < 0); ++c) {
+                        const float f = h.sums[2 * at + c];
+                        ok = f != f || (double)f - h.qu_a[2 * at + c] == m.wts[3 * b + 1 + c];
+                    }
+                    if (!ok) {
+                        err << "the pair copy does not give back the arrays at detectors " << d << ", " << d + 1 << " sample " << i;
                         return false;
                     }
                 }
@@ -694,23 +970,29 @@ void backend_called(bool from_pack) {
 std::string random_sequence(uint64_t seed, int n_ops) {
     // room for three pairs and the packed copies of about two of them: packing, eviction and "no room" all occur
     Harness h(seed, 3 * kRows * kSamp * 32 + 2 * kRows * kSamp * 20 + 512);
-    const std::vector<int32_t> all = {0, 1, 2, 3}, some = {3, 1};
+    const std::vector<int32_t> all = {0, 1, 2, 3}, some = {3, 1}, swapped = {2, 3, 0, 1}, split = {1, 2}, three = {0, 1, 2};
     g_lazy_give = true;
     for (int op = 0; op < n_ops && h.err.str().empty() && !h.lock_violation; ++op) {
         const int what = h.rng.below(100);
-        // every other pack allocates under pressure and releases, from inside the backend
-        h.pack_pressure = h.rng.below(2) == 0 ? 0 : 2 * kRows * kSamp * 20;
+        // three packs in four allocate under pressure and release, from inside the backend
+        h.pack_pressure = h.rng.below(4) == 0 ? 0 : 2 * kRows * kSamp * 20;
         if (h.pairs.empty() || what < 4) {
             if (h.pairs.size() < 3) h.add_pair();
             continue;
         }
         ModelPair & m = h.pairs[(size_t)h.rng.below((int)h.pairs.size())];
+        // two expansions in three write co-pointing pairs (the pair form needs both arrays that way), one in eight of those
+        // with escapes over the threshold behind the probe's reach
+        h.paired = h.rng.below(3) != 0;
+        h.pair_escape_from = h.rng.below(8) == 0 ? 40 : kSamp;
         if (what < 12) {
             h.expand_pixels(m, h.rng.below(4) == 0 ? 1 : 0);
         } else if (what < 20) {
             h.expand_weights(m, h.rng.below(4) == 0 ? 1 : 0);
         } else if (what < 70) {
-            if (!h.consume(m, h.rng.below(8) == 0 ? 1 : 0, h.rng.below(3) == 0 ? some : all)) break;
+            const int which = h.rng.below(12);
+            const std::vector<int32_t> & dets = which < 6 ? all : which < 8 ? some : which < 10 ? swapped : which < 11 ? split : three;
+            if (!h.consume(m, h.rng.below(8) == 0 ? 1 : 0, dets)) break;
         } else if (what < 75) {
             // a whitelisted call writes over rows of one of the arrays (a scan_map whose det_data lies there)
             const int32_t rows[2] = {(int32_t)h.rng.below(kRows), (int32_t)h.rng.below(kRows)};
@@ -760,8 +1042,13 @@ std::string random_sequence(uint64_t seed, int n_ops) {
         }
     }
     const int64_t hits = h.hits, reentries = h.pack_reentries;
+    const Stats st = h.reg.stats();
     std::string e = h.finish();
     if (e.empty() && n_ops >= 2000 && hits == 0) e = "no hit in the whole sequence";
+    // (a pack every few hundred steps: a long sequence takes both forms)
+    if (e.empty() && n_ops >= 20000 && st.pair_packs == 0) e = "the pair form was never taken";
+    if (e.empty() && n_ops >= 20000 && st.pair_demotions == 0) e = "the pair form was never demoted";
+    if (e.empty() && n_ops >= 20000 && st.packs == st.pair_packs) e = "the plain form was never taken";
     if (e.empty() && n_ops >= 2000 && reentries == 0) e = "the backend's pack never came back into the registry";
     return e;
 }
@@ -882,6 +1169,84 @@ std::string scenario(int which) {
             h.pack_pressure = 0;
             calls(1);
             if (h.reg.stats().hits != 2) fail("a hit on an evicted copy");
+            break;
+        }
+        case 8: {   // co-pointing pairs: the pair form is chosen and hit; one escape in 102 pair-samples stays within the threshold
+            h.paired = true;
+            h.expand_pixels(m, 0);
+            h.expand_weights(m, 0);
+            m.pix[3 * kSamp + 40] += 1;   // (before the first consumer call: the model's arrays ARE what was sealed)
+            calls(2);
+            if (h.reg.stats().packs != 0 || h.reg.stats().hits != 0) fail("packed before the third call");
+            calls(1);
+            Stats a = h.reg.stats();
+            if (a.packs != 1 || a.pair_packs != 1 || a.hits != 1 || a.pair_demotions != 0) fail("the third call did not take the pair form and hit");
+            if (a.packed_bytes != (uint64_t)(kRows / 2) * kSamp * kPairBytes) fail("the pair copy is not 28 B per pair-sample");
+            if (a.pair_escapes != 1) fail("the one escaped pair-sample was not counted");
+            calls(3);
+            a = h.reg.stats();
+            if (a.packs != 1 || a.hits != 4) fail("later calls did not hit the one pair copy");
+            // a reseal of the weights alone gives the pair copy up: it belongs to both seals
+            h.expand_weights(m, 0);
+            if (h.reg.stats().packed_bytes != 0 || h.reg.stats().pair_escapes != 0) fail("the pair copy outlived the weight seal");
+            calls(3);
+            a = h.reg.stats();
+            if (a.pair_packs != 2 || a.hits != 5) fail("the pair form was not packed again on the third call after the reseal");
+            // TOAST_HIP_PAIR=0: the plain form
+            g_pair_form = false;
+            h.expand_pixels(m, 0);
+            calls(3);
+            a = h.reg.stats();
+            if (a.pair_packs != 2 || a.packs != 3 || a.pair_demotions != 0 || a.packed_bytes != (uint64_t)kRows * kSamp * 20) {
+                fail("with the pair form switched off the plain form was not taken");
+            }
+            g_pair_form = true;
+            break;
+        }
+        case 9: {   // escapes over the threshold, out of the probe's reach: demoted to the plain form in the same call
+            h.paired = true;
+            h.pair_escape_from = 30;   // (all of the second interval, none of the first)
+            h.expand_pixels(m, 0);
+            h.expand_weights(m, 0);
+            calls(2);
+            const size_t live = h.arena.live.size();
+            calls(1);
+            const Stats a = h.reg.stats();
+            if (a.pair_demotions != 1 || a.pair_packs != 0) fail("the pair form was not demoted");
+            if (a.packs != 1 || a.hits != 1 || a.packed_bytes != (uint64_t)kRows * kSamp * 20) fail("the plain form was not packed in the same call");
+            if (h.arena.live.size() != live + 2) fail("the demoted pair block was not given back");
+            calls(2);
+            if (h.reg.stats().hits != 3 || h.reg.stats().packs != 1) fail("later calls did not hit the plain copy");
+            break;
+        }
+        case 10: {   // the hit rule of the pair form
+            h.paired = true;
+            h.expand_pixels(m, 0);
+            h.expand_weights(m, 0);
+            calls(3);
+            if (h.reg.stats().pair_packs != 1) fail("the pair form was not taken");
+            auto one = [&](std::vector<int32_t> dets, bool want, const char * what) {
+                const int64_t hits = h.reg.stats().hits, misses = h.reg.stats().misses;
+                if (!h.consume(m, 0, dets)) return;
+                const Stats b = h.reg.stats();
+                if (b.hits != hits + (want ? 1 : 0) || b.misses != misses + (want ? 0 : 1)) fail(what);
+            };
+            one({1, 2}, false, "a call that splits two pairs hit");
+            one({2, 3, 0, 1}, true, "the pairs in another order missed");
+            one({2, 3}, true, "a subset of the pairs missed");
+            one({1, 0}, false, "a pair in the other orientation hit");
+            one({0, 1, 2}, false, "a lone detector that was packed as the A of a pair hit");
+            if (h.reg.stats().packs != 1 || h.reg.stats().packed_bytes != (uint64_t)(kRows / 2) * kSamp * kPairBytes) {
+                fail("a miss on the pair form packed something");
+            }
+            // ... and with a lone last detector in the call that packs
+            h.expand_pixels(m, 0);
+            for (int i = 0; i < 3; ++i) one({2, 3, 0}, i == 2, "the third call with a lone detector did not pack and hit");
+            if (h.reg.stats().pair_packs != 2) fail("the pair form with a lone detector was not taken");
+            one({0}, true, "the recorded lone missed");
+            one({0, 2, 3}, false, "the recorded lone as the A of a pair hit");
+            one({2, 3, 1}, false, "a lone detector that was not recorded hit");
+            one({2, 3, 0}, true, "the packing call's own list missed");
             break;
         }
         default:

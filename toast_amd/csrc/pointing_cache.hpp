@@ -60,6 +60,33 @@ struct Backend {
     void (*pack)(int kind, const void * src, void * dst, const int32_t * rows, int n_rows, int64_t n_samp, void * stream);
     // false: this stream must not seal, pack or hit now (deterministic mode, stream capture)
     bool (*may_cache)(void * stream);
+    // The pair form (PairLayout below): row k of the copy = detectors rows[4 k .. 4 k + 3] = (pixel row A, pixel row B,
+    // weight row A, weight row B; B = -1: a lone detector) of the caller's arrays, samples [s_begin, s_end).  dst =
+    // nullptr: nothing is written.  Returns, READ BACK from the device (blocks on `stream`; like pack it is never called
+    // with the registry's lock held), the number of pair-samples of [s_begin, s_end) inside ivl (first, last, first,
+    // ...) that the pair form cannot express -- the two pixels differ, or a weight sum is not exact -- or -1 when the
+    // pair form is not to be had (TOAST_HIP_PAIR=0).  May be nullptr: no pair form.  The registry calls it twice per
+    // pair pack -- the probe, then the sweep -- so a packing call blocks twice.  The count is held against the
+    // pair-samples in view of ALL n_pairs rows (a lone detector's row never escapes and counts): escapes x 100 <= that.
+    int64_t (*pack_pairs)(const void * pixels, const void * weights, const int32_t * rows, int n_pairs, int64_t n_samp,
+                          const int64_t * ivl, int n_view, int64_t s_begin, int64_t s_end, void * dst, void * stream);
+};
+
+// The pair form of the packed copy: per pair of co-pointing detectors and sample one int32 word (the common global pixel,
+// -1 kept, kPairEscape where the two differ), double2 (q_a, u_a) and float2 (q_a + q_b, u_a + u_b), NaN where the sum is
+// not exact -- 28 B per pair-sample in ONE block: [n_pairs][n_samp] double2, then float2, then int32.
+constexpr int32_t kPairEscape = INT32_MIN;       // (no pixel: 12 nside^2 <= 2^31 - 1 ... and -1 are all there is)
+constexpr size_t kPairBytes = 28;
+constexpr int64_t kPairProbeSamples = 256;       // the probe in front of the pair pack: this many samples of the first interval
+struct PairLayout {
+    static size_t bytes(int64_t n_pairs, int64_t n_samp) { return (size_t)n_pairs * (size_t)n_samp * kPairBytes; }
+    static const double * qu(const void * b, int64_t, int64_t) { return static_cast<const double *>(b); }
+    static const float * sums(const void * b, int64_t n_pairs, int64_t n_samp) {
+        return reinterpret_cast<const float *>(static_cast<const char *>(b) + (size_t)n_pairs * (size_t)n_samp * 16);
+    }
+    static const int32_t * word(const void * b, int64_t n_pairs, int64_t n_samp) {
+        return reinterpret_cast<const int32_t *>(static_cast<const char *>(b) + (size_t)n_pairs * (size_t)n_samp * 24);
+    }
 };
 
 struct Stats {
@@ -72,6 +99,9 @@ struct Stats {
     int64_t pack_no_room = 0;    // packs that found no free arena space
     int64_t live_seals = 0;
     uint64_t packed_bytes = 0;   // bytes in packed copies now
+    int64_t pair_packs = 0;      // packs that took the pair form
+    int64_t pair_demotions = 0;  // packs that tried the pair form (probe or full sweep) and published the plain one
+    int64_t pair_escapes = 0;    // escaped pair-samples in view of the live pair copies
 };
 
 // What a consumer launches with on a hit: packed arrays and, per detector of the call, its row in each and its cal.
@@ -80,6 +110,12 @@ struct Hit {
     const double * qu = nullptr;      // [rows][n_samp][2]
     std::vector<int32_t> pix_row, qu_row;
     std::vector<double> cal;
+    // the pair form (pix and qu stay nullptr): detectors (2 b, 2 b + 1) of the call are row pair_row[b] of the copy
+    bool pair = false;
+    const int32_t * word = nullptr;   // [pairs][n_samp]
+    const double * qu_a = nullptr;    // [pairs][n_samp][2]
+    const float * sums = nullptr;     // [pairs][n_samp][2]
+    std::vector<int32_t> pair_row;
 };
 
 class Registry {
@@ -136,6 +172,18 @@ private:
         void * packed = nullptr;
         size_t packed_bytes = 0;
     };
+    // A pair copy belongs to the pixel seal and the weight seal together: dropping either gives it up.
+    struct PairCopy {
+        uint64_t pix_id = 0, wts_id = 0;
+        void * block = nullptr;
+        size_t bytes = 0;
+        void * stream = nullptr;
+        int64_t n_pairs = 0;
+        int64_t n_samp = 0;
+        int64_t escapes = 0;
+        std::vector<int32_t> rows;                             // per pair in pack order: pixel A, pixel B, weight A, weight B
+        std::vector<std::pair<int32_t, int32_t>> by_pixel_a;   // (pixel row A, pair), sorted
+    };
     struct Lock;
     using Parting = std::vector<std::pair<void *, void *>>;   // (block, stream) to be given back
     void drop_at(size_t i, DropReason why, Parting & parting);   // mutex_ held; the blocks go to `parting`
@@ -143,10 +191,15 @@ private:
     void reap(bool wait);                        // mutex_ NOT held: try limbo_ again
     Seal * find(Kind kind, int device, void * stream, const void * base, int64_t n_samp);
     Seal * by_id(uint64_t id);
+    PairCopy * pair_of(uint64_t pix_id, uint64_t wts_id);
+    void release_pair_copy(size_t k, Parting & parting);             // mutex_ held; the block goes to `parting`
+    void drop_pair_copies_of(uint64_t seal_id, Parting & parting);   // mutex_ held
+    bool pair_hit(const PairCopy & pc, const int32_t * pixel_index, const int32_t * weight_index, int64_t n_det, Hit * out) const;
 
     Backend be_;
     std::mutex mutex_;
     std::vector<Seal> seals_;
+    std::vector<PairCopy> pair_copies_;
     Parting limbo_;              // blocks that could not be given back yet
     uint64_t next_id_ = 0;
     Stats st_;
@@ -163,7 +216,8 @@ Registry & global();
 // host memory against a model that knows when a hit is allowed (which = 0), or one named scenario (1: the pack happens on
 // the third call, 2: another interval list misses, 3: a reseal discards the copy, 4: eviction under allocation pressure,
 // 5: a non-whitelisted call drops every seal, 6: an expansion that does not seal still drops what it overwrites, 7: the
-// backend's pack comes back into the registry); "" when sound, else what went wrong
+// backend's pack comes back into the registry, 8: co-pointing pairs take the pair form and hit, 9: escapes over the threshold
+// demote to the plain form in the same call, 10: a call that splits a pair misses); "" when sound, else what went wrong
 std::string selftest(uint64_t seed, int n_ops, int which);
 
 }  // namespace pointing_cache

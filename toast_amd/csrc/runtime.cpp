@@ -1384,15 +1384,45 @@ void dev_pack(int kind, const void * src, void * dst, const int32_t * rows, int 
 
 bool dev_may_cache(void * stream) { return !deterministic_mode() && !stream_capturing(stream); }
 
+// The pair pack (or, dst = nullptr, its probe) and the blocking read-back of its escape count: a word of the small
+// arena, zeroed and read on `stream`.  Twice per packing call that reaches the sweep (probe, then sweep), once when the
+// probe already says no; the registry never calls this on a capturing stream (may_cache) nor with its lock held.
+int64_t dev_pack_pairs(const void * pixels, const void * weights, const int32_t * rows, int n_pairs, int64_t n_samp,
+                       const int64_t * ivl, int n_view, int64_t s_begin, int64_t s_end, void * dst, void * stream) {
+    if (!pair_detectors() || alloc_policy().plain) return -1;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    // (free space of slabs the arenas already hold, like the copies: the small arena may hold none)
+    void * word = small_arena().alloc(256, st, false);
+    if (word == nullptr) word = big_arena().alloc(256, st, false);
+    if (word == nullptr) return -1;
+    auto release = [&] { (void)(small_arena().release(word) || big_arena().release(word)); };
+    unsigned long long escaped = 0;
+    try {
+        TH_HIP(hipMemsetAsync(word, 0, sizeof(escaped), st));
+        launch_pointing_pack_pairs(static_cast<const int64_t *>(pixels), static_cast<const double *>(weights), rows, n_pairs, n_samp,
+                                   ivl, n_view, s_begin, s_end, dst, static_cast<unsigned long long *>(word), st);
+        TH_HIP(hipMemcpyAsync(&escaped, word, sizeof(escaped), hipMemcpyDeviceToHost, st));
+        TH_HIP(hipStreamSynchronize(st));
+    } catch (...) {
+        (void)hipStreamSynchronize(st);
+        release();
+        throw;
+    }
+    release();   // (nothing queued reads it any more)
+    return (int64_t)escaped;
+}
+
 void print_stats_at_exit() {
     const Stats s = global().stats();
     std::fprintf(stderr,
                  "[toast_hip] pointing cache: seals %lld packs %lld hits %lld misses %lld evictions %lld pack_no_room %lld "
-                 "packed_bytes %llu drops{foreign_call %lld overlap_write %lld free %lld manager %lld reseal %lld explicit %lld}\n",
+                 "packed_bytes %llu drops{foreign_call %lld overlap_write %lld free %lld manager %lld reseal %lld explicit %lld} "
+                 "pair_packs %lld pair_demotions %lld pair_escapes %lld\n",
                  (long long)s.seals, (long long)s.packs, (long long)s.hits, (long long)s.misses, (long long)s.evictions,
                  (long long)s.pack_no_room, (unsigned long long)s.packed_bytes, (long long)s.drops[kDropForeignCall],
                  (long long)s.drops[kDropOverlapWrite], (long long)s.drops[kDropFree], (long long)s.drops[kDropManager],
-                 (long long)s.drops[kDropReseal], (long long)s.drops[kDropExplicit]);
+                 (long long)s.drops[kDropReseal], (long long)s.drops[kDropExplicit], (long long)s.pair_packs,
+                 (long long)s.pair_demotions, (long long)s.pair_escapes);
 }
 
 }  // namespace
@@ -1400,7 +1430,7 @@ void print_stats_at_exit() {
 Registry & global() {
     // (never destroyed: nothing of it may run into the runtime's own exit)
     static Registry * const r = [] {
-        static const Backend be = {dev_block_of, dev_take, dev_give, dev_pack, dev_may_cache};
+        static const Backend be = {dev_block_of, dev_take, dev_give, dev_pack, dev_may_cache, dev_pack_pairs};
         Registry * reg = new Registry(be);
         const char * e = std::getenv("TOAST_HIP_POINTING_CACHE");
         if (e != nullptr && e[0] == '0') reg->enable(false);
@@ -1546,6 +1576,9 @@ int toast_hip_pointing_cache_stats(toast_hip_pointing_cache_stats_t * out) {
         out->pack_no_room = s.pack_no_room;
         out->live_seals = s.live_seals;
         out->packed_bytes = s.packed_bytes;
+        out->pair_packs = s.pair_packs;
+        out->pair_demotions = s.pair_demotions;
+        out->pair_escapes = s.pair_escapes;
     });
 }
 

@@ -49,6 +49,11 @@ void pointing_cache_entered(const char * fn) noexcept;
 // kernels.hip: the pack kernels of the pointing cache, queued on st (kind: pointing_cache::Kind)
 void launch_pointing_pack(int kind, const void * src, void * dst, const int32_t * rows, int n_rows, int64_t n_samp,
                           hipStream_t st);
+// ... and the pair form's (pointing_cache::Backend::pack_pairs; dst = nullptr: only the count); *d_escaped += the
+// pair-samples of [s_begin, s_end) inside ivl that the form cannot express
+void launch_pointing_pack_pairs(const int64_t * pixels, const double * weights, const int32_t * rows, int n_pairs,
+                                int64_t n_samp, const int64_t * ivl, int n_view, int64_t s_begin, int64_t s_end, void * dst,
+                                unsigned long long * d_escaped, hipStream_t st);
 
 // the device that is current (0 when the runtime cannot say)
 inline int current_device() {
