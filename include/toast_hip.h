@@ -1625,6 +1625,77 @@ int toast_hip_filterbin_det_tile(int64_t order);
 int toast_hip_filterbin_max_order(void);
 
 /* ------------------------------------------------------------------------------------
+ * HWP-synchronous signal model (csrc/hwpss.hip; ops.HWPSynchronousModel).  Replaces the per-sample work of
+ * src/toast/ops/hwpss_model.py and src/toast/hwp_utils.py:43-392; the small dense solves stay on the host.
+ *
+ * The model of a detector and chunk has n_coeff coefficients: 2 * harmonics of them in the order [sin_1, cos_1, sin_2,
+ * ...] or, with time_drift, 4 * harmonics in the order [sin_h, t sin_h, cos_h, t cos_h] per harmonic (the order of the code,
+ * hwp_utils.py:147-222, not of its docstring).  basis_k(i) is the matching product of sin / cos((double)(h + 1) *
+ * d_angle[i]) and d_reltime[i] (needed with time_drift and for splines).  d_shared [n_samp] is the COMBINED shared
+ * flag byte (mask applied, HWP stopped, outside the chunk view: hwpss_model.py:898-916): a sample is shared-good where
+ * it is 0, and good for detector d where it is shared-good and (det_flags[flag_index[d]][i] & det_flag_mask) == 0.
+ * NULL d_shared / d_det_flags flag nothing.  Signals and flags are rows of n_samp samples; the row index arrays are on
+ * the host.  1 <= n_coeff <= toast_hip_hwpss_max_coeff() (36: 9 harmonics with time_drift).  fp64 throughout, no atomics:
+ * a sum runs over the samples of a tile of toast_hip_hwpss_chunk() samples of its chunk in order, then over the tiles
+ * in order.
+ *
+ * toast_hip_hwpss_gram_dev (hwp_utils.py:139-231 without the n_samp / n_good scaling): for every chunk
+ * [starts[c], min(ends[c], n_samp)) -- chunks may overlap -- the upper triangle of M^T M over the shared-good samples
+ * into d_gram [n_chunk][n_coeff][n_coeff] (the lower triangle is zero) and their number into d_n_good [n_chunk].  Like
+ * the reference it depends on the shared flags only.
+ *
+ * toast_hip_hwpss_project_dev (hwpss_model.py:807-818, hwp_utils.py:287-310): per detector and chunk, into
+ * [n_det][n_chunk] arrays, d_n_good = the number of the detector's good samples, d_mean = the mean of the signal over
+ * them (0 without one), and d_rhs [n_det][n_chunk][n_coeff] = sum over them of (signal - mean) basis_k.  The signal of
+ * a flagged sample is replaced by zero, not multiplied by it: a NaN there reaches no sum (the rule of
+ * toast_hip_template_fit_dev).  The mean is a compensated sum kept as a pair hi + lo and the right-hand side
+ * accumulates (signal - hi) - lo, so a constant of any size in front of the HWPSS costs no digits.  The basis values of
+ * a sample are formed once per workgroup, in LDS, for its toast_hip_hwpss_det_tile() detectors.
+ *
+ * toast_hip_hwpss_subtract_dev (hwp_utils.py:318-392, hwpss_model.py:325-335, :573-578), one sweep over all samples:
+ *   flag value fv = (det_flags & det_flag_mask) | shared; det_flags |= (uint8)(fv * hwp_flag_mask) -- the reference's
+ *   uint8 PRODUCT of the value, not of a boolean -- for every listed detector;
+ *   for a detector with active[d] != 0: model = sum_k c_k(i) basis_k(i) in coefficient order, and signal -= model on
+ *   its good samples when `subtract`; d_sum / d_count [n_det] receive the sum and the number of its (cleaned) good
+ *   samples.
+ * Coefficients: d_coeff [n_det][n_coeff] (fixed), or, when d_coeff is NULL, one cubic B-spline per detector and
+ * coefficient: knots spl_t and coefficients spl_c (device, as scipy.interpolate.splrep returns them: as many c as t)
+ * at [spl_offset[d n_coeff + k], spl_offset[d n_coeff + k + 1]) (host, n_det n_coeff + 1 entries; at least 8 knots for
+ * an active detector), evaluated at d_reltime[i] the way FITPACK's splev(ext=0) does: the basis functions of the span
+ * that holds the time, the span clamped to the first / last one so that times outside the knots extrapolate.
+ * d_relcal (float rows, NULL: none; splines only): cal_center / sqrt(c_2f_sin^2 + c_2f_cos^2) from the interpolated
+ * coefficients on the good samples of an active detector and cal_center / 1 on its other samples -- the reference sets
+ * the magnitude, not the calibration, to one where fv != 0 (hwpss_model.py:578, :347).
+ *
+ * toast_hip_hwpss_remove_mean_dev (hwpss_model.py:334-335): signal -= d_sum / d_count on the good samples of every
+ * active detector with d_count > 0.  (The flag update never changes which samples are good.)
+ * ---------------------------------------------------------------------------------- */
+int toast_hip_hwpss_det_tile(void);
+int toast_hip_hwpss_chunk(void);
+int toast_hip_hwpss_max_coeff(void);
+int toast_hip_hwpss_gram_dev(int64_t n_samp, int64_t harmonics, int time_drift, const double * d_angle,
+                             const double * d_reltime, const uint8_t * d_shared, const int64_t * starts /*host*/,
+                             const int64_t * ends /*host*/, int64_t n_chunk, double * d_gram, int64_t * d_n_good,
+                             void * stream);
+int toast_hip_hwpss_project_dev(int64_t n_samp, int64_t harmonics, int time_drift, const double * d_angle,
+                                const double * d_reltime, const uint8_t * d_shared, const int32_t * signal_index /*host*/,
+                                const double * d_signal, const int32_t * flag_index /*host*/, const uint8_t * d_det_flags,
+                                uint8_t det_flag_mask, int64_t n_det, const int64_t * starts /*host*/,
+                                const int64_t * ends /*host*/, int64_t n_chunk, int64_t * d_n_good, double * d_mean,
+                                double * d_rhs, void * stream);
+int toast_hip_hwpss_subtract_dev(int64_t n_samp, int64_t harmonics, int time_drift, const double * d_angle,
+                                 const double * d_reltime, const uint8_t * d_shared, const int32_t * signal_index /*host*/,
+                                 double * d_signal, const int32_t * flag_index /*host*/, uint8_t * d_det_flags,
+                                 uint8_t det_flag_mask, uint8_t hwp_flag_mask, int64_t n_det, const int32_t * active /*host*/,
+                                 int subtract, const double * d_coeff, const int64_t * spl_offset /*host*/,
+                                 const double * d_spl_t, const double * d_spl_c, const int32_t * relcal_index /*host*/,
+                                 float * d_relcal, double cal_center, double * d_sum, int64_t * d_count, void * stream);
+int toast_hip_hwpss_remove_mean_dev(int64_t n_samp, const uint8_t * d_shared, const int32_t * signal_index /*host*/,
+                                    double * d_signal, const int32_t * flag_index /*host*/, const uint8_t * d_det_flags,
+                                    uint8_t det_flag_mask, int64_t n_det, const int32_t * active /*host*/,
+                                    const double * d_sum, const int64_t * d_count, void * stream);
+
+/* ------------------------------------------------------------------------------------
  * Deterministic debug mode (TOAST_HIP_DETERMINISTIC=1 in the environment, or this switch).
  * The production A^T kernels add run-reduced partial sums with fp64 atomics, so zmap / the
  * inverse covariance differ from run to run in the last bits.  With the mode on,

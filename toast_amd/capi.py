@@ -2226,6 +2226,78 @@ class _Dev:
     def filterbin_max_order(self):
         return int(real_lib().toast_hip_filterbin_max_order())
 
+    # ---- HWP-synchronous signal model (csrc/hwpss.hip)
+    def hwpss_det_tile(self):
+        """Detectors that share one workgroup's basis values."""
+        return int(real_lib().toast_hip_hwpss_det_tile())
+
+    def hwpss_chunk(self):
+        """Samples of a chunk per workgroup: one run of every sum."""
+        return int(real_lib().toast_hip_hwpss_chunk())
+
+    def hwpss_max_coeff(self):
+        """Largest number of model coefficients per detector and chunk the kernels take."""
+        return int(real_lib().toast_hip_hwpss_max_coeff())
+
+    def hwpss_gram(self, n_samp, harmonics, time_drift, d_angle, d_reltime, d_shared, starts, ends, d_gram, d_n_good,
+                   stream=0):
+        """Upper triangle of M^T M over the shared-good samples of every chunk and their number.
+        toast_hip_hwpss_gram_dev."""
+        st, en = self._small(starts, np.int64), self._small(ends, np.int64)
+        if st.size != en.size:
+            raise RuntimeError("hwpss_gram: one start and one end per chunk")
+        _check(lib().toast_hip_hwpss_gram_dev(
+            _i64(n_samp), _i64(harmonics), _int(time_drift), _p(d_angle), _p(d_reltime or None), _p(d_shared or None),
+            _p(st), _p(en), _i64(st.size), _p(d_gram), _p(d_n_good), _p(stream)))
+
+    def hwpss_project(self, n_samp, harmonics, time_drift, d_angle, d_reltime, d_shared, signal_index, d_signal,
+                      flag_index, d_det_flags, det_flag_mask, starts, ends, d_n_good, d_mean, d_rhs, stream=0):
+        """Good counts, means and right-hand sides [n_det][n_chunk]([n_coeff]).  toast_hip_hwpss_project_dev."""
+        si = self._small(signal_index, np.int32)
+        fi = None if flag_index is None else self._small(flag_index, np.int32)
+        st, en = self._small(starts, np.int64), self._small(ends, np.int64)
+        if st.size != en.size or (fi is not None and fi.size != si.size):
+            raise RuntimeError("hwpss_project: starts / ends or signal / flag rows do not match")
+        _check(lib().toast_hip_hwpss_project_dev(
+            _i64(n_samp), _i64(harmonics), _int(time_drift), _p(d_angle), _p(d_reltime or None), _p(d_shared or None),
+            _p(si), _p(d_signal), _p(fi), _p(d_det_flags or None), _u8(int(det_flag_mask) & 255), _i64(si.size), _p(st),
+            _p(en), _i64(st.size), _p(d_n_good), _p(d_mean), _p(d_rhs), _p(stream)))
+
+    def hwpss_subtract(self, n_samp, harmonics, time_drift, d_angle, d_reltime, d_shared, signal_index, d_signal,
+                       flag_index, d_det_flags, det_flag_mask, hwp_flag_mask, active, subtract, d_sum, d_count,
+                       d_coeff=0, spl_offset=None, d_spl_t=0, d_spl_c=0, relcal_index=None, d_relcal=0, cal_center=1.0,
+                       stream=0):
+        """Flag update, model subtraction, calibration rows and the sums of the cleaned good samples in one sweep;
+        fixed coefficients ``d_coeff`` or packed splines.  toast_hip_hwpss_subtract_dev."""
+        si = self._small(signal_index, np.int32)
+        fi = None if flag_index is None else self._small(flag_index, np.int32)
+        ac = self._small(active, np.int32)
+        so = None if spl_offset is None else self._small(spl_offset, np.int64)
+        ri = None if relcal_index is None else self._small(relcal_index, np.int32)
+        n_coeff = int(harmonics) * (4 if time_drift else 2)
+        if ac.size != si.size or (fi is not None and fi.size != si.size) or (ri is not None and ri.size != si.size):
+            raise RuntimeError("hwpss_subtract: one flag row, calibration row and switch per detector")
+        if so is not None and so.size != si.size * n_coeff + 1:
+            raise RuntimeError("hwpss_subtract: the spline offsets have n_det n_coeff + 1 entries")
+        _check(lib().toast_hip_hwpss_subtract_dev(
+            _i64(n_samp), _i64(harmonics), _int(time_drift), _p(d_angle), _p(d_reltime or None), _p(d_shared or None),
+            _p(si), _p(d_signal), _p(fi), _p(d_det_flags or None), _u8(int(det_flag_mask) & 255),
+            _u8(int(hwp_flag_mask) & 255), _i64(si.size), _p(ac), _int(subtract), _p(d_coeff or None), _p(so),
+            _p(d_spl_t or None), _p(d_spl_c or None), _p(ri), _p(d_relcal or None), C.c_double(float(cal_center)),
+            _p(d_sum), _p(d_count), _p(stream)))
+
+    def hwpss_remove_mean(self, n_samp, d_shared, signal_index, d_signal, flag_index, d_det_flags, det_flag_mask, active,
+                          d_sum, d_count, stream=0):
+        """``signal -= sum / count`` on the good samples of the active detectors.  toast_hip_hwpss_remove_mean_dev."""
+        si = self._small(signal_index, np.int32)
+        fi = None if flag_index is None else self._small(flag_index, np.int32)
+        ac = self._small(active, np.int32)
+        if ac.size != si.size or (fi is not None and fi.size != si.size):
+            raise RuntimeError("hwpss_remove_mean: one flag row and switch per detector")
+        _check(lib().toast_hip_hwpss_remove_mean_dev(
+            _i64(n_samp), _p(d_shared or None), _p(si), _p(d_signal), _p(fi), _p(d_det_flags or None),
+            _u8(int(det_flag_mask) & 255), _i64(si.size), _p(ac), _p(d_sum), _p(d_count), _p(stream)))
+
     def test_math(self, op, n, d_a, d_b, d_out, stream=0):
         _check(lib().toast_hip_test_math_dev(C.c_int(op), _i64(n), _p(d_a), _p(d_b), _p(d_out), _p(stream)))
 

@@ -294,7 +294,7 @@ public:
 
     static constexpr int kScratchFftTime = 0, kScratchFftFreq = 1, kScratchDot = 2, kScratchFftWork = 3,
                          kScratchSort = 4, kScratchFftImpulse = 5, kScratchCommA = 6, kScratchCommB = 7, kScratchStatus = 8, kScratchPoly = 9,
-                         kScratchTemplate = 10, kScratchSimNoise = 11, kScratchNoiseEstim = 12, kScratchNoiseEstimHp = 13, kScratchAtm = 14;
+                         kScratchTemplate = 10, kScratchSimNoise = 11, kScratchNoiseEstim = 12, kScratchNoiseEstimHp = 13, kScratchAtm = 14, kScratchHwpss = 15;
 
 private:
     std::map<std::pair<int, int>, std::pair<void *, size_t>> scratch_;   // (device, slot) -> (ptr, bytes)

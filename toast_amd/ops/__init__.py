@@ -19,6 +19,7 @@ from .mapmaker_solve import SolverLHS, SolverRHS, TemplateMatrix, solve
 from .demodulation import Demodulate, StokesWeightsDemod
 from .filterbin import FilterBin
 from .ground_filter import GroundFilter
+from .hwpss_model import HWPSynchronousModel
 from .noise_estimation import NoiseEstim
 from .noise_filter import NoiseFilter
 from .operator import Operator

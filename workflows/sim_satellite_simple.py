@@ -8,13 +8,18 @@ configs[0] (4 detectors x 10 min @ 100 Hz, Nside 64) by default, configs[1] with
 
     python workflows/sim_satellite_simple.py [--ndet 4] [--minutes 10] [--rate 100] [--nside 64]
                                              [--destripe] [--sim-noise] [--estimate-noise] [--out map.npz]
-                                             [--demodulate [--nskip N] [--hwp-rpm R]]
+                                             [--demodulate [--nskip N] [--hwp-rpm R] [--hwpss AMP]]
                                              [--gain-drift ORDER [--noise-free]]
                                              [--dipole {solar,orbital,total}]
 
 ``--demodulate``: the HWP spins at ``--hwp-rpm`` (default 120, i.e. 2 Hz), a piecewise-constant input sky is scanned into
 the signal, and after the usual (modulated) map the data goes through Demodulate -> StokesWeightsDemod -> the same
 binning / ``--destripe`` map-maker; the residual of both maps against the input sky is printed.
+
+``--hwpss AMP`` (with ``--demodulate``): an HWP-synchronous signal -- harmonics 1, 2 and 4 of the HWP angle, the 2f line
+``AMP`` times the rms of the scanned signal, a few per cent of scatter between detectors -- is added to the signal.  The
+data is demodulated and mapped once as it is (residual printed), then ops.HWPSynchronousModel subtracts its model and the
+usual modulated and demodulated runs follow.
 
 ``--gain-drift ORDER``: the input sky is scanned into a detdata key of its own, the *signal estimate*; the signal is
 ``estimate * (1 + L a_injected)`` -- a Legendre series of that order per detector, a few per cent -- plus the usual noise
@@ -134,7 +139,21 @@ def report_gain_drift(data, mapper, injected):
           f"{np.sqrt(np.mean(injected ** 2)):.3e}")
 
 
-def demodulate_and_map(data, args, sky):
+def add_hwpss(data, amp, det_data):
+    """Add an HWP-synchronous signal to every detector: harmonics 1, 2 and 4 of the HWP angle, ``amp`` times the rms of the
+    scanned signal at 2f (0.4 and 0.25 of that at 1f and 4f), with a few per cent of scatter between the detectors."""
+    rng = np.random.default_rng(7)
+    for ob in data.obs:
+        sig = ob.detdata[det_data].data
+        angle = ob.shared[defaults.hwp_angle].data
+        level = amp * float(np.sqrt(np.mean((sig - sig.mean(axis=1, keepdims=True)) ** 2)))
+        for d in range(sig.shape[0]):
+            for h, rel in ((1, 0.4), (2, 1.0), (4, 0.25)):
+                sig[d] += level * rel * (1 + 0.03 * rng.standard_normal()) * np.sin(h * angle + rng.uniform(0, 2 * np.pi))
+    print(f"HWPSS added to '{det_data}': 2f amplitude {level:.4g} = {amp:g} x the rms of the scanned signal")
+
+
+def demodulate_and_map(data, args, sky, label="demodulated run"):
     """Demodulate -> StokesWeightsDemod -> the same map-maker on the pseudo-detectors."""
     from toast_amd.accel import accel_enabled
 
@@ -156,9 +175,9 @@ def demodulate_and_map(data, args, sky):
     m = demod_data["mapmaker_map"].data
     good = hits[:, :, 0] > 0
     n_pseudo = sum(len(ob.local_detectors) for ob in demod_data.obs)
-    print(f"demodulated run: {n_pseudo} pseudo-detectors x {demod_data.obs[0].n_local_samples} samples (nskip {args.nskip})  "
+    print(f"{label}: {n_pseudo} pseudo-detectors x {demod_data.obs[0].n_local_samples} samples (nskip {args.nskip})  "
           f"hit pixels {np.count_nonzero(good)}  wall {time.time() - t0:.2f} s")
-    print("demodulated run: " + residual(m, good, sky, demod_data["pixel_dist"]))
+    print(f"{label}: " + residual(m, good, sky, demod_data["pixel_dist"]))
     return demod_data
 
 
@@ -181,6 +200,9 @@ def main(argv=None):
                          "pseudo-detectors; prints both maps' residual against the input sky")
     ap.add_argument("--nskip", type=int, default=3, help="decimation factor of --demodulate")
     ap.add_argument("--hwp-rpm", type=float, default=None, help="HWP rotation rate (9, or 120 with --demodulate)")
+    ap.add_argument("--hwpss", type=float, default=None, metavar="AMP",
+                    help="with --demodulate: add an HWP-synchronous signal of AMP times the sky rms per detector, demodulate "
+                         "and map it once as it is, then remove it with ops.HWPSynchronousModel before everything else")
     ap.add_argument("--gain-drift", type=int, default=None, metavar="ORDER",
                     help="inject a Legendre gain drift of this order per detector on a scanned input sky and solve for "
                          "[Offset, GainTemplate]; prints injected against recovered amplitudes")
@@ -195,6 +217,8 @@ def main(argv=None):
         ap.error("--gain-drift takes an order >= 0 and does not combine with --demodulate")
     if args.noise_free and not gain:
         ap.error("--noise-free belongs to --gain-drift")
+    if args.hwpss is not None and not args.demodulate:
+        ap.error("--hwpss belongs to --demodulate")
 
     n_samp = int(args.minutes * 60 * args.rate)
     t0 = time.time()
@@ -218,6 +242,23 @@ def main(argv=None):
         from toast_amd.accel import accel_enabled
 
         ops.SimNoise(noise_model=defaults.noise_model).apply(data, use_accel=accel_enabled())
+    if args.hwpss is not None:
+        from toast_amd.accel import accel_enabled
+
+        add_hwpss(data, args.hwpss, defaults.det_data)
+        demodulate_and_map(data, args, sky, label="demodulated run, HWPSS left in")
+        for key in ("pixel_dist", "mapmaker_hits", "mapmaker_map"):
+            if key in data:
+                del data[key]
+        # Every sample is modelled and cleaned (no flags): the operator subtracts from good samples only, a flagged sample
+        # would keep its HWPSS (the reference fills such gaps with noise, fill_gaps) and Demodulate's filters spread it.
+        # The operator also removes each detector's mean; the level the detector had before (the HWPSS adds next to
+        # nothing to it over whole turns) is put back so that the I map can be compared.
+        level = [ob.detdata[defaults.det_data].data.mean(axis=1, keepdims=True) for ob in data.obs]
+        ops.HWPSynchronousModel(subtract_model=True, det_flags=None, shared_flags=None).apply(data, use_accel=accel_enabled())
+        for ob, dc in zip(data.obs, level):
+            ob.detdata[defaults.det_data].data[:] += dc
+        print("HWPSynchronousModel: one chunk, 9 harmonics, model subtracted from every sample, detector levels restored")
     if args.estimate_noise:
         ops.NoiseEstim(out_model="measured_noise", lagmax=min(10000, n_samp // 4)).apply(data)
         for ob in data.obs:
